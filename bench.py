@@ -12,9 +12,10 @@ already resident in HBM (the reference engine keeps its pre-generated input sets
 memory and a request only names (batch_id, batch_size): inferenceEngine.py:83,200-215).
 `--steps 20 --warmup 5` therefore times 1 638 400 queries (~12 s on one MI355X: long enough for an
 outside sampler of GPU activity to see it) after 409 600 untimed ones: the launch pipeline and the
-chip's power state are in steady state, and p99 is taken over every query of the region.  The
-outputs of the region's last launch sets are checked against the CPU oracle afterwards
-(`verified`).  Queries are submitted through the C ABI
+chip's power state are in steady state, and p99 is taken over every query of the region.  With
+`--full` the outputs of the region's last launch sets are checked against the CPU oracle afterwards
+(`verified`), and the other legs below run too; a plain run sets up, warms up, times the K steps and
+prints its line.  Queries are submitted through the C ABI
 (include/drs.h), `--coalesce` per launch set and `--slots` sets in flight; a query's latency
 runs from the submit of its launch set to the moment its result is observed on the host.
 
@@ -107,10 +108,17 @@ def parse(argv=None):
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--cpu_table", default="", help="cpu_baseline: also write the reference's `***` latency table "
                     "(ms per iteration at batch 1 .. 1024, one CPU engine) to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the benchmark measures or checks beside the timed steps: the oracle check of "
+                         "the timed region's outputs (`verified`), the GPU's clocks and power around it (`gpu_state`), "
+                         "the hip-event / single-query / gather-alone / host-input legs and the CPU baseline")
     ap.add_argument("--timed_only", action="store_true",
-                    help="warm-up + timed region only: skip the cross-check / single-query / host-input "
-                         "legs and the CPU baseline (profiling runs: every gather launch rocprofv3 sees "
-                         "is then a launch of the benchmark itself)")
+                    help="with --full: warm-up + timed region only: skip the oracle check, the cross-check / "
+                         "single-query / host-input legs and the CPU baseline (profiling runs: every gather launch "
+                         "rocprofv3 sees is then a launch of the benchmark itself)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned for a fixed sample (drawn from "
+                         "--seed) of the queries of its last step to DIR/outputs.npy: float32 [queries, batch, n_out]")
     ap.add_argument("--collective", default="rccl", choices=("rccl", "gloo"),
                     help="N > 1: how the run statistics are combined (rccl = drs_stats_allreduce)")
     ap.add_argument("--sweep", action="store_true", help="also A/B the gather variants (stderr)")
@@ -194,9 +202,32 @@ def trace_inputs(opt, args, m_den, rows, L):
 
 
 MID_SETS = 16     # launch sets of the timed region whose outputs are kept for the oracle (beside the last `slots` ones)
+DUMP_QUERIES = 1024          # --dump-outputs: queries of the last step whose outputs are written ...
+DUMP_BYTES = 64 << 20        # ... and at most this many bytes of them
 
 
-def run_queries(eng, n, bs, nb, slots, lat=None, start_id=0, coalesce=1, tail=None, mid=None):
+def dump_sample(opt, n_timed, per_step, n_out):
+    """--dump-outputs: the queries (numbered from 0 in the timed region) whose outputs are written -- a fixed sample,
+    drawn from --seed, of the last step's queries, so that two builds run with the same arguments write the outputs
+    of the same queries.  Returns {query number: None}; run_queries() fills in the outputs."""
+    m = max(1, min(per_step, DUMP_QUERIES, DUMP_BYTES // (opt.batch * n_out * 4)))
+    picked = np.random.RandomState(opt.seed).choice(per_step, m, replace=False)
+    return {n_timed - per_step + int(q): None for q in np.sort(picked)}
+
+
+def _take(keep, q0, out, bs):
+    """The outputs of the queries in `keep` among those of one launch set, whose first query is number q0."""
+    for k in range(len(out) // bs):
+        if q0 + k in keep:
+            keep[q0 + k] = out[k * bs:(k + 1) * bs]
+
+
+def write_outputs(path, keep):
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "outputs.npy"), np.stack([keep[q] for q in sorted(keep)]).astype(np.float32))
+
+
+def run_queries(eng, n, bs, nb, slots, lat=None, start_id=0, coalesce=1, tail=None, mid=None, keep=None):
     """Closed loop: exactly n queries, `coalesce` of them per launch set, `slots` launch
     sets in flight.  Every query's latency runs from the submit of its launch set to the
     moment the set's results are observed on the host.  Returns elapsed seconds.
@@ -205,21 +236,29 @@ def run_queries(eng, n, bs, nb, slots, lat=None, start_id=0, coalesce=1, tail=No
     (batch ids, outputs [sum(bs), n_out]): what verify_tail() checks against the oracle.
     mid (a list): MID_SETS launch sets spread evenly over the region are collected WITH their outputs as well
     (one host copy of bs * coalesce * n_out floats each, at the moment the set's slot is reused) and appended the
-    same way: samples from all along the pipelined stream, not only from its drain."""
+    same way: samples from all along the pipelined stream, not only from its drain.
+    keep (a dict {query number: None}, queries numbered from 0 in this call): the launch sets that carry those
+    queries are waited for WITH an output buffer as well, and each such query's [bs, n_out] outputs go into `keep`."""
     t_submit = [0.0] * slots
     in_slot = [0] * slots
     ids_in = [None] * slots
     t0 = time.perf_counter()
     i = g = 0
     n_sets = -(-n // max(1, coalesce))
-    g_mid = {int((k + 0.5) * n_sets / MID_SETS) for k in range(MID_SETS)} if mid is not None else ()
+    g_mid = {int((k + 0.5) * n_sets / MID_SETS) for k in range(MID_SETS)} if mid is not None else set()
+    g_keep = {q // coalesce for q in keep} if keep is not None else set()     # set g carries queries g*coalesce ..
+    g_out = g_mid | g_keep
     set_no = [-1] * slots
     while i < n:
         c = min(coalesce, n - i)
         s = g % slots
         if in_slot[s]:
-            if set_no[s] in g_mid:
-                mid.append((ids_in[s], eng.wait(s, bs * in_slot[s])))
+            if set_no[s] in g_out:
+                out = eng.wait(s, bs * in_slot[s])
+                if set_no[s] in g_mid:
+                    mid.append((ids_in[s], out))
+                if set_no[s] in g_keep:
+                    _take(keep, set_no[s] * coalesce, out, bs)
             else:
                 eng.wait(s)
             if lat is not None:
@@ -237,11 +276,13 @@ def run_queries(eng, n, bs, nb, slots, lat=None, start_id=0, coalesce=1, tail=No
     for k in range(slots):
         s = (g + k) % slots
         if in_slot[s]:
-            out = eng.wait(s, None if tail is None else bs * in_slot[s])
+            out = eng.wait(s, None if tail is None and set_no[s] not in g_keep else bs * in_slot[s])
             if lat is not None:
                 lat.extend([time.perf_counter() - t_submit[s]] * in_slot[s])
             if tail is not None:
                 tail.append((ids_in[s], out))
+            if set_no[s] in g_keep:
+                _take(keep, set_no[s] * coalesce, out, bs)
             in_slot[s] = 0
     return time.perf_counter() - t0
 
@@ -754,7 +795,9 @@ def main():
         # the job's statistics have been combined (8 ranks x 8 spinning threads on 16 CPUs)
         host_threads = max(0, min(7, job_cores // world - 1))
         eng.set_option("host_threads", host_threads)
-    state_before = gpu_state(local) if rank == 0 else None
+    check = opt.full and not opt.timed_only          # the oracle check and the legs beside the timed region
+    state_before = gpu_state(local) if rank == 0 and opt.full else None
+    keep = dump_sample(opt, n_timed, qps_, eng.n_out) if opt.dump_outputs and rank == 0 else None
     # warmup
     run_queries(eng, n_warm, bs, nb, slots, coalesce=co)
     # timed region: exactly K steps (K * queries_per_step queries) per rank, barrier + device sync
@@ -762,11 +805,11 @@ def main():
     # the results: no copy, no sync, no extra launch) stays on inside it, so the roofline figure is
     # taken over the timed region itself; the engine adds up the algorithmic bytes of exactly the
     # launches it timed (a trailing partial launch set counts with its own bytes).
-    lat, tail, mid = [], [], []
+    lat, tail, mid = [], ([] if check else None), ([] if check else None)
     eng.reset_kernel_time()
     eng.set_profiling(1)
     barrier()
-    elapsed = run_queries(eng, n_timed, bs, nb, slots, lat, coalesce=co, tail=tail, mid=mid)
+    elapsed = run_queries(eng, n_timed, bs, nb, slots, lat, coalesce=co, tail=tail, mid=mid, keep=keep)
     barrier()
     eng.set_profiling(0)
     sls_ms, sls_n = eng.kernel_time(N.KERNEL_SLS_CLOCK)
@@ -783,9 +826,11 @@ def main():
     elif dist is not None:
         tot_elapsed, tot_queries, hist = stats.allreduce_run_stats(dist, elapsed, n_timed, hist)
     p50, p95, p99 = (stats.percentile_from_histogram(hist, q) for q in (50, 95, 99))
-    state_after = gpu_state(local) if rank == 0 else None
+    state_after = gpu_state(local) if rank == 0 and opt.full else None
+    if keep is not None:
+        write_outputs(opt.dump_outputs, keep)
 
-    extra = not opt.timed_only and rank == 0
+    extra = check and rank == 0
     ev_ms = ev_n = ev_bytes = mlp_ms = mlp_n = one_ms = one_n = one_bytes = alone_ms = alone_n = alone_bytes = 0
     if extra:
         # cross-check leg (not part of `value`): HIP events recorded around the gather launch on the
@@ -1001,8 +1046,9 @@ def main():
                 "what": "2 x batch x MACs of the bottom / top (/ task) FC layers x queries/s, all %d GPU(s); "
                         "peak = dense fp32 MFMA (v_mfma_f32_16x16x4_f32) of one MI355X x n_gpus" % world,
             }
-        out["gpu_state"] = {"device": local, "before_warmup": state_before, "after_timed_region": state_after}
-        if not opt.timed_only:
+        if opt.full:
+            out["gpu_state"] = {"device": local, "before_warmup": state_before, "after_timed_region": state_after}
+        if check:
             # the results the timed region itself produced, checked after the fact (VERDICT r3 #1c)
             try:
                 os.sched_setaffinity(0, job_mask)    # (the oracle check runs on every core of the host; the timed region is over)
@@ -1013,7 +1059,7 @@ def main():
             except Exception as e:      # noqa: BLE001  (the line must still come out; "ok" is then absent)
                 out["verified"] = {"verified_queries": 0, "error": repr(e)[:300]}
             out["verified_queries"] = out["verified"].get("verified_queries", 0)
-        if not opt.no_cpu_baseline and not opt.timed_only and world == 1:
+        if check and not opt.no_cpu_baseline and world == 1:
             os.sched_setaffinity(0, job_mask)        # the CPU legs get every core of the host, not the GPU's NUMA node only
             out["cpu_baseline"] = cpu_baseline(opt, net, data, opt.cpu_seconds)
         print(json.dumps(out), file=json_out, flush=True)

@@ -229,9 +229,9 @@ def test_bench_rank_entry_world_size_2_end_to_end_on_cpu():
     assert one["n_gpus"] == 1 and one["latency_ms"]["queries"] == 60 and one["config"]["collective"] is None
     # identical line structure at N = 1 and N = 2
     assert set(one) == set(two) and set(one["roofline"]) == set(two["roofline"])
-    # without --timed_only the line carries the check of the timed region's own outputs against the oracle
+    # with --full (and without --timed_only) the line carries the check of the timed region's own outputs against the oracle
     tiny = [a for a in _TINY if a != "--timed_only"]
-    chk = _bench(["--gpus", "1"] + tiny, cpu, cpu_abi=True)
+    chk = _bench(["--gpus", "1", "--full"] + tiny, cpu, cpu_abi=True)
     assert chk["verified"]["ok"] is True and chk["verified_queries"] == chk["verified"]["verified_queries"] > 0
 
 
@@ -308,7 +308,8 @@ def test_bench_line_verifies_the_timed_regions_own_outputs():
     """VERDICT r3 #1c, r4 #1: what the pipelined engine produced for the LAST launch sets of the timed region and for sixteen sets spread over it
     (default flat gather, 12 queries per set, 3 sets in flight, MLP on its own stream) is compared with the
     oracle's forward inside bench.py, at BASELINE configs[1]'s full size."""
-    out = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--queries_per_step", "3000", "--no_cpu_baseline"])
+    out = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--queries_per_step", "3000", "--no_cpu_baseline",
+                  "--full"])
     v = out["verified"]
     # the last three sets and (round 6) sixteen sets spread evenly over the timed region: 19 x 12 queries
     assert v["ok"] is True and v["launch_sets"] == 19 and v["mid_region_sets"] == 16 and out["verified_queries"] == 228
@@ -491,7 +492,8 @@ def test_bench_cpu_baseline_has_the_reference_serving_shape_leg(tmp_path):
     reference's `***` table; `kind` / `leg` name the leg whose value is reported."""
     tab = str(tmp_path / "results_rm1.txt")
     out = _bench(["--workload", "tiny", "--steps", "1", "--warmup", "1", "--queries_per_step", "8", "--batch", "4",
-                  "--num_batches", "2", "--cpu_seconds", "1.2", "--cpu_table", tab], {"OMP_NUM_THREADS": "2"}, cpu_abi=True)
+                  "--num_batches", "2", "--cpu_seconds", "1.2", "--cpu_table", tab, "--full"], {"OMP_NUM_THREADS": "2"},
+                 cpu_abi=True)
     c = out["cpu_baseline"]
     assert c["kind"] in ("port", "torch") and c["leg"] in ("oracle_port", "torch_cpu")
     assert (c["kind"] == "port") == (c["leg"] == "oracle_port")
@@ -504,6 +506,36 @@ def test_bench_cpu_baseline_has_the_reference_serving_shape_leg(tmp_path):
     from deeprecsys_amd.latency_table import parse_results
     rows = parse_results(tab)
     assert len(rows) == 6 and all(r[5] > 0 for r in rows)      # six batch sizes, ms/iter in the column GPU_Data reads
+
+
+def test_bench_dump_outputs_are_the_last_steps_outputs(tmp_path, cpu_abi):
+    """--dump-outputs: what the timed path returned for a fixed sample of its last step's queries -- the same file
+    from run to run, each query's outputs those of its own input set (the oracle's forward on it) -- while the
+    plain line carries nothing of what --full adds."""
+    import bench
+    args = ["--workload", "tiny", "--steps", "2", "--warmup", "1", "--queries_per_step", "1500", "--batch", "4",
+            "--num_batches", "5", "--table_placements", "1"]
+    cpu = {"OMP_NUM_THREADS": "1"}
+    a = _bench(args + ["--dump-outputs", str(tmp_path / "a")], cpu, cpu_abi=True)
+    _bench(args + ["--dump-outputs", str(tmp_path / "b")], cpu, cpu_abi=True)
+    assert a["steps"] == 2 and a["config"]["timed_queries_per_gpu"] == 3000 and a["ms_per_step"] > 0
+    assert not {"verified", "verified_queries", "gpu_state", "cpu_baseline"} & set(a)
+    got = np.load(str(tmp_path / "a" / "outputs.npy"))
+    assert got.dtype == np.float32 and got.shape == (bench.DUMP_QUERIES, 4, 1)
+    assert np.array_equal(got, np.load(str(tmp_path / "b" / "outputs.npy")))
+    opt = bench.parse(args)
+    _, net, (lX, lS_l, lS_i) = bench.make_model(opt, 0)
+    try:
+        om, _ = bench.oracle_twin(opt, net)
+        picked = sorted(bench.dump_sample(opt, 3000, 1500, 1))
+        assert len(picked) == bench.DUMP_QUERIES and 1500 <= picked[0] and picked[-1] < 3000
+        for q, out in zip(picked, got):
+            b = q % opt.num_batches                    # the timed region serves the input sets in turn
+            exp = np.asarray(om.forward(lX[b], lS_i[b], lS_l[b], bs=4), np.float32).reshape(4, -1)
+            assert np.all(np.abs(out - exp) <= 1e-4 * np.abs(exp) + 1e-6), q
+    finally:
+        bench._ORACLE.clear()
+        net.engine.close()
 
 
 # ------------------------------------------------------------------------------------

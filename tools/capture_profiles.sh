@@ -34,9 +34,9 @@ trace() { # name, command...
   rm -rf "$d"
 }
 
-# 1. the bench line exactly as the driver runs it (N=1), with the CPU baseline legs
+# 1. the bench line as the driver runs it (N=1), with --full: the oracle check, the extra legs and the CPU baseline
 mkdir -p "$OUT/cpu_epyc9575f/raw_data"
-run 900 python bench.py --gpus 1 --steps 20 --warmup 5 --cpu_table "$OUT/cpu_epyc9575f/raw_data/results_rm1.txt" > "$OUT/bench.json" 2> "$OUT/bench.err"
+run 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu_table "$OUT/cpu_epyc9575f/raw_data/results_rm1.txt" > "$OUT/bench.json" 2> "$OUT/bench.err"
 # 2. rocprofv3's per-kernel summary of the same warm-up + timed region (--timed_only: none of the
 #    extra legs, so every gather launch in the trace is a launch of the benchmark itself)
 trace bench python bench.py --gpus 1 --steps 20 --warmup 5 --timed_only
@@ -80,8 +80,8 @@ pmc "$OUT/gemm_pmc_summary.txt" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE
 [ -x tools/ubench/gemm_lab ] && run 200 tools/ubench/gemm_lab 4096 2560 1024 >> "$OUT/gemm_lab.txt" 2>&1
 # (round 6: "mlp_layout" 1 and "mlp_gemm32" 0 are lab options; their RM3 lines are profiles/r05_rmc3_bench_layout1.json / _gemm32_0.json)
 # 5. other operating points and shapes (one line each)
-run 300 python bench.py --no_cpu_baseline --steps 5 --warmup 2 --set shared_stream=1 > "$OUT/bench_single_stream.json" 2>/dev/null
-run 300 python bench.py --no_cpu_baseline --steps 5 --warmup 2 --coalesce 1 > "$OUT/bench_coalesce1.json" 2>/dev/null
+run 300 python bench.py --full --no_cpu_baseline --steps 5 --warmup 2 --set shared_stream=1 > "$OUT/bench_single_stream.json" 2>/dev/null
+run 300 python bench.py --full --no_cpu_baseline --steps 5 --warmup 2 --coalesce 1 > "$OUT/bench_coalesce1.json" 2>/dev/null
 # round 6: small launch sets with and without the column-split MLP launch ("mlp_nsplit" 4, the default for DLRM), the arms alternating
 for rep in 1 2; do
   for c in 1 2 4; do
@@ -97,13 +97,13 @@ trace coalesce1 python bench.py --no_cpu_baseline --timed_only --steps 2 --warmu
 [ -f deeprecsys_amd/libdrs_hip_tl.so ] && TL_ROWS=80 run 200 python tools/mlp_timeline.py --coalesce 1 --set mlp_nsplit=0 > "$OUT/mlp_timeline_one_query_plain.txt" 2>&1
 # the 8-wave packed MLP launch in place of stream4_kernel (what each costs
 # the gather beside it), and launch sets of 8 instead of 12 queries
-run 300 python bench.py --no_cpu_baseline --steps 5 --warmup 2 --set mlp_stream=2 > "$OUT/bench_mlp_stream2.json" 2>/dev/null
-run 300 python bench.py --no_cpu_baseline --steps 5 --warmup 2 --set mlp_stream_2cu=1 > "$OUT/bench_mlp_stream4_2cu.json" 2>/dev/null
-run 300 python bench.py --no_cpu_baseline --steps 5 --warmup 2 --coalesce 8 > "$OUT/bench_coalesce8.json" 2>/dev/null
+run 300 python bench.py --full --no_cpu_baseline --steps 5 --warmup 2 --set mlp_stream=2 > "$OUT/bench_mlp_stream2.json" 2>/dev/null
+run 300 python bench.py --full --no_cpu_baseline --steps 5 --warmup 2 --set mlp_stream_2cu=1 > "$OUT/bench_mlp_stream4_2cu.json" 2>/dev/null
+run 300 python bench.py --full --no_cpu_baseline --steps 5 --warmup 2 --coalesce 8 > "$OUT/bench_coalesce8.json" 2>/dev/null
 # round 4: what the non-temporal row loads and the 32-row MLP form are worth on this box (same line, one option off)
-run 300 python bench.py --no_cpu_baseline --steps 5 --warmup 2 --set sls_nt=0 > "$OUT/bench_sls_nt0.json" 2>/dev/null
-run 300 python bench.py --no_cpu_baseline --steps 5 --warmup 2 --set mlp_rows32=0 > "$OUT/bench_mlp_rows32_0.json" 2>/dev/null
-run 300 python bench.py --no_cpu_baseline --steps 5 --warmup 2 > "$OUT/bench_again.json" 2>/dev/null
+run 300 python bench.py --full --no_cpu_baseline --steps 5 --warmup 2 --set sls_nt=0 > "$OUT/bench_sls_nt0.json" 2>/dev/null
+run 300 python bench.py --full --no_cpu_baseline --steps 5 --warmup 2 --set mlp_rows32=0 > "$OUT/bench_mlp_rows32_0.json" 2>/dev/null
+run 300 python bench.py --full --no_cpu_baseline --steps 5 --warmup 2 > "$OUT/bench_again.json" 2>/dev/null
 # the MLP launch ALONE (one stream, 8-query sets = 128 workgroups) in its three forms: durations from
 # rocprofv3, MFMA counters, and the in-kernel timeline of stream4_kernel (needs libdrs_hip_tl.so: make timeline)
 MA="python bench.py --no_cpu_baseline --timed_only --steps 2 --warmup 1 --queries_per_step 2048 --coalesce 8 --set shared_stream=1"
@@ -116,24 +116,24 @@ pmc "$OUT/mlp_alone_pmc_summary.txt" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ
 pmc "$OUT/mlp_alone_pmc_summary.txt" "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES" $MA --set mlp_stream=4
 [ -f deeprecsys_amd/libdrs_hip_tl.so ] && TL_ROWS=40 run 200 python tools/mlp_timeline.py --coalesce 8 --set mlp_stream=4 --set shared_stream=1 > "$OUT/mlp_timeline_stream4.txt" 2>&1
 for w in rmc1_ref rmc2_ref rmc3_ref rmc1_dot wnd ncf mtwnd din dien; do
-  run 400 python bench.py --workload $w --no_cpu_baseline --steps 5 --warmup 2 --queries_per_step 4096 > "$OUT/bench_$w.json" 2>/dev/null
+  run 400 python bench.py --full --workload $w --no_cpu_baseline --steps 5 --warmup 2 --queries_per_step 4096 > "$OUT/bench_$w.json" 2>/dev/null
   run 400 python bench.py --workload $w --no_cpu_baseline --timed_only --steps 3 --warmup 1 --queries_per_step 4096 --set shared_stream=1 > "$OUT/bench_${w}_single_stream.json" 2>/dev/null
 done
-run 400 python bench.py --workload rmc3 --batch 512 --no_cpu_baseline --steps 5 --warmup 2 --queries_per_step 2048 > "$OUT/bench_rmc3.json" 2>/dev/null
+run 400 python bench.py --full --workload rmc3 --batch 512 --no_cpu_baseline --steps 5 --warmup 2 --queries_per_step 2048 > "$OUT/bench_rmc3.json" 2>/dev/null
 run 600 python bench.py --workload rmc3 --batch 512 --steps 3 --warmup 1 --queries_per_step 2048 --timed_only > /dev/null 2>&1
 # round 6: the one-lookup gather as a row copy (sls_one_kernel) against the lane-group-per-bag walk ("sls_one" 0), arms alternating;
 # kernel traces of W&D and MT-WnD (is some kernel running all the time?  MT-WnD's output transfer has its own stream now)
 for rep in 1 2; do
   for w in wnd mtwnd dien ncf; do
     for one in 0 1; do
-      run 300 python bench.py --workload $w --no_cpu_baseline --steps 5 --warmup 2 --set sls_one=$one > "$OUT/bench_${w}_sls_one${one}_$rep.json" 2>/dev/null
+      run 300 python bench.py --full --workload $w --no_cpu_baseline --steps 5 --warmup 2 --set sls_one=$one > "$OUT/bench_${w}_sls_one${one}_$rep.json" 2>/dev/null
     done
   done
 done
 trace wnd python bench.py --workload wnd --no_cpu_baseline --timed_only --steps 3 --warmup 1
 trace mtwnd python bench.py --workload mtwnd --no_cpu_baseline --timed_only --steps 3 --warmup 1
 # CPU baseline legs on the MLP-bound shapes as well (port + torch)
-run 600 python bench.py --workload wnd --steps 3 --warmup 1 --queries_per_step 4096 > "$OUT/bench_wnd_cpu.json" 2>/dev/null
+run 600 python bench.py --full --workload wnd --steps 3 --warmup 1 --queries_per_step 4096 > "$OUT/bench_wnd_cpu.json" 2>/dev/null
 # 5b. DIN (fused gather + attention launch) and DIEN (recurrence on the matrix cores): per-kernel
 #     summaries, HBM traffic of the fused launch, MFMA-busy of the recurrent launch, CPU legs
 DN="python bench.py --workload din --no_cpu_baseline --timed_only --steps 3 --warmup 1 --queries_per_step 2048"
@@ -144,8 +144,8 @@ for pass in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
   pmc "$OUT/din_pmc_summary.txt" "$pass" $DN
 done
 pmc "$OUT/dien_pmc_summary.txt" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE" $DE
-run 400 python bench.py --workload din --steps 5 --warmup 2 --queries_per_step 4096 --cpu_seconds 6 > "$OUT/bench_din_cpu.json" 2>/dev/null
-run 400 python bench.py --workload dien --steps 5 --warmup 2 --queries_per_step 4096 --cpu_seconds 6 > "$OUT/bench_dien_cpu.json" 2>/dev/null
+run 400 python bench.py --full --workload din --steps 5 --warmup 2 --queries_per_step 4096 --cpu_seconds 6 > "$OUT/bench_din_cpu.json" 2>/dev/null
+run 400 python bench.py --full --workload dien --steps 5 --warmup 2 --queries_per_step 4096 --cpu_seconds 6 > "$OUT/bench_dien_cpu.json" 2>/dev/null
 run 300 python bench.py --workload din --no_cpu_baseline --timed_only --steps 3 --warmup 1 --queries_per_step 2048 --set din_fused=0 > "$OUT/bench_din_two_launch.json" 2>/dev/null
 run 300 python bench.py --workload dien --no_cpu_baseline --timed_only --steps 3 --warmup 1 --queries_per_step 2048 --set dien_mfma=0 > "$OUT/bench_dien_valu.json" 2>/dev/null
 # (round 4: the top MLP in a launch of its own behind the recurrence, as before; NCF with three launch sets in flight)
@@ -165,10 +165,10 @@ run 300 python tools/serve.py --mix --avg_arrival_rate 0.01 --nepochs 512 2>/dev
 # 8. the driver's multi-GPU launch line, on the one GPU of this box (RCCL communicator of size 1 is
 #    not created: world == 1), and the self-spawn path
 run 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 \
-    bench.py --gpus 1 --steps 5 --warmup 2 --no_cpu_baseline > "$OUT/bench_torchrun_n1.json" 2> "$OUT/bench_torchrun_n1.err"
+    bench.py --full --gpus 1 --steps 5 --warmup 2 --no_cpu_baseline > "$OUT/bench_torchrun_n1.json" 2> "$OUT/bench_torchrun_n1.err"
 # 9. locality-aware traces: the gather on uniform / shipped-profile / reuse-heavy index streams,
 #    through the same line as everything else (bench.py --trace = --data_generation synthetic)
-TR="python bench.py --no_cpu_baseline --steps 3 --warmup 1 --queries_per_step 8192 --num_batches 16"
+TR="python bench.py --full --no_cpu_baseline --steps 3 --warmup 1 --queries_per_step 8192 --num_batches 16"
 run 400 $TR > "$OUT/bench_trace_uniform.json" 2>/dev/null
 for p in shipped hot; do
   run 600 $TR --trace $p > "$OUT/bench_trace_$p.json" 2>/dev/null
