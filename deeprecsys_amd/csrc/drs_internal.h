@@ -96,8 +96,11 @@ hipError_t gemm_set_attrs();   // gemm.hip's kernels, on the current device
 
 // launch on `stream`; exact != 0 selects the sequential-order variant.
 // stop_event (optional): recorded by the gather dispatch itself when it completes
+// dtype: element type of the tables a.tables points at (DRS_TABLE_*; a.tab_off counts elements of that type) -- the
+// same launch decisions and grids for every type, rows widened to fp32 before they are summed
 hipError_t launch_sls(const SlsArgs& a, int exact, const Tune& tune, hipStream_t stream,
-                      hipEvent_t stop_event = nullptr);
+                      hipEvent_t stop_event = nullptr, int dtype = DRS_TABLE_FP32);
+inline int64_t table_elem_bytes(int dtype) { return dtype == DRS_TABLE_FP32 ? 4 : 2; }
 int64_t sls_grid_blocks(const SlsArgs& a, int exact, const Tune& tune);
 bool sls_flat_applicable(const SlsArgs& a, const Tune& tune);   // would a non-exact launch run the flat variant?
 
@@ -285,5 +288,10 @@ hipError_t probe_latency(const void* base, size_t chunk_bytes, int n_chunks, int
 
 hipError_t launch_fill_uniform(float* W, int64_t n, int32_t t, float lo, float hi, uint64_t seed,
                                hipStream_t stream);
+// the same values rounded to the element type `dtype` (DRS_TABLE_*; fp32: launch_fill_uniform)
+hipError_t launch_fill_uniform_dtype(void* W, int dtype, int64_t n, int32_t t, float lo, float hi, uint64_t seed,
+                                     hipStream_t stream);
+// n table elements of type src_dtype -> dst_dtype (rounded to nearest even; widening is exact)
+hipError_t launch_convert_table(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, hipStream_t stream);
 
 }  // namespace drs

@@ -3,7 +3,7 @@
 // counterpart, reference accelInferenceEngine.py:18-86).
 //
 // HBM layout (all hipMalloc'ed once in drs_create / first use):
-//   tables   one arena, table t at a 256-B aligned offset, rows*D fp32 row-major
+//   tables   one arena, table t at a 64-element aligned offset, rows*D row-major fp32 (or fp16 / bf16: "table_dtype")
 //   weights  one arena: all biases back to back (layer order, padded to 4 floats), then per
 //            layer W [N, K] dense row-major (as fed by the reference)
 //   batches  per staged batch: dense [max_batch, m_den] f32 | idx [T, cap] i32 |
@@ -178,6 +178,8 @@ struct drs_engine {
   std::vector<Arena> arenas;
   std::vector<hipMemGenericAllocationHandle_t> spacers;   // "table_spacer": device memory taken (never mapped) between placement candidates
   size_t tables_bytes = 0;
+  int64_t table_elems = 0;          // elements of the arena (tables at tab_off, 64-element aligned)
+  int table_dtype = DRS_TABLE_FP32; // "table_dtype": element type of the arena (DRS_TABLE_*); sums and outputs stay fp32
   // how the NEXT arena is built (drs_create's first one, "table_placement" -1 candidates)
   int table_alloc = 0;              // 0 hipMalloc | 1 virtual-memory API
   int64_t vmm_chunk = -1;           // bytes of physical memory per handle (0: one handle | -1: 1 GiB handles from 1 GiB on, else one); rounded up to whole 2 MiB pages
@@ -293,6 +295,7 @@ namespace eng {
   } while (0)
 
 // engine_create.hip
+void choose_launch_forms(drs_engine* e);
 int32_t fail(drs_engine* e, int32_t code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
 int32_t set_device(drs_engine* e);
 int32_t alloc_batch(drs_engine* e, Batch& b);

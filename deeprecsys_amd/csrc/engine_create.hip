@@ -116,7 +116,9 @@ const char* drs_last_error(drs_handle h) { return h ? h->err.c_str() : g_create_
 //   MT-WnD                                             up to 4      stream_kernel, two per CU  --            gemm32 64 x 128 from 256 tiles
 //   DIN                                                1            stream_kernel, two per CU  --            --
 //   NCF (145)                                          up to 4      stream_kernel, one per CU  --            --
-static void choose_launch_forms(drs_engine* e) {
+// ("table_dtype" runs it again for the new element size: what drs_create would have chosen for it)
+}  // extern "C"
+void drs::eng::choose_launch_forms(drs_engine* e) {
   const int T = e->T, D = e->D;
   // A wave of the wave-split gather takes 256/D rows per load instruction: a bag shorter than 8 such instructions cannot
   // fill its load rings, and a lane group per bag (the sequential variant, which is also bit-exact) is faster: RM3
@@ -130,7 +132,7 @@ static void choose_launch_forms(drs_engine* e) {
     for (size_t i = 0; i + 1 < mm->ln.size(); ++i) flop += 2.0 * mm->ln[i] * (mm->ln[i + 1] > 0 ? mm->ln[i + 1] : 64);
   // (DIEN: the recurrence, (T - 3) steps of two layers)
   for (const Mlp& rn : e->rnn) flop += 2.0 * (T - 3) * ((double)rn.ln[0] * rn.ln[1] + (double)rn.ln[1] * rn.ln[2]);
-  const double bytes = (double)T * e->max_lookups * D * 4.0;
+  const double bytes = (double)T * e->max_lookups * D * (double)table_elem_bytes(e->table_dtype);
   const bool mlp_bound = flop / bytes > 20.0;
   // How many streams, and how many sets in flight the engine asks its feeder for ("preferred_slots"), round 6, one box,
   // (sets in flight, streams) -> k queries/s:  RM3 config 3 (3,3) 34.1 (6,4) 35.0 (4,2) 31.7 | RM3 JSON 67.8 / 70.8 / 70.9 |
@@ -200,6 +202,7 @@ static void choose_launch_forms(drs_engine* e) {
   // within 1 % of each other either way (profiles/r06_wnd_set_sizes.txt)
   if (e->kind == DRS_MODEL_WND) { e->tune.gemm32_small = 12; e->tune.gemm32_small_blocks = 384; }
 }
+extern "C" {
 
 int32_t drs_create(const drs_model_cfg* cfg, int32_t device_id, drs_handle* out) {
   if (!cfg || !out) return fail(nullptr, DRS_ERR_BAD_ARG, "null cfg/out");
@@ -366,6 +369,7 @@ int32_t drs_create(const drs_model_cfg* cfg, int32_t device_id, drs_handle* out)
 #define CREATE_TRY(call) if (!hip_ok(call)) return bail(last_rr == hipErrorOutOfMemory ? DRS_ERR_OOM : DRS_ERR_HIP, (std::string(#call ": ") + e->err).c_str())
   e->tune.device = device_id;
   CREATE_TRY(device_init(device_id, &e->tune.zero));
+  e->table_elems = off;
   e->tables_bytes = sizeof(float) * (size_t)off;
   CREATE_TRY(hipMalloc(&e->d_tab_off, sizeof(int64_t) * T));
   CREATE_TRY(hipMalloc(&e->d_tab_rows, sizeof(int64_t) * T));
@@ -569,7 +573,24 @@ int32_t drs_set_table(drs_handle e, int32_t t, const float* h_W, int64_t rows) {
   if (rows != e->rows[t]) return fail(e, DRS_ERR_BAD_ARG, "table %d has %lld rows, got %lld", t, (long long)e->rows[t], (long long)rows);
   if ((rc = drs_sync(e))) return rc;
   drop_other_placements(e);
-  HIP_TRY(e, hipMemcpy(e->tables + e->tab_off[t], h_W, sizeof(float) * (size_t)rows * e->D, hipMemcpyHostToDevice));
+  if (e->table_dtype == DRS_TABLE_FP32) {
+    HIP_TRY(e, hipMemcpy(e->tables + e->tab_off[t], h_W, sizeof(float) * (size_t)rows * e->D, hipMemcpyHostToDevice));
+  } else {
+    // half tables: the fp32 rows cross the bus through a staging buffer, chunk by chunk, and are rounded on the device
+    const int64_t n = rows * e->D, chunk = std::min<int64_t>(n, (int64_t)16 << 20);
+    char* dst = reinterpret_cast<char*>(e->tables) + e->tab_off[t] * table_elem_bytes(e->table_dtype);
+    float* stage = nullptr;
+    HIP_TRY(e, hipMalloc(&stage, sizeof(float) * (size_t)chunk));
+    hipError_t r = hipSuccess;
+    for (int64_t i = 0; i < n && r == hipSuccess; i += chunk) {
+      const int64_t m = std::min(chunk, n - i);
+      r = hipMemcpy(stage, h_W + i, sizeof(float) * (size_t)m, hipMemcpyHostToDevice);
+      if (r == hipSuccess) r = launch_convert_table(stage, DRS_TABLE_FP32, dst + i * table_elem_bytes(e->table_dtype), e->table_dtype, m, nullptr);
+      if (r == hipSuccess) r = hipStreamSynchronize(nullptr);    // (before the next chunk overwrites the staging buffer)
+    }
+    (void)hipFree(stage);
+    if (r != hipSuccess) return fail(e, DRS_ERR_HIP, "drs_set_table: %s", hipGetErrorString(r));
+  }
   e->table_set[t] = true;
   return DRS_OK;
 }
@@ -579,7 +600,8 @@ int32_t drs_fill_table_uniform(drs_handle e, int32_t t, float lo, float hi, uint
   if (rc) return rc;
   if (t < 0 || t >= e->T) return fail(e, DRS_ERR_BAD_ARG, "bad table id");
   if (e->arenas.size() > 1) { if ((rc = drs_sync(e))) return rc; drop_other_placements(e); }
-  HIP_TRY(e, launch_fill_uniform(e->tables + e->tab_off[t], e->rows[t] * e->D, t, lo, hi, seed, e->slots[0].stream));
+  HIP_TRY(e, launch_fill_uniform_dtype(reinterpret_cast<char*>(e->tables) + e->tab_off[t] * table_elem_bytes(e->table_dtype), e->table_dtype,
+                                       e->rows[t] * e->D, t, lo, hi, seed, e->slots[0].stream));
   HIP_TRY(e, hipStreamSynchronize(e->slots[0].stream));
   e->table_set[t] = true;
   return DRS_OK;

@@ -318,7 +318,7 @@ int32_t enqueue_forward(drs_engine* e, Slot& s, int n, const Batch* const* bts, 
     int64_t bytes = 0;
     for (int i = 0; i < q.n_q; ++i)
       for (int t = 0; t < e->T; ++t)
-        bytes += (int64_t)qb[i]->h_off[(size_t)t * (e->max_batch + 1) + q.bs[i]] * ((int64_t)e->D * 4 + 4) +
+        bytes += (int64_t)qb[i]->h_off[(size_t)t * (e->max_batch + 1) + q.bs[i]] * ((int64_t)e->D * table_elem_bytes(e->table_dtype) + 4) +
                  (int64_t)q.bs[i] * (4 + (int64_t)e->D * 4);
     // (the fused DIN launch writes the 4 D floats of the top MLP's input row per sample instead
     // of T pooled vectors)
@@ -331,7 +331,7 @@ int32_t enqueue_forward(drs_engine* e, Slot& s, int n, const Batch* const* bts, 
   if (din_fused)
     HIP_TRY(e, launch_din_fused(a, e->att[0].ln[1], e->d_att_packed, s.R, e->ldR, e->tune, gstream, piped ? s.ev_sls : nullptr));
   else
-    HIP_TRY(e, launch_sls(a, exact_now, e->tune, gstream, piped ? s.ev_sls : nullptr));
+    HIP_TRY(e, launch_sls(a, exact_now, e->tune, gstream, piped ? s.ev_sls : nullptr, e->table_dtype));
   if (evts) HIP_TRY(e, hipEventRecord(s.ev[1], gstream));
   bool joined = !piped;   // has s.stream been made to wait for the gather yet?
   auto join = [&]() -> hipError_t {

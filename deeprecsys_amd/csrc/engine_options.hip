@@ -91,6 +91,39 @@ int32_t set_table_spacer(drs_engine* e, int64_t value) {
     return DRS_OK;
 }
 
+int32_t set_table_dtype(drs_engine* e, int64_t value) {
+  // The tables in use are converted on the device into a new arena of the new element type (round to nearest even;
+  // widening is exact), which then replaces the old arena and every other placement candidate.  Refused (DRS_ERR_OOM,
+  // nothing changes) when the new arena would not leave 3/4 of the device's memory free -- the rule of "table_placement" -1.
+  // The launch forms that depend on the gathered bytes are chosen again (choose_launch_forms): set this one first.
+  if (value == e->table_dtype) return DRS_OK;
+  if (e->kind == DRS_MODEL_DIN || e->kind == DRS_MODEL_DIEN)
+    return fail(e, DRS_ERR_UNSUPPORTED, "table_dtype %lld: DIN and DIEN gather fp32 tables only", (long long)value);
+  const int dt = (int)value;
+  const size_t bytes = (size_t)e->table_elems * (size_t)table_elem_bytes(dt);
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 4)
+    return fail(e, DRS_ERR_OOM, "table_dtype: no room for the converted tables (%zu bytes)", bytes);
+  Arena fresh;
+  hipError_t ar = arena_alloc(e, bytes, &fresh);
+  if (ar != hipSuccess) { (void)hipGetLastError(); return fail(e, DRS_ERR_OOM, "table_dtype: arena allocation: %s", hipGetErrorString(ar)); }
+  if (launch_convert_table(e->tables, e->table_dtype, fresh.p, dt, e->table_elems, nullptr) != hipSuccess ||
+      hipStreamSynchronize(nullptr) != hipSuccess) {
+    arena_free(fresh);
+    (void)hipGetLastError();
+    return fail(e, DRS_ERR_HIP, "table_dtype: conversion");
+  }
+  for (Arena& a : e->arenas) arena_free(a);
+  drop_spacers(e);
+  e->arenas.assign(1, fresh);
+  e->tables = fresh.p;
+  e->tables_bytes = bytes;
+  e->table_dtype = dt;
+  choose_launch_forms(e);
+  apply_stream_mode(e);
+  return DRS_OK;
+}
+
 int64_t arena_in_use(drs_engine* e) {
   return (int64_t)(std::find_if(e->arenas.begin(), e->arenas.end(), [&](const Arena& a) { return a.p == e->tables; }) - e->arenas.begin());
 }
@@ -141,6 +174,7 @@ const OptDesc kOptions[] = {
 #else
     OPT("table_alloc", 0, 2, nullptr, 0, table_alloc),
 #endif
+    {"table_dtype", 0, 2, nullptr, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_dtype; }, nullptr, set_table_dtype},
     {"table_spacer", 0, kBig, nullptr, 0, [](drs_engine* e) -> int64_t { return (int64_t)e->spacers.size() << 30; }, nullptr, set_table_spacer},
     // what the engine tells its feeder (read only)
     OPT_RO("preferred_coalesce", return e->mlp_streams > 1 ? DRS_MAX_COALESCE : (e->kind == DRS_MODEL_DLRM ? 12 : 8);),
@@ -454,7 +488,7 @@ int32_t drs_gather_bytes(drs_handle e, int32_t batch_id, int32_t bs, int64_t* by
   int64_t total = 0;
   for (int t = 0; t < e->T; ++t) {
     const int64_t n = b.h_off[(size_t)t * (e->max_batch + 1) + bs];
-    total += n * ((int64_t)e->D * 4 + 4) + (int64_t)bs * (4 + (int64_t)e->D * 4);
+    total += n * ((int64_t)e->D * table_elem_bytes(e->table_dtype) + 4) + (int64_t)bs * (4 + (int64_t)e->D * 4);
   }
   *bytes = total;
   return DRS_OK;

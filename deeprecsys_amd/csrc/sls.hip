@@ -102,12 +102,54 @@ __device__ __forceinline__ float2 ld_nt(const float2* p) {
   const f2v_nt t = __builtin_nontemporal_load(reinterpret_cast<const f2v_nt*>(p));
   return make_float2(t.x, t.y);
 }
+typedef unsigned int u2v_nt __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint2 ld_nt(const uint2* p) {
+  const u2v_nt t = __builtin_nontemporal_load(reinterpret_cast<const u2v_nt*>(p));
+  return make_uint2(t.x, t.y);
+}
+
+// Row-element policies ("table_dtype"): what a table element is, and the PIECE a lane loads -- 4 elements, 16 B of fp32
+// or 8 B of fp16 / bf16, one load instruction -- widened to 4 fp32 values before they are summed.  Every fp16 / bf16
+// value is an fp32 value, so a half form sums exactly what its fp32 twin sums on the upcast table, in the same order:
+// the same bits.  tag: the dispatch log's dtype token (none for fp32).
+struct F32 {
+  using elem = float;
+  using piece = float4;
+  static constexpr const char* tag = "";
+  __device__ static __forceinline__ float4 up(const float4& p) { return p; }
+  __device__ static __forceinline__ float up1(float x) { return x; }
+};
+struct F16 {
+  using elem = uint16_t;
+  using piece = uint2;
+  static constexpr const char* tag = "f16";
+  __device__ static __forceinline__ float up1(uint16_t x) { return (float)__builtin_bit_cast(_Float16, x); }
+  __device__ static __forceinline__ float4 up(const uint2& p) {
+    return make_float4(up1((uint16_t)p.x), up1((uint16_t)(p.x >> 16)), up1((uint16_t)p.y), up1((uint16_t)(p.y >> 16)));
+  }
+};
+struct BF16 {
+  using elem = uint16_t;
+  using piece = uint2;
+  static constexpr const char* tag = "bf16";
+  __device__ static __forceinline__ float up1(uint16_t x) { return __uint_as_float((uint32_t)x << 16); }
+  __device__ static __forceinline__ float4 up(const uint2& p) {
+    return make_float4(__uint_as_float(p.x << 16), __uint_as_float(p.x & 0xffff0000u), __uint_as_float(p.y << 16),
+                       __uint_as_float(p.y & 0xffff0000u));
+  }
+};
+template <class E>
+__device__ __forceinline__ const typename E::elem* table_base(const float* tables) {
+  return reinterpret_cast<const typename E::elem*>(tables);
+}
 
 // NT: the hint must be a COMPILE-TIME property of the load: a run-time `nt ? ld_nt(p) : *p` is if-converted
 // into one plain load (the hint is metadata the merge drops): measured in the ISA, 0 of 5 / 2 of 14 loads kept it.
-template <int G, int V, int U, bool EXACT, bool NT = false>
+template <int G, int V, int U, bool EXACT, bool NT = false, class E = F32>
 __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
   using vec = typename Vec<V>::type;
+  using piece = typename E::piece;
+  static_assert(V == 4, "a lane's piece of a row is 4 elements");
   constexpr int NG = 64 / G;                  // lane groups per wave
   constexpr int BAGS = EXACT ? NG : 1;        // bags per wave
   constexpr int STEP = EXACT ? 1 : NG;        // row stride between a lane's loads
@@ -167,7 +209,7 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
     end = bag_ok ? offp[b + 1] : 0;
   }
   const int32_t* __restrict__ ip = qidx + (int64_t)t * a.idx_stride;
-  const float* __restrict__ W = a.tables + a.tab_off[t] + col;
+  const typename E::elem* __restrict__ W = table_base<E>(a.tables) + a.tab_off[t] + col;
   const uint32_t rows = (uint32_t)a.tab_rows[t];
   const int64_t D = a.D;
   const uint32_t Dv = (uint32_t)a.D / V;   // row stride in load-width units: rows * D / V < 2^32 (rows * D < 2^33 is enforced at table creation)
@@ -206,7 +248,7 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
     __builtin_amdgcn_wave_barrier();
 
     // U independent, unconditional row loads
-    auto issue = [&](vec (&ring)[U], int pos) {
+    auto issue = [&](piece (&ring)[U], int pos) {
       uint32_t r[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) r[u] = (uint32_t)my_idx[min(pos + u * STEP, last)];
@@ -214,13 +256,13 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
       for (int u = 0; u < U; ++u) {
         bad |= (pos + u * STEP < n) && (r[u] >= rows);
         r[u] = r[u] < rows ? r[u] : 0u;
-        const vec* rp_ = reinterpret_cast<const vec*>(W) + (uint64_t)(r[u] * Dv);
+        const piece* rp_ = reinterpret_cast<const piece*>(W) + (uint64_t)(r[u] * Dv);
         if constexpr (NT) ring[u] = ld_nt(rp_); else ring[u] = *rp_;
       }
     };
-    auto consume = [&](const vec (&ring)[U], int pos) {
+    auto consume = [&](const piece (&ring)[U], int pos) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) vadd(acc, vsel<V>(pos + u * STEP < n, ring[u]));
+      for (int u = 0; u < U; ++u) vadd(acc, vsel<V>(pos + u * STEP < n, E::up(ring[u])));
     };
 
     // software pipeline over two register rings: while ring A (round k) is summed
@@ -228,7 +270,7 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
     // Each arm holds its own issue+consume pair; the distinct asm comments keep
     // SimplifyCFG from sinking the common tails into a join.
     constexpr int R = U * STEP;
-    vec ringA[U], ringB[U];
+    piece ringA[U], ringB[U];
     int jj = first;                                 // per-lane row position
     int ju = 0;                                     // uniform round position
     issue(ringA, jj);
@@ -284,8 +326,9 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
 // coming over the cross-lane network.  The value stored is 0.0f + row, the sequential form's single addition:
 // the same bits.  D == 4 G exactly.  BW = samples per wave: 64, or 16 for launches that would otherwise be a few dozen
 // waves (one query of NCF: 4 tables x 256 samples) -- lanes 0 .. 15 fetch the indices then.
-template <int G, int BW>
+template <int G, int BW, class E = F32>
 __global__ __launch_bounds__(64) void sls_one_kernel(SlsArgs a, int tiles) {
+  using piece = typename E::piece;
   constexpr int NG = 64 / G, PER = BW / NG;          // bags a lane group copies
   constexpr int M = PER < 8 ? PER : 8;               // ... M at a time
   static_assert(PER >= 1 && PER % M == 0, "whole rounds");
@@ -322,11 +365,11 @@ __global__ __launch_bounds__(64) void sls_one_kernel(SlsArgs a, int tiles) {
   // what the copying lanes need of sample i: its row number, and its output row (-1: nothing to store)
   const int dst = ok ? vrow : -1;
   const int keep = bad ? 0 : 1;
-  const float4* __restrict__ W = reinterpret_cast<const float4*>(a.tables + a.tab_off[t]) + gl;
+  const piece* __restrict__ W = reinterpret_cast<const piece*>(table_base<E>(a.tables) + a.tab_off[t]) + gl;
   float* __restrict__ out = a.out + a.col0 + (int64_t)t * (4 * G) + gl * 4;
 #pragma unroll
   for (int j0 = 0; j0 < PER; j0 += M) {
-    float4 v[M];
+    piece v[M];
     int vr[M], kp[M];
 #pragma unroll
     for (int j = 0; j < M; ++j) {
@@ -339,8 +382,9 @@ __global__ __launch_bounds__(64) void sls_one_kernel(SlsArgs a, int tiles) {
 #pragma unroll
     for (int j = 0; j < M; ++j)
       if (vr[j] >= 0) {
-        const float4 o = make_float4(0.f + (kp[j] ? v[j].x : 0.f), 0.f + (kp[j] ? v[j].y : 0.f),
-                                     0.f + (kp[j] ? v[j].z : 0.f), 0.f + (kp[j] ? v[j].w : 0.f));
+        const float4 w = E::up(v[j]);
+        const float4 o = make_float4(0.f + (kp[j] ? w.x : 0.f), 0.f + (kp[j] ? w.y : 0.f),
+                                     0.f + (kp[j] ? w.z : 0.f), 0.f + (kp[j] ? w.w : 0.f));
         *reinterpret_cast<float4*>(out + (int64_t)vr[j] * a.ld_out) = o;
       }
   }
@@ -354,8 +398,10 @@ __global__ __launch_bounds__(64) void sls_one_kernel(SlsArgs a, int tiles) {
 // FLAT variant: fixed-length bags, G lanes per row (16 B per lane), NL loads per lane, BPW
 // bags (same sample, consecutive tables) per wave.  Requires L * BPW <= NL * (64 / G) and
 // T % BPW == 0 (checked by launch_sls).
-template <int G, int NL, int BPW, bool NT = false>
+template <int G, int NL, int BPW, bool NT = false, class E = F32>
 __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_order) {
+  using elem = typename E::elem;
+  using piece = typename E::piece;
   constexpr int NG = 64 / G;                       // lane groups = rows per load instruction
   // Work item w = (table group, sample), numbered TABLE-MAJOR; everything that depends only on
   // the wave (sample, query, tables) is scalar.  XCD-aware order (xcd_order != 0): workgroup id
@@ -449,15 +495,15 @@ __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_
                     "+s"(tab_off_k[BPW > 2 ? 2 : 0]), "+s"(tab_rows_k[BPW > 2 ? 2 : 0]), "+s"(tab_off_k[BPW > 3 ? 3 : 0]), "+s"(tab_rows_k[BPW > 3 ? 3 : 0]));
 
   // ---- phase 2: range check (Caffe2 ENFORCE) and every row address of the wave ----------------
-  const float* rp[NL];
+  const elem* rp[NL];
   bool bad = false;
 #pragma unroll
   for (int u = 0; u < NL; ++u) {
-    const float* W = a.tables + tab_off_k[0];
+    const elem* W = table_base<E>(a.tables) + tab_off_k[0];
     uint32_t rk = (uint32_t)tab_rows_k[0];
 #pragma unroll
     for (int z = 1; z < BPW; ++z) {
-      W = kj[u] == z ? a.tables + tab_off_k[z] : W;
+      W = kj[u] == z ? table_base<E>(a.tables) + tab_off_k[z] : W;
       rk = kj[u] == z ? (uint32_t)tab_rows_k[z] : rk;
     }
     bad |= g + NG * u < R && ridx[u] >= rk;
@@ -466,11 +512,11 @@ __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_
   }
   // ---- phase 3: all row loads, back to back, nothing else in between --------------------------
   __builtin_amdgcn_sched_barrier(0);
-  float4 v[NL];
+  piece v[NL];
 #pragma unroll
   for (int u = 0; u < NL; ++u) {
-    if constexpr (NT) v[u] = ld_nt(reinterpret_cast<const float4*>(rp[u]));
-    else v[u] = *reinterpret_cast<const float4*>(rp[u]);
+    if constexpr (NT) v[u] = ld_nt(reinterpret_cast<const piece*>(rp[u]));
+    else v[u] = *reinterpret_cast<const piece*>(rp[u]);
   }
   __builtin_amdgcn_sched_barrier(0);
 
@@ -482,10 +528,10 @@ __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_
   for (int u = 0; u < NL; ++u) {
     const int j = g + NG * u;
     if (BPW == 1) {
-      vadd(acc[0], vsel<4>(j < R, v[u]));
+      vadd(acc[0], vsel<4>(j < R, E::up(v[u])));
     } else {
 #pragma unroll
-      for (int k = 0; k < BPW; ++k) vadd(acc[k], vsel<4>(j < R && kj[u] == k, v[u]));
+      for (int k = 0; k < BPW; ++k) vadd(acc[k], vsel<4>(j < R && kj[u] == k, E::up(v[u])));
     }
   }
 #pragma unroll
@@ -516,8 +562,10 @@ __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_
 // (everything in flight at once) on RMC1's 80 x 256-B bags beside the MLP launch: 0.74 vs 0.72 of
 // peak for 8-query launches, 0.57-0.59 vs 0.51 for a single query; so one-bag-per-wave launches
 // take this one ("sls_flat" 1) and the phased form serves the several-bags-per-wave shapes.
-template <int G, int NL, bool NT>
+template <int G, int NL, bool NT, class E = F32>
 __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
+  using elem = typename E::elem;
+  using piece = typename E::piece;
   constexpr int BPW = 1;
   constexpr int NG = 64 / G;                       // lane groups = rows per load instruction
   constexpr int NI = (NL * NG + 63) / 64;          // index registers per lane
@@ -553,11 +601,11 @@ __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
   }
   const int R = BPW * L;
   const uint32_t D4 = (uint32_t)a.D >> 2;          // row stride in 16-byte units: rows * D / 4 < 2^32 (enforced at table creation)
-  const float* Wk[BPW];
+  const elem* Wk[BPW];
   uint32_t rows_k[BPW];
 #pragma unroll
   for (int k = 0; k < BPW; ++k) {
-    Wk[k] = a.tables + a.tab_off[t0 + k] + col;
+    Wk[k] = table_base<E>(a.tables) + a.tab_off[t0 + k] + col;
     rows_k[k] = (uint32_t)a.tab_rows[t0 + k];
   }
   // which of the wave's bags does flattened row j belong to (j < R)
@@ -588,12 +636,12 @@ __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
   }
 
   // every row load of the wave, back to back
-  float4 v[NL];
+  piece v[NL];
 #pragma unroll
   for (int u = 0; u < NL; ++u) {
     const int j = g + NG * u;                      // (j >> 6) == (NG * u) >> 6: compile time
     const uint32_t ro = (uint32_t)__shfl((int)roff[(NG * u) >> 6], j & 63);
-    const float* W = Wk[0];
+    const elem* W = Wk[0];
     if (BPW > 1) {
       const int k = bag_of(min(j, R - 1));
 #pragma unroll
@@ -601,9 +649,9 @@ __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
     }
     // NT ("sls_nt" 1): the rows are read once (~1 % reuse inside a batch): non-temporal loads
     if constexpr (NT) {
-      v[u] = ld_nt(reinterpret_cast<const float4*>(W) + (uint64_t)ro);
+      v[u] = ld_nt(reinterpret_cast<const piece*>(W) + (uint64_t)ro);
     } else {
-      v[u] = reinterpret_cast<const float4*>(W)[(uint64_t)ro];
+      v[u] = reinterpret_cast<const piece*>(W)[(uint64_t)ro];
     }
   }
 
@@ -614,11 +662,11 @@ __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
   for (int u = 0; u < NL; ++u) {
     const int j = g + NG * u;
     if (BPW == 1) {
-      vadd(acc[0], vsel<4>(j < R, v[u]));
+      vadd(acc[0], vsel<4>(j < R, E::up(v[u])));
     } else {
       const int kj = bag_of(min(j, R - 1));
 #pragma unroll
-      for (int k = 0; k < BPW; ++k) vadd(acc[k], vsel<4>(j < R && kj == k, v[u]));
+      for (int k = 0; k < BPW; ++k) vadd(acc[k], vsel<4>(j < R && kj == k, E::up(v[u])));
     }
   }
 #pragma unroll
@@ -646,6 +694,7 @@ __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
 // every shipped config satisfies.  Other widths -- D = 10, 50, 300 -- take this one: a wave per bag, lane c takes columns
 // c, c + 64, ... (dword loads: rows need no alignment), rows strictly in index order, i.e. Caffe2's own summation order
 // (bit-identical to the oracle), ragged bags through the prefix sums.  Slow by design (one row at a time), never wrong.
+template <class E = F32>
 __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
   if (a.ts && threadIdx.x == 0) a.ts[2 * blockIdx.x] = wall_clock64();
   const int lane = threadIdx.x;
@@ -674,7 +723,7 @@ __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
     end = offp[b + 1];
   }
   const int32_t* __restrict__ ip = qidx + (int64_t)t * a.idx_stride;
-  const float* __restrict__ W = a.tables + a.tab_off[t];
+  const typename E::elem* __restrict__ W = table_base<E>(a.tables) + a.tab_off[t];
   const uint32_t rows = (uint32_t)a.tab_rows[t];
   const int D = a.D;
   float* o = a.out + (int64_t)vrow * a.ld_out + a.col0 + (int64_t)t * D;
@@ -685,11 +734,11 @@ __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
       uint32_t r = (uint32_t)ip[j];
       bad |= r >= rows;
       r = r < rows ? r : 0u;
-      const float* row = W + (int64_t)r * D;
+      const typename E::elem* row = W + (int64_t)r * D;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int c = c0 + lane + 64 * k;
-        acc[k] += c < D ? row[c] : 0.f;
+        acc[k] += c < D ? E::up1(row[c]) : 0.f;
       }
     }
 #pragma unroll
@@ -717,18 +766,18 @@ void launch_k(K kernel, dim3 grid, hipStream_t s, hipEvent_t stop, const X&... x
   launch_kb(kernel, grid, dim3(64), s, stop, x...);
 }
 
-template <int G, int V, int U>
+template <int G, int V, int U, class E>
 hipError_t launch_variant(const SlsArgs& a, int exact, int nt, hipStream_t s, hipEvent_t stop) {
   const int64_t n_bags = (int64_t)a.q.cum[a.q.n_q] * a.T;
   if (n_bags == 0) return hipSuccess;
   if (exact) {
     constexpr int BAGS = 64 / G;
     const unsigned grid = (unsigned)((n_bags + BAGS - 1) / BAGS);
-    launch_k(sls_kernel<G, V, U, true>, grid, s, stop, a);
+    launch_k(sls_kernel<G, V, U, true, false, E>, grid, s, stop, a);
   } else if (nt) {
-    launch_k(sls_kernel<G, V, U, false, true>, (unsigned)n_bags, s, stop, a);
+    launch_k(sls_kernel<G, V, U, false, true, E>, (unsigned)n_bags, s, stop, a);
   } else {
-    launch_k(sls_kernel<G, V, U, false>, (unsigned)n_bags, s, stop, a);
+    launch_k(sls_kernel<G, V, U, false, false, E>, (unsigned)n_bags, s, stop, a);
   }
   return hipGetLastError();
 }
@@ -736,9 +785,9 @@ hipError_t launch_variant(const SlsArgs& a, int exact, int nt, hipStream_t s, hi
 // U (row loads per register ring and lane) is 4: two rings, so 4..8 loads in flight per lane, the waves per
 // CU provide the rest of the memory-level parallelism.  (8, 16 and 20 were options until round 4 -- measured
 // equal or slower on every shape -- as was a 16-lane x 8-byte form for D == 32.)
-template <int G, int V>
+template <int G, int V, class E>
 hipError_t launch_u(const SlsArgs& a, int exact, int nt, hipStream_t s, hipEvent_t stop) {
-  return launch_variant<G, V, 4>(a, exact, nt, s, stop);
+  return launch_variant<G, V, 4, E>(a, exact, nt, s, stop);
 }
 
 int lanes_per_row(int D) { return D <= 8 ? 2 : D <= 16 ? 4 : D <= 32 ? 8 : D <= 64 ? 16 : D <= 128 ? 32 : 64; }
@@ -784,40 +833,41 @@ FlatPlan flat_plan(const SlsArgs& a, const Tune& tune) {
   return p;
 }
 
-template <int G, int NL>
+template <int G, int NL, class E>
 hipError_t launch_flat_b(const SlsArgs& a, const FlatPlan& p, dim3 grid, hipStream_t s, hipEvent_t stop) {
-  if (p.coal && p.nt) launch_k(sls_flatc_kernel<G, NL, true>, grid, s, stop, a, p.L);
-  else if (p.coal) launch_k(sls_flatc_kernel<G, NL, false>, grid, s, stop, a, p.L);
+  if (p.coal && p.nt) launch_k(sls_flatc_kernel<G, NL, true, E>, grid, s, stop, a, p.L);
+  else if (p.coal) launch_k(sls_flatc_kernel<G, NL, false, E>, grid, s, stop, a, p.L);
   else if (p.nt) {
-    if (p.BPW == 1) launch_k(sls_flat_kernel<G, NL, 1, true>, grid, s, stop, a, p.L, p.xcd);
+    if (p.BPW == 1) launch_k(sls_flat_kernel<G, NL, 1, true, E>, grid, s, stop, a, p.L, p.xcd);
     else if constexpr (NL <= 10) {
-      if (p.BPW == 2) launch_k(sls_flat_kernel<G, NL, 2, true>, grid, s, stop, a, p.L, p.xcd);
-      else launch_k(sls_flat_kernel<G, NL, 4, true>, grid, s, stop, a, p.L, p.xcd);
+      if (p.BPW == 2) launch_k(sls_flat_kernel<G, NL, 2, true, E>, grid, s, stop, a, p.L, p.xcd);
+      else launch_k(sls_flat_kernel<G, NL, 4, true, E>, grid, s, stop, a, p.L, p.xcd);
     }
   }
-  else if (p.BPW == 1) launch_k(sls_flat_kernel<G, NL, 1>, grid, s, stop, a, p.L, p.xcd);
+  else if (p.BPW == 1) launch_k(sls_flat_kernel<G, NL, 1, false, E>, grid, s, stop, a, p.L, p.xcd);
   else if constexpr (NL <= 10) {
-    if (p.BPW == 2) launch_k(sls_flat_kernel<G, NL, 2>, grid, s, stop, a, p.L, p.xcd);
-    else launch_k(sls_flat_kernel<G, NL, 4>, grid, s, stop, a, p.L, p.xcd);
+    if (p.BPW == 2) launch_k(sls_flat_kernel<G, NL, 2, false, E>, grid, s, stop, a, p.L, p.xcd);
+    else launch_k(sls_flat_kernel<G, NL, 4, false, E>, grid, s, stop, a, p.L, p.xcd);
   }
   return hipGetLastError();
 }
-template <int G>
+template <int G, class E>
 hipError_t launch_flat_g(const SlsArgs& a, const FlatPlan& p, dim3 grid, hipStream_t s, hipEvent_t stop) {
   switch (p.NL) {
-    case 5: return launch_flat_b<G, 5>(a, p, grid, s, stop);
-    case 10: return launch_flat_b<G, 10>(a, p, grid, s, stop);
-    default: return launch_flat_b<G, 20>(a, p, grid, s, stop);
+    case 5: return launch_flat_b<G, 5, E>(a, p, grid, s, stop);
+    case 10: return launch_flat_b<G, 10, E>(a, p, grid, s, stop);
+    default: return launch_flat_b<G, 20, E>(a, p, grid, s, stop);
   }
 }
+template <class E>
 hipError_t launch_flat(const SlsArgs& a, const FlatPlan& p, hipStream_t s, hipEvent_t stop) {
   const int64_t n_bags = (int64_t)a.q.cum[a.q.n_q] * a.T;
   if (n_bags == 0) return hipSuccess;
   const dim3 grid(p.grid);
   switch (p.G) {
-    case 8: return launch_flat_g<8>(a, p, grid, s, stop);
-    case 16: return launch_flat_g<16>(a, p, grid, s, stop);
-    default: return launch_flat_g<32>(a, p, grid, s, stop);
+    case 8: return launch_flat_g<8, E>(a, p, grid, s, stop);
+    case 16: return launch_flat_g<16, E>(a, p, grid, s, stop);
+    default: return launch_flat_g<32, E>(a, p, grid, s, stop);
   }
 }
 
@@ -857,22 +907,26 @@ int64_t sls_grid_blocks(const SlsArgs& a, int exact, const Tune& tune) {
   return (n_bags + bags - 1) / bags;
 }
 
-hipError_t launch_sls(const SlsArgs& a, int exact, const Tune& tune, hipStream_t s, hipEvent_t stop) {
+// the launch for tables of element type E (F32 / F16 / BF16): the same decisions, the same grids for every E
+template <class E>
+static hipError_t launch_sls_e(const SlsArgs& a, int exact, const Tune& tune, hipStream_t s, hipEvent_t stop) {
+  const char* dt = E::tag;                // dispatch log: "" for fp32, else the dtype token
+  const char* sep = *dt ? "," : "";
   const int D = a.D;
   if (D <= 0) return hipErrorInvalidValue;
   if (any_width(D)) {            // the generic form: any width, sequential order
     const int64_t n_bags = (int64_t)a.q.cum[a.q.n_q] * a.T;
     if (n_bags == 0) return hipSuccess;
-    log_launch(tune.log, "sls_any_kernel[%lld wg, D=%d]", (long long)n_bags, D);
-    launch_k(sls_any_kernel, dim3((unsigned)n_bags), s, stop, a);
+    log_launch(tune.log, "sls_any_kernel%s%s%s[%lld wg, D=%d]", *dt ? "<" : "", dt, *dt ? ">" : "", (long long)n_bags, D);
+    launch_k(sls_any_kernel<E>, dim3((unsigned)n_bags), s, stop, a);
     return hipGetLastError();
   }
   if (!exact) {
     const FlatPlan p = flat_plan(a, tune);
     if (p.ok) {
-      log_launch(tune.log, "%s<%d,%d%s%s>[%u wg, L=%d]", p.coal ? "sls_flatc_kernel" : "sls_flat_kernel", p.G, p.NL,
-                 p.coal ? "" : (p.BPW == 4 ? ",bpw4" : p.BPW == 2 ? ",bpw2" : ",bpw1"), p.nt ? ",nt" : "", p.grid, p.L);
-      return launch_flat(a, p, s, stop);
+      log_launch(tune.log, "%s<%d,%d%s%s%s%s>[%u wg, L=%d]", p.coal ? "sls_flatc_kernel" : "sls_flat_kernel", p.G, p.NL,
+                 p.coal ? "" : (p.BPW == 4 ? ",bpw4" : p.BPW == 2 ? ",bpw2" : ",bpw1"), p.nt ? ",nt" : "", sep, dt, p.grid, p.L);
+      return launch_flat<E>(a, p, s, stop);
     }
   }
   if (exact && one_lookup(a, tune)) {
@@ -880,31 +934,37 @@ hipError_t launch_sls(const SlsArgs& a, int exact, const Tune& tune, hipStream_t
     const int tiles = (a.q.cum[a.q.n_q] + bw - 1) / bw;
     if (tiles == 0) return hipSuccess;
     const dim3 grid((unsigned)one_lookup_grid(a, tune));
-    log_launch(tune.log, "sls_one_kernel<%d,%d>[%u wg]", D / 4, bw, grid.x);
+    log_launch(tune.log, "sls_one_kernel<%d,%d%s%s>[%u wg]", D / 4, bw, sep, dt, grid.x);
     if (bw == 64) {
-      if (D == 16) launch_k(sls_one_kernel<4, 64>, grid, s, stop, a, tiles);
-      else if (D == 32) launch_k(sls_one_kernel<8, 64>, grid, s, stop, a, tiles);
-      else if (D == 64) launch_k(sls_one_kernel<16, 64>, grid, s, stop, a, tiles);
-      else launch_k(sls_one_kernel<32, 64>, grid, s, stop, a, tiles);
+      if (D == 16) launch_k(sls_one_kernel<4, 64, E>, grid, s, stop, a, tiles);
+      else if (D == 32) launch_k(sls_one_kernel<8, 64, E>, grid, s, stop, a, tiles);
+      else if (D == 64) launch_k(sls_one_kernel<16, 64, E>, grid, s, stop, a, tiles);
+      else launch_k(sls_one_kernel<32, 64, E>, grid, s, stop, a, tiles);
     } else {
-      if (D == 16) launch_k(sls_one_kernel<4, 16>, grid, s, stop, a, tiles);
-      else if (D == 32) launch_k(sls_one_kernel<8, 16>, grid, s, stop, a, tiles);
-      else if (D == 64) launch_k(sls_one_kernel<16, 16>, grid, s, stop, a, tiles);
-      else launch_k(sls_one_kernel<32, 16>, grid, s, stop, a, tiles);
+      if (D == 16) launch_k(sls_one_kernel<4, 16, E>, grid, s, stop, a, tiles);
+      else if (D == 32) launch_k(sls_one_kernel<8, 16, E>, grid, s, stop, a, tiles);
+      else if (D == 64) launch_k(sls_one_kernel<16, 16, E>, grid, s, stop, a, tiles);
+      else launch_k(sls_one_kernel<32, 16, E>, grid, s, stop, a, tiles);
     }
     return hipGetLastError();
   }
-  log_launch(tune.log, "sls_kernel<%d,%s>[%lld wg]", lanes_per_row(D), exact ? "sequential" : (tune.sls_nt ? "split,nt" : "split"),
+  log_launch(tune.log, "sls_kernel<%d,%s%s%s>[%lld wg]", lanes_per_row(D), exact ? "sequential" : (tune.sls_nt ? "split,nt" : "split"), sep, dt,
              (long long)sls_grid_blocks(a, exact, tune));
   // the non-temporal hint is for bags of many rows out of big tables; the one-lookup models (W&D, NCF, MT-WnD:
   // the sequential form) keep their rows cacheable -- NCF's tables live in the Infinity Cache (measured: -3 % with it)
   const int nt = exact ? 0 : tune.sls_nt;
-  if (D <= 8) return launch_u<2, 4>(a, exact, nt, s, stop);
-  if (D <= 16) return launch_u<4, 4>(a, exact, nt, s, stop);
-  if (D <= 32) return launch_u<8, 4>(a, exact, nt, s, stop);
-  if (D <= 64) return launch_u<16, 4>(a, exact, nt, s, stop);
-  if (D <= 128) return launch_u<32, 4>(a, exact, nt, s, stop);
-  return launch_u<64, 4>(a, exact, nt, s, stop);
+  if (D <= 8) return launch_u<2, 4, E>(a, exact, nt, s, stop);
+  if (D <= 16) return launch_u<4, 4, E>(a, exact, nt, s, stop);
+  if (D <= 32) return launch_u<8, 4, E>(a, exact, nt, s, stop);
+  if (D <= 64) return launch_u<16, 4, E>(a, exact, nt, s, stop);
+  if (D <= 128) return launch_u<32, 4, E>(a, exact, nt, s, stop);
+  return launch_u<64, 4, E>(a, exact, nt, s, stop);
+}
+
+hipError_t launch_sls(const SlsArgs& a, int exact, const Tune& tune, hipStream_t s, hipEvent_t stop, int dtype) {
+  if (dtype == DRS_TABLE_FP16) return launch_sls_e<F16>(a, exact, tune, s, stop);
+  if (dtype == DRS_TABLE_BF16) return launch_sls_e<BF16>(a, exact, tune, s, stop);
+  return launch_sls_e<F32>(a, exact, tune, s, stop);
 }
 
 // ---------------------------------------------------------------------------
@@ -920,6 +980,38 @@ __global__ void fill_uniform_kernel(float* W, int64_t n, int32_t t, float lo, fl
     z ^= z >> 31;
     const float u = (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
     W[i] = __fmaf_rn(u, span, lo);
+  }
+}
+
+// "table_dtype": an fp32 value as it is stored in a table of element type dt (fp16 / bf16: the hardware's
+// round-to-nearest-even conversions, v_cvt_f16_f32 / v_cvt_pk_bf16_f32 -- NaN stays NaN, overflow gives +-inf, fp16
+// subnormals are kept), and back (exact)
+__device__ __forceinline__ void store_elem(void* W, int dt, int64_t i, float x) {
+  if (dt == DRS_TABLE_FP16) static_cast<_Float16*>(W)[i] = (_Float16)x;
+  else if (dt == DRS_TABLE_BF16) static_cast<__bf16*>(W)[i] = (__bf16)x;
+  else static_cast<float*>(W)[i] = x;
+}
+__device__ __forceinline__ float load_elem(const void* W, int dt, int64_t i) {
+  if (dt == DRS_TABLE_FP16) return F16::up1(static_cast<const uint16_t*>(W)[i]);
+  if (dt == DRS_TABLE_BF16) return BF16::up1(static_cast<const uint16_t*>(W)[i]);
+  return static_cast<const float*>(W)[i];
+}
+// n elements of type sdt -> type ddt (the arena conversion of "table_dtype", drs_set_table's staged rows)
+__global__ void convert_table_kernel(const void* src, int sdt, void* dst, int ddt, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    store_elem(dst, ddt, i, load_elem(src, sdt, i));
+}
+// fill_uniform_kernel's fp32 value, rounded to the table's element type
+__global__ void fill_uniform_round_kernel(void* W, int dt, int64_t n, int32_t t, float lo, float hi, uint64_t seed) {
+  const float span = hi - lo;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)i + ((uint64_t)(uint32_t)t << 40) + 1ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    const float u = (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
+    store_elem(W, dt, i, __fmaf_rn(u, span, lo));
   }
 }
 
@@ -1050,6 +1142,24 @@ hipError_t launch_fill_uniform(float* W, int64_t n, int32_t t, float lo, float h
   const int64_t want = (n + 255) / 256;
   const unsigned grid = (unsigned)(want < 8192 ? want : 8192);
   hipLaunchKernelGGL(fill_uniform_kernel, dim3(grid), dim3(256), 0, s, W, n, t, lo, hi, seed);
+  return hipGetLastError();
+}
+
+hipError_t launch_fill_uniform_dtype(void* W, int dtype, int64_t n, int32_t t, float lo, float hi, uint64_t seed,
+                                     hipStream_t s) {
+  if (dtype == DRS_TABLE_FP32) return launch_fill_uniform(static_cast<float*>(W), n, t, lo, hi, seed, s);
+  if (n <= 0) return hipSuccess;
+  const int64_t want = (n + 255) / 256;
+  const unsigned grid = (unsigned)(want < 8192 ? want : 8192);
+  hipLaunchKernelGGL(fill_uniform_round_kernel, dim3(grid), dim3(256), 0, s, W, dtype, n, t, lo, hi, seed);
+  return hipGetLastError();
+}
+
+hipError_t launch_convert_table(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int64_t want = (n + 255) / 256;
+  const unsigned grid = (unsigned)(want < 16384 ? want : 16384);
+  hipLaunchKernelGGL(convert_table_kernel, dim3(grid), dim3(256), 0, s, src, src_dtype, dst, dst_dtype, n);
   return hipGetLastError();
 }
 

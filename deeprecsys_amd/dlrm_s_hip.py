@@ -35,6 +35,17 @@ def _ints(s):
     return np.array([int(x) for x in str(s).split("-")], dtype=int)
 
 
+_TABLE_DTYPES = {"fp32": N.TABLE_FP32, "fp16": N.TABLE_FP16, "bf16": N.TABLE_BF16}
+
+
+def _table_dtype(args):
+    """--accel_table_dtype -> the engine's "table_dtype" value (fp32 when the flag is absent)."""
+    name = str(getattr(args, "accel_table_dtype", "fp32") or "fp32")
+    if name not in _TABLE_DTYPES:
+        raise ValueError("--accel_table_dtype %r: one of %s" % (name, ", ".join(_TABLE_DTYPES)))
+    return _TABLE_DTYPES[name]
+
+
 def _init_table(n, m):
     # models/dlrm_s_caffe2.py:297-299
     return np.random.uniform(low=-np.sqrt(1 / n), high=np.sqrt(1 / n), size=(n, m)).astype(np.float32)
@@ -85,14 +96,20 @@ class _HipNet(object):
         a = self.args
         n_stage = max(int(getattr(a, "num_batches", 0)), 1)
         max_batch = max(int(getattr(a, "max_mini_batch_size", 1)), int(getattr(a, "mini_batch_size", 1)), 1)
+        dtype = _table_dtype(a)
         def make(n_slots):
-            return N.Engine(self.kind, self.ln_emb, self.m_spa, ln_bot_cfg, ln_top_cfg,
-                            interaction_op=interaction_op, interaction_itself=itself,
-                            sigmoid_top=sigmoid_top, max_batch=max_batch,
-                            max_lookups=max(int(a.num_indices_per_lookup), 1),
-                            num_staged_batches=n_stage,
-                            num_slots=n_slots, device=self._device,
-                            ln_task=ln_task, num_tasks=num_tasks)
+            eng = N.Engine(self.kind, self.ln_emb, self.m_spa, ln_bot_cfg, ln_top_cfg,
+                           interaction_op=interaction_op, interaction_itself=itself,
+                           sigmoid_top=sigmoid_top, max_batch=max_batch,
+                           max_lookups=max(int(a.num_indices_per_lookup), 1),
+                           num_staged_batches=n_stage,
+                           num_slots=n_slots, device=self._device,
+                           ln_task=ln_task, num_tasks=num_tasks)
+            # --accel_table_dtype: first, while the arena is empty -- the engine then re-derives its by-model launch
+            # forms (and "preferred_slots") for the element size, and every table write below is rounded on the device
+            if dtype != N.TABLE_FP32:
+                eng.set_option("table_dtype", dtype)
+            return eng
         eng = make(self._num_slots())
         if int(getattr(a, "accel_slots", 0) or 0) <= 0 and eng.get_option("preferred_slots") != eng.num_slots:
             # (an MLP-bound DLRM such as RM3: the class follows from the shapes, which the engine has just read)
