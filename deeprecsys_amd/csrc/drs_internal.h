@@ -141,26 +141,13 @@ struct Done {
 struct XSrc {
   QTable q;
   const float* x[DRS_MAX_COALESCE];
-  // > 0 (gemm32_kernel's scalar-base forms only, launch_gemm): columns [0, ksplit) of an input row come from the
+  // > 0 (gemm32_kernel's scalar-base forms only, gemm.hip gemm_plan): columns [0, ksplit) of an input row come from the
   // queries' own staged arrays (rows ksplit floats apart), columns from ksplit on from `x` at the VIRTUAL row -- W&D's and
   // MT-WnD's first layer reads Concat(dense, pooled embeddings) without the dense rows ever being copied next to the
   // embeddings (models/wide_and_deep.py:271-281).  A multiple of 32, >= 64, < K.
   int32_t ksplit;
 };
 
-hipError_t launch_fc(const float* x, int64_t ldx, int64_t M, int32_t K, const float* W,
-                     const float* b, int32_t N, int32_t act, float* y, int64_t ldy,
-                     const Tune& tune, hipStream_t stream, const Done* done = nullptr,
-                     const XSrc* xs = nullptr);
-
-// would launch_gemm take a form that reads a split input row (XSrc::ksplit) for this layer?  (gemm.hip)
-bool gemm_split_applicable(const float* x, int64_t ldx, int64_t M, int32_t K, const float* W, int32_t N, const XSrc& xs,
-                           const Tune& tune);
-// Register-blocked GEMM for wide layers (gemm.hip); false = not applicable, use launch_fc's
-// own kernel.  zero_page: 16 B of zeros in device memory.
-bool launch_gemm(const float* x, int64_t ldx, int64_t M, int32_t K, const float* W, const float* b,
-                 int32_t N, int32_t act, float* y, int64_t ldy, const Tune& tune,
-                 hipStream_t stream, const Done& done, const XSrc& xs, hipError_t* err);
 
 // Fused chain of up to DRS_MAX_CHAIN FC layers on 16-row slabs; intermediate
 // activations never leave LDS.
@@ -177,12 +164,9 @@ struct ChainArgs {
   float* y;
   int64_t ldy;
 };
-hipError_t launch_chain(const ChainArgs& a, const Tune& tune, hipStream_t stream,
-                        const Done* done = nullptr, const XSrc* xs = nullptr);
-size_t chain_lds_bytes(const ChainArgs& a, const Tune& tune);
-// two chains on the same rows in one launch (bottom MLP, then the top MLP that reads the
-// buffer the first one wrote its last layer into)
-// Optional dot interaction BETWEEN the two chains of launch_chain2 (DLRM "dot",
+// Two chains on the same rows in one launch (bottom MLP, then the top MLP that reads the
+// buffer the first one wrote its last layer into), mlp.hip plan_chains.
+// Optional dot interaction BETWEEN the two chains (DLRM "dot",
 // models/dlrm_s_caffe2.py:334-354): the first chain writes the dense_out slot of T, the
 // interaction turns T [M, F*D] into R [M, D + P], the second chain reads R.
 struct DotArgs {
@@ -203,14 +187,6 @@ struct SumArgs {
   float* dst;
   int64_t ldd;
 };
-hipError_t launch_chain2(const ChainArgs& a, const ChainArgs* b, const Tune& tune, hipStream_t stream,
-                         const Done* done = nullptr, const XSrc* xs = nullptr,
-                         const DotArgs* dot = nullptr, const SumArgs* sum = nullptr);
-// would launch_chain2(a, &b, ..., dot) run as the stream kernel?  (With a dot interaction in
-// between it is the only kernel that can.)
-bool stream_applicable(const ChainArgs& a, const ChainArgs& b, const Tune& tune, const XSrc* xs,
-                       const DotArgs* dot, const SumArgs* sum = nullptr, bool* can_defer = nullptr);
-size_t chain2_lds_bytes(const ChainArgs& a, const ChainArgs& b, const Tune& tune);
 
 // T [B, F, D] (sample stride ldt) -> R [B, D + P] (ld = ldr), see drs_interact_dot
 hipError_t launch_interact_dot(const float* T, int64_t ldt, int64_t B, int32_t F, int32_t D,

@@ -1,6 +1,7 @@
 // libdrs_hip.so, host side: ONE launch set -- which kernels, on which streams, in which order (enqueue_forward), its completion
 // (wait_slot), and the entry points on top: drs_forward*, drs_wait, drs_sync, drs_fetch_interaction, the operator-level calls.
 #include "engine.h"
+#include "mlp_stream.h"
 
 namespace drs {
 namespace eng {
@@ -31,8 +32,6 @@ void fill_chain(ChainArgs& c, const Mlp& m, int l0, int cnt, const float* x, int
   }
 }
 
-constexpr size_t kChainLds = 156 * 1024;
-
 // The stream the set's next MLP launch goes on.  "mlp_layout" 0: the set's own MLP stream.  1: wide-layer
 // GEMMs of full launch sets on the gather stream, everything else on the set's MLP stream; when the kind
 // changes inside a set, the new stream waits for an event recorded behind the set's previous launch.
@@ -59,44 +58,44 @@ hipError_t rejoin_stream(drs_engine* e, Slot& s) {
   return mlp_launch_stream(e, s, false, 0, &st);
 }
 
+
 // Run all layers of `m` on x -> y.  A huge layer runs as its own 2-D launch; runs of
 // ordinary layers are fused into one LDS-resident chain.  Segment outputs that are not
-// the final one ping-pong between s.H and s.Hb.
-int32_t run_mlp(drs_engine* e, Slot& s, const Mlp& m, const float* x, int64_t ldx, int64_t M,
-                float* y, int64_t ldy, const Done* done = nullptr, const XSrc* xs = nullptr) {
+// the final one ping-pong between s.H and s.Hb.  first (optional): the caller's plan of layer 0 alone.
+int32_t run_mlp(drs_engine* e, Slot& s, const Mlp& m, const float* x, int64_t ldx, int64_t M, float* y, int64_t ldy,
+                const Done* done = nullptr, const XSrc* xs = nullptr, const MlpPlan* first = nullptr) {
   const int n_layers = (int)m.layers.size();
-  int l0 = 0;
   const float* in = x;
   int64_t ldin = ldx;
-  while (l0 < n_layers) {
-    int cnt = 1;
-    ChainArgs c;
-    memset(&c, 0, sizeof c);
-    bool standalone = is_wide(e, m, l0);
-    if (!standalone) {
-      cnt = 0;
+  for (int l0 = 0, cnt = 1; l0 < n_layers; l0 += cnt) {
+    MlpPlan own;
+    // layers [l0, l0 + n) as one chain; n == 0: layer l0 alone
+    auto plan = [&](int n) {
+      const bool last = l0 + (n ? n : 1) == n_layers;
+      float* out = last ? y : (in == s.H ? s.Hb : s.H);
+      const int64_t ldo = last ? ldy : e->ldH;
+      const Done* d = last ? done : nullptr;
+      const XSrc* x0 = l0 == 0 ? xs : nullptr;
+      if (!n)
+        return plan_layer(in, ldin, M, m.ln[l0], m.layers[l0].W, m.layers[l0].b, m.ln[l0 + 1], act_of(m, l0), out, ldo,
+                          e->tune, d, x0, &own);
+      ChainArgs c;
+      fill_chain(c, m, l0, n, in, ldin, M, out, ldo);
+      return plan_chains(c, nullptr, e->tune, d, x0, nullptr, nullptr, &own);
+    };
+    const bool given = l0 == 0 && first;
+    cnt = 0;
+    if (!given && !is_wide(e, m, l0))
       while (l0 + cnt < n_layers && cnt < DRS_MAX_CHAIN && !is_wide(e, m, l0 + cnt)) ++cnt;
-      for (;;) {
-        fill_chain(c, m, l0, cnt, in, ldin, M, nullptr, 0);
-        if (chain_lds_bytes(c, e->tune) <= kChainLds) break;
-        if (cnt == 1) { standalone = true; break; }
-        --cnt;
-      }
-    }
-    const bool last = l0 + cnt == n_layers;
-    float* out = last ? y : (in == s.H ? s.Hb : s.H);
-    const int64_t ldo = last ? ldy : e->ldH;
+    while (cnt > 0 && !plan(cnt)) --cnt;   // the longest run that a chain kernel holds, else the layer alone
+    const bool ok = given || cnt > 0 || plan(0);
+    cnt = cnt > 0 ? cnt : 1;
+    const MlpPlan& p = given ? *first : own;
     hipStream_t st = s.stream;
-    HIP_TRY(e, mlp_launch_stream(e, s, standalone && is_wide(e, m, l0), M, &st));
-    if (standalone) {
-      HIP_TRY(e, launch_fc(in, ldin, M, m.ln[l0], m.layers[l0].W, m.layers[l0].b, m.ln[l0 + 1],
-                           act_of(m, l0), out, ldo, e->tune, st, last ? done : nullptr,
-                           l0 == 0 ? xs : nullptr));
-    } else {
-      c.y = out; c.ldy = ldo;
-      HIP_TRY(e, launch_chain(c, e->tune, st, last ? done : nullptr, l0 == 0 ? xs : nullptr));
-    }
-    in = out; ldin = ldo; l0 += cnt;
+    HIP_TRY(e, mlp_launch_stream(e, s, is_wide(e, m, l0), M, &st));
+    if (!ok) return fail(e, DRS_ERR_HIP, "no kernel takes the %dx%d layer %d", m.ln[l0], m.ln[l0 + 1], l0);
+    HIP_TRY(e, launch_plan(p, e->tune, st));
+    in = p.a.y; ldin = p.a.ldy;
   }
   return DRS_OK;
 }
@@ -104,48 +103,21 @@ int32_t run_mlp(drs_engine* e, Slot& s, const Mlp& m, const float* x, int64_t ld
 // DLRM: bottom MLP, interaction and top MLP of a 16-row slab in ONE launch (the slab's
 // dense_out never waits for a kernel boundary).  "cat": the top chain reads the buffer the
 // bottom chain wrote; "dot": the stream kernel computes T.T^T in LDS between the chains.
-struct FusedPlan {
-  bool ok = false;
-  ChainArgs a, b;
-  DotArgs dot;
-  bool has_dot = false;
-};
-
-FusedPlan fused_plan(const drs_engine* e, const Slot& s, int64_t Mv, float* out, const XSrc* xs, bool* can_defer = nullptr) {
-  if (can_defer) *can_defer = false;
-  FusedPlan p;
-  if (!e->mlp_fuse || Mv < e->mlp_fuse_rows || e->kind != DRS_MODEL_DLRM) return p;
+bool fused_plan(const drs_engine* e, const Slot& s, int64_t Mv, float* out, const Done* dp, const XSrc* xs, MlpPlan* p) {
+  if (!e->mlp_fuse || Mv < e->mlp_fuse_rows || e->kind != DRS_MODEL_DLRM) return false;
   const int nb = (int)e->bot.layers.size(), nt = (int)e->top.layers.size();
-  if (nb < 1 || nt < 1 || nb > DRS_MAX_CHAIN || nt > DRS_MAX_CHAIN) return p;
-  for (int l = 0; l < nb; ++l) if (is_wide(e, e->bot, l)) return p;
-  for (int l = 0; l < nt; ++l) if (is_wide(e, e->top, l)) return p;
-  fill_chain(p.a, e->bot, 0, nb, nullptr, e->m_den, Mv, s.T, e->ldT);
+  if (nb < 1 || nt < 1 || nb > DRS_MAX_CHAIN || nt > DRS_MAX_CHAIN) return false;
+  for (int l = 0; l < nb; ++l) if (is_wide(e, e->bot, l)) return false;
+  for (int l = 0; l < nt; ++l) if (is_wide(e, e->top, l)) return false;
+  ChainArgs a, b;
+  fill_chain(a, e->bot, 0, nb, nullptr, e->m_den, Mv, s.T, e->ldT);
   if (e->interaction_op == DRS_INTERACT_CAT) {
-    fill_chain(p.b, e->top, 0, nt, s.T, e->ldT, Mv, out, e->n_out);
-    p.ok = can_defer ? (stream_applicable(p.a, p.b, e->tune, xs, nullptr, nullptr, can_defer) || chain2_lds_bytes(p.a, p.b, e->tune) <= kChainLds)
-                     : (chain2_lds_bytes(p.a, p.b, e->tune) <= kChainLds || stream_applicable(p.a, p.b, e->tune, xs, nullptr));
-  } else {
-    fill_chain(p.b, e->top, 0, nt, s.R, e->ldR, Mv, out, e->n_out);
-    p.dot.T = s.T; p.dot.ldt = e->ldT; p.dot.F = e->T + 1; p.dot.D = e->D; p.dot.itself = e->itself;
-    p.dot.R = s.R; p.dot.ldr = e->ldR;
-    p.has_dot = true;
-    p.ok = stream_applicable(p.a, p.b, e->tune, xs, &p.dot, nullptr, can_defer);   // only the stream kernel has the interaction
+    fill_chain(b, e->top, 0, nt, s.T, e->ldT, Mv, out, e->n_out);
+    return plan_chains(a, &b, e->tune, dp, xs, nullptr, nullptr, p);
   }
-  return p;
-}
-
-bool fused_applicable(const drs_engine* e, const Slot& s, int64_t Mv, const XSrc* xs) {
-  return fused_plan(e, s, Mv, s.d_out, xs).ok;
-}
-
-bool try_fused_bottom_top(drs_engine* e, Slot& s, int64_t Mv, float* out, const Done* dp,
-                          const XSrc* xs, int32_t* rc) {
-  *rc = DRS_OK;
-  FusedPlan p = fused_plan(e, s, Mv, out, xs);
-  if (!p.ok) return false;
-  hipError_t r = launch_chain2(p.a, &p.b, e->tune, s.stream, dp, xs, p.has_dot ? &p.dot : nullptr);
-  if (r != hipSuccess) *rc = fail(e, DRS_ERR_HIP, "launch_chain2: %s", hipGetErrorString(r));
-  return true;
+  fill_chain(b, e->top, 0, nt, s.R, e->ldR, Mv, out, e->n_out);
+  const DotArgs dot = {s.T, e->ldT, e->T + 1, e->D, e->itself, s.R, e->ldR};
+  return plan_chains(a, &b, e->tune, dp, xs, &dot, nullptr, p);
 }
 
 // shared_stream: 1 = one stream for everything (launch sets strictly back to back);
@@ -181,10 +153,8 @@ hipStream_t job_gather_stream(const drs_engine* e, const Slot& s, int64_t Mv) {
   return (e->shared_stream == 2 && Mv <= e->mlp_small_rows && !e->small_piped) ? s.own_stream : s.gather_stream;
 }
 
-// Enqueue n >= 1 coalesced queries (query i = first bs[i] samples of *bts[i]) as ONE set of
-// launches on the slot's stream.
-int32_t enqueue_forward(drs_engine* e, Slot& s, int n, const Batch* const* bts, const int32_t* bss) {
-  if (n < 1 || n > DRS_MAX_COALESCE) return fail(e, DRS_ERR_BAD_ARG, "1..%d queries per launch, got %d", DRS_MAX_COALESCE, n);
+
+static int32_t weights_ready(drs_engine* e) {
   for (int t = 0; t < e->T; ++t)
     if (!e->table_set[t]) return fail(e, DRS_ERR_STATE, "table %d has no data", t);
   int32_t rc;
@@ -197,58 +167,88 @@ int32_t enqueue_forward(drs_engine* e, Slot& s, int n, const Batch* const* bts, 
     if ((rc = mlp_ready(e, au, "attention"))) return rc;
   for (auto& rn : e->rnn)
     if ((rc = mlp_ready(e, rn, "rnn"))) return rc;
-  if (!e->rnn.empty() && e->att_dirty) {
+  return DRS_OK;
+}
+
+// e->d_att: {W, b} of the first `layers` layers (0: all) of every unit, as a device table of pointers
+static hipError_t upload_weight_table(drs_engine* e, const std::vector<Mlp>& units, size_t layers) {
+  std::vector<const float*> hp;
+  for (auto& u : units)
+    for (size_t l = 0; l < (layers ? layers : u.layers.size()); ++l) { hp.push_back(u.layers[l].W); hp.push_back(u.layers[l].b); }
+  hipError_t r = hipMalloc(reinterpret_cast<void**>(&e->d_att), sizeof(float*) * hp.size());
+  if (r == hipSuccess) r = hipMemcpy(e->d_att, hp.data(), sizeof(float*) * hp.size(), hipMemcpyHostToDevice);
+  return r;
+}
+
+// The DIEN recurrence's and the DIN attention units' weights in the form their kernels read: rebuilt after drs_set_fc
+// changed them (att_dirty).  (drs_set_fc is synchronous; nothing of this engine is in flight while weights change)
+static int32_t pack_weights(drs_engine* e) {
+  if (!e->att_dirty) return DRS_OK;
+  if (!e->rnn.empty()) {
     const int H = e->rnn[0].ln[1];
     if (!e->d_att) {
-      std::vector<const float*> hp;
-      for (auto& rn : e->rnn) { hp.push_back(rn.layers[0].W); hp.push_back(rn.layers[0].b); hp.push_back(rn.layers[1].W); hp.push_back(rn.layers[1].b); }
-      HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&e->d_att), sizeof(float*) * hp.size()));
-      HIP_TRY(e, hipMemcpy(e->d_att, hp.data(), sizeof(float*) * hp.size(), hipMemcpyHostToDevice));
+      HIP_TRY(e, upload_weight_table(e, e->rnn, 2));
       HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&e->d_att_packed), sizeof(float) * (size_t)dien_packed_floats(e->D, H)));
     }
     HIP_TRY(e, launch_dien_pack(e->d_att, e->d_att_packed, e->D, H, nullptr));
     HIP_TRY(e, hipStreamSynchronize(nullptr));
-    e->att_dirty = false;
-  }
-  if (!e->att.empty() && e->att_dirty && e->din_any) {
+  } else if (!e->att.empty() && e->din_any) {
     // any-shape units (din_any.hip): the kernel reads the layers where drs_set_fc put them
     if (!e->d_att) {
-      std::vector<const float*> hp;
-      for (auto& au : e->att)
-        for (auto& L : au.layers) { hp.push_back(L.W); hp.push_back(L.b); }
-      HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&e->d_att), sizeof(float*) * hp.size()));
-      HIP_TRY(e, hipMemcpy(e->d_att, hp.data(), sizeof(float*) * hp.size(), hipMemcpyHostToDevice));
+      HIP_TRY(e, upload_weight_table(e, e->att, 0));
       HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&e->d_att_ln), sizeof(int32_t) * e->att[0].ln.size()));
       HIP_TRY(e, hipMemcpy(e->d_att_ln, e->att[0].ln.data(), sizeof(int32_t) * e->att[0].ln.size(), hipMemcpyHostToDevice));
     }
-    e->att_dirty = false;
-  }
-  if (!e->att.empty() && e->att_dirty) {
+  } else if (!e->att.empty()) {
     const int U = (int)e->att.size(), h = e->att[0].ln[1];
     if (!e->d_att) {
-      std::vector<const float*> hp;
-      for (auto& au : e->att) { hp.push_back(au.layers[0].W); hp.push_back(au.layers[0].b); hp.push_back(au.layers[1].W); hp.push_back(au.layers[1].b); }
-      HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&e->d_att), sizeof(float*) * hp.size()));
-      HIP_TRY(e, hipMemcpy(e->d_att, hp.data(), sizeof(float*) * hp.size(), hipMemcpyHostToDevice));
+      HIP_TRY(e, upload_weight_table(e, e->att, 2));
       HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&e->d_att_packed), sizeof(float) * (size_t)U * din_unit_stride(e->D, h)));
     }
-    // (drs_set_fc is synchronous; nothing of this engine is in flight while weights change)
     HIP_TRY(e, launch_din_pack(e->d_att, e->d_att_packed, U, e->D, h, nullptr));
     HIP_TRY(e, hipStreamSynchronize(nullptr));
-    e->att_dirty = false;
+  } else {
+    return DRS_OK;
   }
-  // layout of the job: zero-sized queries take no rows
+  e->att_dirty = false;
+  return DRS_OK;
+}
+
+// One launch set being enqueued: what its steps hand on to each other.
+struct SetCtx {
+  drs_engine* e;
+  Slot& s;
   QTable q;
-  memset(&q, 0, sizeof q);
   const Batch* qb[DRS_MAX_COALESCE];
+  int64_t Mv;
+  int32_t c;              // valid samples
+  hipStream_t gstream;    // the gather's stream
+  bool piped, joined;     // does s.stream differ from it / has it been made to wait for the gather yet?
+  bool din_fused;
+  Done done;
+  const Done* dp;         // the set's completion hand-off (zero copy), or null
+  float* out;
+  bool out_dma;
+  XSrc xs;                // the queries' dense rows
+  hipError_t join() {
+    if (joined) return hipSuccess;
+    joined = true;
+    return hipStreamWaitEvent(s.stream, s.ev_sls, 0);
+  }
+};
+
+// layout of the set: zero-sized queries take no rows
+static int32_t lay_out_set(SetCtx& x, int n, const Batch* const* bts, const int32_t* bss) {
+  QTable& q = x.q;
+  memset(&q, 0, sizeof q);
   int32_t v = 0, c = 0;
   for (int i = 0; i < n; ++i) {
     if (bss[i] < 0 || bss[i] > bts[i]->n_samples)
-      return fail(e, DRS_ERR_BAD_ARG, "bs=%d outside [0, %d]", bss[i], bts[i]->n_samples);
-    s.q_bs[i] = bss[i];
-    s.q_vstart[i] = v;
+      return fail(x.e, DRS_ERR_BAD_ARG, "bs=%d outside [0, %d]", bss[i], bts[i]->n_samples);
+    x.s.q_bs[i] = bss[i];
+    x.s.q_vstart[i] = v;
     if (bss[i] == 0) continue;
-    qb[q.n_q] = bts[i];
+    x.qb[q.n_q] = bts[i];
     q.vstart[q.n_q] = v;
     q.cum[q.n_q] = c;
     q.bs[q.n_q] = bss[i];
@@ -258,34 +258,24 @@ int32_t enqueue_forward(drs_engine* e, Slot& s, int n, const Batch* const* bts, 
   }
   q.vstart[q.n_q] = v;
   q.cum[q.n_q] = c;
-  if (v > e->max_rows) return fail(e, DRS_ERR_BAD_ARG, "%d coalesced rows exceed the slot capacity %lld", v, (long long)e->max_rows);
-  s.last_n = n;
-  s.last_bs = c;
-  s.busy = true;
-  s.polled = false;
-  if (c == 0) return DRS_OK;
-  const int64_t Mv = v;
-  // Pipelined mode, small launch set (a single query: 256 rows = 16 MLP workgroups on a 256-CU
-  // chip): its latency-bound MLP launch goes on the SLOT's own stream, so the MLP launches of
-  // consecutive sets overlap each other instead of queueing on the one shared MLP stream
-  // (one query per launch set: 23 k -> see DESIGN 3.5).  Full sets (8 queries, 128 workgroups)
-  // keep the shared stream: there the extra concurrency only takes CUs from the gather.
-  // Safe: a slot is reused only after its previous job was observed complete on the host.
-  s.stream = job_stream(e, s, Mv);
-  s.cur = nullptr;               // (the set's first MLP launch needs no event: join() orders it behind the gather)
-  s.dlog.len = 0; s.dlog.text[0] = 0;
-  // ("dispatch_log" 1: the launch functions note what they choose for this set -- drs_last_dispatch; off by default: four
-  //  to eight vsnprintf per set are ~1 us of the ~11 us a small set costs the host)
-  e->tune.log = e->dispatch_log ? &s.dlog : nullptr;
-  e->tune.xbuf = s.xbuf; e->tune.xcnt = s.xcnt; e->tune.xbuf_rows = s.xrows; e->tune.xbuf_cols = s.xcols;
-  // (both belong to THIS slot: launches made outside this function -- the operator-level entry points -- must not see them)
-  struct TuneScope { Tune& t; ~TuneScope() { t.log = nullptr; t.xbuf = nullptr; t.xcnt = nullptr; } } tune_scope{e->tune};
+  if (v > x.e->max_rows) return fail(x.e, DRS_ERR_BAD_ARG, "%d coalesced rows exceed the slot capacity %lld", v, (long long)x.e->max_rows);
+  x.Mv = v;
+  x.c = c;
+  return DRS_OK;
+}
+
+// The gather (the fused DIN launch: gather + attention units) on the gather's stream.
+static int32_t launch_gather(SetCtx& x) {
+  drs_engine* e = x.e;
+  Slot& s = x.s;
+  const QTable& q = x.q;
+  const int64_t Mv = x.Mv;
   log_launch(e->tune.log, "set[%d queries, %d rows, gather on %s, mlp on %s]", q.n_q, (int)Mv,
              job_gather_stream(e, s, Mv) == e->stream_g ? "stream_g" : "own", s.stream == s.own_stream ? "own" : "shared");
-  const hipStream_t gstream = job_gather_stream(e, s, Mv);
+  const hipStream_t gstream = x.gstream = job_gather_stream(e, s, Mv);
   const bool prof = e->profiling >= 1;
   const bool evts = e->profiling >= 2;
-  const bool piped = gstream != s.stream;
+  const bool piped = x.piped = gstream != s.stream;
   if (evts) HIP_TRY(e, hipEventRecord(s.ev[0], gstream));
 
   SlsArgs a;
@@ -293,9 +283,9 @@ int32_t enqueue_forward(drs_engine* e, Slot& s, int n, const Batch* const* bts, 
   a.tables = e->tables; a.tab_off = e->d_tab_off; a.tab_rows = e->d_tab_rows;
   a.q = q;
   for (int i = 0; i < q.n_q; ++i) {
-    a.idx[i] = qb[i]->idx;
-    a.off[i] = qb[i]->off;
-    a.uniform_len[i] = e->sls_uniform ? qb[i]->uniform_len : -1;
+    a.idx[i] = x.qb[i]->idx;
+    a.off[i] = x.qb[i]->off;
+    a.uniform_len[i] = e->sls_uniform ? x.qb[i]->uniform_len : -1;
   }
   a.idx_stride = e->cap; a.off_stride = e->max_batch + 1;
   a.out = s.T; a.ld_out = e->ldT; a.col0 = e->kind == DRS_MODEL_NCF ? 0 : e->w0;
@@ -304,13 +294,13 @@ int32_t enqueue_forward(drs_engine* e, Slot& s, int n, const Batch* const* bts, 
   // Bags of a few rows (W&D / NCF: one lookup per table) would leave most of a wave idle in the
   // wave-per-bag variant: a lane group per bag is both faster there and bit-exact.
   bool short_bags = true;
-  for (int i = 0; i < q.n_q; ++i) short_bags = short_bags && qb[i]->uniform_len >= 0 && qb[i]->uniform_len <= e->sls_short_bag;
+  for (int i = 0; i < q.n_q; ++i) short_bags = short_bags && x.qb[i]->uniform_len >= 0 && x.qb[i]->uniform_len <= e->sls_short_bag;
   // ... unless the flat variant takes the launch (fixed-length bags of >= 2 rows: several short
   // bags share a wave and all of its row loads are in flight at once)
   const int exact_now = e->sls_exact || (short_bags && !sls_flat_applicable(a, e->tune));
   // DIN, default mode: the attention units are fused into the gather launch (din.hip)
-  const bool din_fused = e->kind == DRS_MODEL_DIN && !e->sls_exact && e->din_fused && !e->din_any &&
-                         din_fused_applicable(e->D, e->att[0].ln[1]);
+  const bool din_fused = x.din_fused = e->kind == DRS_MODEL_DIN && !e->sls_exact && e->din_fused && !e->din_any &&
+                                       din_fused_applicable(e->D, e->att[0].ln[1]);
   s.ts_blocks = prof ? (din_fused ? din_fused_grid(a, e->tune) : sls_grid_blocks(a, exact_now, e->tune)) : 0;
   if (prof) {
     // algorithmic bytes of THIS launch (rows + int32 indices + length + pooled output
@@ -318,11 +308,11 @@ int32_t enqueue_forward(drs_engine* e, Slot& s, int n, const Batch* const* bts, 
     int64_t bytes = 0;
     for (int i = 0; i < q.n_q; ++i)
       for (int t = 0; t < e->T; ++t)
-        bytes += (int64_t)qb[i]->h_off[(size_t)t * (e->max_batch + 1) + q.bs[i]] * ((int64_t)e->D * table_elem_bytes(e->table_dtype) + 4) +
+        bytes += (int64_t)x.qb[i]->h_off[(size_t)t * (e->max_batch + 1) + q.bs[i]] * ((int64_t)e->D * table_elem_bytes(e->table_dtype) + 4) +
                  (int64_t)q.bs[i] * (4 + (int64_t)e->D * 4);
     // (the fused DIN launch writes the 4 D floats of the top MLP's input row per sample instead
     // of T pooled vectors)
-    if (din_fused) bytes -= (int64_t)c * (e->T - 4) * e->D * 4;
+    if (din_fused) bytes -= (int64_t)x.c * (e->T - 4) * e->D * 4;
     s.ts_bytes = bytes;
   }
   // pipelined mode: the event the MLP stream waits for is recorded by the gather dispatch itself
@@ -333,183 +323,208 @@ int32_t enqueue_forward(drs_engine* e, Slot& s, int n, const Batch* const* bts, 
   else
     HIP_TRY(e, launch_sls(a, exact_now, e->tune, gstream, piped ? s.ev_sls : nullptr, e->table_dtype));
   if (evts) HIP_TRY(e, hipEventRecord(s.ev[1], gstream));
-  bool joined = !piped;   // has s.stream been made to wait for the gather yet?
-  auto join = [&]() -> hipError_t {
-    if (joined) return hipSuccess;
-    joined = true;
-    return hipStreamWaitEvent(s.stream, s.ev_sls, 0);
-  };
+  x.joined = !piped;
+  return DRS_OK;
+}
 
-  // last kernel of the job: outputs either go straight to host-mapped pinned memory
-  // followed by a flag store (zero copy, no stream sync), or to a device buffer + memcpy
+// last kernel of the job: outputs either go straight to host-mapped pinned memory
+// followed by a flag store (zero copy, no stream sync), or to a device buffer + memcpy
+static void arm_hand_off(SetCtx& x) {
+  drs_engine* e = x.e;
+  Slot& s = x.s;
   s.seq += 1;
   if (s.seq == 0) s.seq = 1;
-  Done done;
+  Done& done = x.done;
   memset(&done, 0, sizeof done);
   done.counter = s.d_counter; done.host_flag = s.dm_out; done.host_err = s.dm_out + 1;
   done.dev_err = s.d_err; done.seq = s.seq;
-  if (prof && e->zero_copy) { done.ts = s.d_ts; done.ts_blocks = (uint32_t)s.ts_blocks; done.span_acc = s.d_span_acc; done.host_span = s.dm_span; }
-  const Done* dp = e->zero_copy ? &done : nullptr;
-  float* out = s.d_out;          // kernels store to the device buffer; see Done::host_out
+  if (e->profiling >= 1 && e->zero_copy) { done.ts = s.d_ts; done.ts_blocks = (uint32_t)s.ts_blocks; done.span_acc = s.d_span_acc; done.host_span = s.dm_span; }
+  x.dp = e->zero_copy ? &done : nullptr;
+  x.out = s.d_out;          // kernels store to the device buffer; see Done::host_out
   done.dev_out = s.d_out; done.host_out = reinterpret_cast<float*>(s.dm_out + kOutOffset);
-  done.out_words = (uint32_t)(Mv * e->n_out);
+  done.out_words = (uint32_t)(x.Mv * e->n_out);
   // "out_dma": the outputs leave through a copy-engine transfer queued behind the last kernel, and the flag through
   // a stream-ordered 32-bit write behind that -- the last workgroup then hands over the error word only
-  const bool out_dma = e->zero_copy && e->out_dma && (int64_t)done.out_words * 4 >= e->out_dma;
-  if (out_dma) { done.out_words = 0; done.host_flag = nullptr; }
-  XSrc xs;
-  memset(&xs, 0, sizeof xs);
-  xs.q = q;
-  for (int i = 0; i < q.n_q; ++i) xs.x[i] = qb[i]->dense;
-  if (e->kind == DRS_MODEL_DIEN) {
-    // the two recurrent layers over the pooled behaviour rows -> top MLP input R [rows, H + 3D]
-    HIP_TRY(e, join());
-    const float* rw[8];
-    for (int l = 0; l < 2; ++l) {
-      rw[4 * l + 0] = e->rnn[l].layers[0].W; rw[4 * l + 1] = e->rnn[l].layers[0].b;
-      rw[4 * l + 2] = e->rnn[l].layers[1].W; rw[4 * l + 3] = e->rnn[l].layers[1].b;
+  x.out_dma = e->zero_copy && e->out_dma && (int64_t)done.out_words * 4 >= e->out_dma;
+  if (x.out_dma) { done.out_words = 0; done.host_flag = nullptr; }
+  memset(&x.xs, 0, sizeof x.xs);
+  x.xs.q = x.q;
+  for (int i = 0; i < x.q.n_q; ++i) x.xs.x[i] = x.qb[i]->dense;
+}
+
+// DIEN: the two recurrent layers over the pooled behaviour rows -> top MLP input R [rows, H + 3D] -> top MLP
+static int32_t mlp_dien(SetCtx& x) {
+  drs_engine* e = x.e;
+  Slot& s = x.s;
+  HIP_TRY(e, x.join());
+  const float* rw[8];
+  for (int l = 0; l < 2; ++l) {
+    rw[4 * l + 0] = e->rnn[l].layers[0].W; rw[4 * l + 1] = e->rnn[l].layers[0].b;
+    rw[4 * l + 2] = e->rnn[l].layers[1].W; rw[4 * l + 3] = e->rnn[l].layers[1].b;
+  }
+  // the top MLP in the recurrence's own launch when it fits ("dien_fuse_top", default on): one workgroup per 16
+  // samples instead of two, one launch less per set
+  const int Hh = e->rnn[0].ln[1], c = x.c;
+  DienTop tp;
+  memset(&tp, 0, sizeof tp);
+  const int nt = (int)e->top.layers.size();
+  // 3: the any-shape form (din_any.hip) -- every shape without an instance in din.hip, or on request
+  const int form = dien_applicable(e->D, Hh) ? e->dien_mfma : 3;
+  const bool mfma_form = form != 3 && form && Hh % 16 == 0;
+  if (e->dien_fuse_top && mfma_form && nt >= 1 && nt <= 4 && e->top.layers[0].packed &&
+      dien_top_fusable(nt, e->top.ln.data(), Hh) && e->top.ln[0] == Hh + 3 * e->D) {
+    tp.n = nt; tp.sc1 = x.dp ? 1 : 0; tp.out = x.out; tp.ldo = e->n_out;
+    for (int l = 0; l < nt; ++l) {
+      const Layer& L = e->top.layers[l];
+      tp.Wp[l] = L.W + ((size_t)L.m * L.n + 63) / 64 * 64; tp.b[l] = L.b;
+      tp.K[l] = e->top.ln[l]; tp.N[l] = e->top.ln[l + 1]; tp.act[l] = act_of(e->top, l);
     }
-    // the top MLP in the recurrence's own launch when it fits ("dien_fuse_top", default on): one workgroup per 16
-    // samples instead of two, one launch less per set
-    const int Hh = e->rnn[0].ln[1];
-    DienTop tp;
-    memset(&tp, 0, sizeof tp);
-    const int nt = (int)e->top.layers.size();
-    // 3: the any-shape form (din_any.hip) -- every shape without an instance in din.hip, or on request
-    const int form = dien_applicable(e->D, Hh) ? e->dien_mfma : 3;
-    const bool mfma_form = form != 3 && form && Hh % 16 == 0;
-    if (e->dien_fuse_top && mfma_form && nt >= 1 && nt <= 4 && e->top.layers[0].packed &&
-        dien_top_fusable(nt, e->top.ln.data(), Hh) && e->top.ln[0] == Hh + 3 * e->D) {
-      tp.n = nt; tp.sc1 = dp ? 1 : 0; tp.out = out; tp.ldo = e->n_out;
-      for (int l = 0; l < nt; ++l) {
-        const Layer& L = e->top.layers[l];
-        tp.Wp[l] = L.W + ((size_t)L.m * L.n + 63) / 64 * 64; tp.b[l] = L.b;
-        tp.K[l] = e->top.ln[l]; tp.N[l] = e->top.ln[l + 1]; tp.act[l] = act_of(e->top, l);
-      }
-      tp.kmax = dien_top_kmax(nt, e->top.ln.data());
+    tp.kmax = dien_top_kmax(nt, e->top.ln.data());
+  }
+  log_launch(e->tune.log, "%s<%d,%d%s>[%d wg]", form == 3 ? "dien_rnn_any_kernel" : mfma_form ? "dien_rnn_mfma_kernel" : "dien_rnn_kernel",
+             e->D, Hh, tp.n ? ",top" : "", form == 3 ? c : mfma_form ? (c + 15) / 16 : (c + 3) / 4);
+  HIP_TRY(e, launch_dien_rnn(s.T, e->ldT, x.q, e->T, e->D, Hh, e->d_att_packed, rw, form, s.R,
+                             e->ldR, s.stream, tp.n ? &tp : nullptr, x.dp));
+  return tp.n ? DRS_OK : run_mlp(e, s, e->top, s.R, e->ldR, x.Mv, x.out, e->n_out, x.dp);
+}
+
+// DIN: attention units over the pooled rows -> top MLP input R [rows, 4D] -> top MLP (all ReLU)
+static int32_t mlp_din(SetCtx& x) {
+  drs_engine* e = x.e;
+  Slot& s = x.s;
+  const int64_t Mv = x.Mv;
+  HIP_TRY(e, x.join());
+  if (e->din_any) {
+    log_launch(e->tune.log, "din_attention_any_kernel[%lld wg]", (long long)Mv);
+    HIP_TRY(e, launch_din_attention_any(s.T, e->ldT, Mv, e->T, e->D, (int)e->att[0].ln.size(), e->d_att_ln, e->d_att, e->din_maxw,
+                                        s.R, e->ldR, s.stream));
+  } else if (!x.din_fused) {
+    log_launch(e->tune.log, "din_attention_kernel[%lld wg]", (long long)((Mv + 3) / 4));
+    HIP_TRY(e, launch_din_attention(s.T, e->ldT, Mv, e->T, e->D, e->att[0].ln[1], e->d_att_packed, s.R, e->ldR, s.stream));
+  }
+  return run_mlp(e, s, e->top, s.R, e->ldR, Mv, x.out, e->n_out, x.dp);
+}
+
+// NCF: mf = Sum(sls0, sls1); mlp = Concat(sls2, sls3) -> MLP; Concat(mf, mlp_out) -> FC+Relu
+static int32_t mlp_ncf(SetCtx& x) {
+  drs_engine* e = x.e;
+  Slot& s = x.s;
+  const int64_t Mv = x.Mv;
+  const int D = e->D;
+  const int wl = e->top.ln.back();
+  const int64_t ldc = D + wl;
+  HIP_TRY(e, x.join());
+  // one launch when it fits: Sum, MLP branch and predictor of a 16-row slab in the stream kernel
+  const int nt = (int)e->top.layers.size();
+  if (e->mlp_fuse && nt >= 1 && nt <= DRS_MAX_CHAIN && e->fin.layers.size() == 1) {
+    ChainArgs ca, cb;
+    fill_chain(ca, e->top, 0, nt, s.T + 2 * D, e->ldT, Mv, s.H2 + D, ldc);
+    fill_chain(cb, e->fin, 0, 1, s.H2, ldc, Mv, x.out, e->n_out);
+    const SumArgs sum = {s.T, e->ldT, 0, D, D, s.H2, ldc};
+    bool wide = is_wide(e, e->fin, 0);
+    for (int l = 0; l < nt; ++l) wide = wide || is_wide(e, e->top, l);
+    MlpPlan p;
+    if (!wide && plan_chains(ca, &cb, e->tune, x.dp, nullptr, nullptr, &sum, &p)) {
+      HIP_TRY(e, launch_plan(p, e->tune, s.stream));
+      return DRS_OK;
     }
-    log_launch(e->tune.log, "%s<%d,%d%s>[%d wg]", form == 3 ? "dien_rnn_any_kernel" : mfma_form ? "dien_rnn_mfma_kernel" : "dien_rnn_kernel",
-               e->D, Hh, tp.n ? ",top" : "", form == 3 ? c : mfma_form ? (c + 15) / 16 : (c + 3) / 4);
-    HIP_TRY(e, launch_dien_rnn(s.T, e->ldT, q, e->T, e->D, Hh, e->d_att_packed, rw, form, s.R,
-                               e->ldR, s.stream, tp.n ? &tp : nullptr, dp));
-    if (!tp.n && (rc = run_mlp(e, s, e->top, s.R, e->ldR, Mv, out, e->n_out, dp))) return rc;
-  } else if (e->kind == DRS_MODEL_DIN) {
-    // attention units over the pooled rows -> top MLP input R [rows, 4D] -> top MLP (all ReLU)
-    HIP_TRY(e, join());
-    if (e->din_any) {
-      log_launch(e->tune.log, "din_attention_any_kernel[%lld wg]", (long long)Mv);
-      HIP_TRY(e, launch_din_attention_any(s.T, e->ldT, Mv, e->T, e->D, (int)e->att[0].ln.size(), e->d_att_ln, e->d_att, e->din_maxw,
-                                          s.R, e->ldR, s.stream));
-    }
-    if (!din_fused && !e->din_any) log_launch(e->tune.log, "din_attention_kernel[%lld wg]", (long long)((Mv + 3) / 4));
-    if (!din_fused && !e->din_any)
-      HIP_TRY(e, launch_din_attention(s.T, e->ldT, Mv, e->T, e->D, e->att[0].ln[1], e->d_att_packed, s.R, e->ldR, s.stream));
-    if ((rc = run_mlp(e, s, e->top, s.R, e->ldR, Mv, out, e->n_out, dp))) return rc;
-  } else if (e->kind == DRS_MODEL_NCF) {
-    // mf = Sum(sls0, sls1); mlp = Concat(sls2, sls3) -> MLP; Concat(mf, mlp_out) -> FC+Relu
-    const int D = e->D;
-    const int wl = e->top.ln.back();
-    const int64_t ldc = D + wl;
-    HIP_TRY(e, join());
-    // one launch when it fits: Sum, MLP branch and predictor of a 16-row slab in the stream kernel
+  }
+  log_launch(e->tune.log, "add_rows_kernel");
+  HIP_TRY(e, launch_add_rows(s.T, e->ldT, s.T + D, e->ldT, s.H2, ldc, Mv, D, s.stream));
+  int32_t rc;
+  if ((rc = run_mlp(e, s, e->top, s.T + 2 * D, e->ldT, Mv, s.H2 + D, ldc))) return rc;
+  return run_mlp(e, s, e->fin, s.H2, ldc, Mv, x.out, e->n_out, x.dp);
+}
+
+// DLRM, W&D, MT-WnD: bottom MLP (DLRM) beside the gather, interaction, top MLP (and MT-WnD's task heads)
+static int32_t mlp_dense(SetCtx& x) {
+  drs_engine* e = x.e;
+  Slot& s = x.s;
+  const int64_t Mv = x.Mv;
+  float* out = x.out;
+  int32_t rc;
+  MlpPlan p;                   // the fused DLRM launch, or W&D's / MT-WnD's first top layer reading a split row
+  bool split = false;          // (the latter: it reads the dense columns in place)
+  s.split_last = false;
+  const bool dot = e->kind == DRS_MODEL_DLRM && e->interaction_op == DRS_INTERACT_DOT;
+  const float* top_in = dot ? s.R : s.T;
+  const int64_t ld_top = dot ? e->ldR : e->ldT;
+  if (!e->bot.layers.empty()) {
     bool fused = false;
-    const int nt = (int)e->top.layers.size();
-    if (e->mlp_fuse && nt >= 1 && nt <= DRS_MAX_CHAIN && e->fin.layers.size() == 1) {
-      ChainArgs ca, cb;
-      fill_chain(ca, e->top, 0, nt, s.T + 2 * D, e->ldT, Mv, s.H2 + D, ldc);
-      fill_chain(cb, e->fin, 0, 1, s.H2, ldc, Mv, out, e->n_out);
-      SumArgs sum = {s.T, e->ldT, 0, D, D, s.H2, ldc};
-      bool wide = false;
-      for (int l = 0; l < nt; ++l) wide = wide || is_wide(e, e->top, l);
-      if (!wide && !is_wide(e, e->fin, 0) && stream_applicable(ca, cb, e->tune, nullptr, nullptr, &sum)) {
-        HIP_TRY(e, launch_chain2(ca, &cb, e->tune, s.stream, dp, nullptr, nullptr, &sum));
-        fused = true;
-      }
-    }
-    if (!fused) {
-      log_launch(e->tune.log, "add_rows_kernel");
-      HIP_TRY(e, launch_add_rows(s.T, e->ldT, s.T + D, e->ldT, s.H2, ldc, Mv, D, s.stream));
-      if ((rc = run_mlp(e, s, e->top, s.T + 2 * D, e->ldT, Mv, s.H2 + D, ldc))) return rc;
-      if ((rc = run_mlp(e, s, e->fin, s.H2, ldc, Mv, out, e->n_out, dp))) return rc;
-    }
-  } else {
-    bool fused = false;
-    bool split_top = false;      // the first top layer reads the dense columns in place (xs_top)
-    s.split_last = false;
-    XSrc xs_top;
-    memset(&xs_top, 0, sizeof xs_top);
-    if (!e->bot.layers.empty()) {
-      // "mlp_early": a small set of staged queries (gather on the slot's own stream, nothing else of the set there) whose
-      // bottom + top MLP is ONE stream4_kernel launch: the launch goes on a second stream WITHOUT waiting for the gather,
-      // runs its prologue and the bottom chain beside it and polls the slot's flag -- a 32-bit write queued behind the
-      // gather -- before it fetches the pooled rows (mlp.hip, Done::wait_flag).  <= 512 rows: at most 32 workgroups spin.
+    // "mlp_early": a small set of staged queries (gather on the slot's own stream, nothing else of the set there) whose
+    // bottom + top MLP is ONE stream4_kernel launch: the launch goes on a second stream WITHOUT waiting for the gather,
+    // runs its prologue and the bottom chain beside it and polls the slot's flag -- a 32-bit write queued behind the
+    // gather -- before it fetches the pooled rows (mlp.hip, Done::wait_flag).  <= 512 rows: at most 32 workgroups spin.
 #ifdef DRS_LAB
-      bool early = false;
-      if (e->mlp_early && e->shared_stream == 2 && !piped && gstream == s.own_stream && Mv <= 512 && dp && s.early_stream &&
-          e->kind == DRS_MODEL_DLRM) {
-        bool staged = true;
-        for (int i = 0; i < q.n_q; ++i)
-          staged = staged && qb[i] >= e->batches.data() && qb[i] < e->batches.data() + e->batches.size();
-        if (staged) {
-          FusedPlan fp = fused_plan(e, s, Mv, out, &xs, &early);
-          early = early && fp.ok;
-        }
-      }
-      if (early) {
-        HIP_TRY(e, hipStreamWriteValue32(gstream, s.d_gflag, s.seq, 0));
-        done.wait_flag = s.d_gflag; done.wait_val = s.seq;
-        s.stream = s.early_stream;
-        log_launch(e->tune.log, "early");
-      }
-#endif
-      if (fused_applicable(e, s, Mv, &xs)) HIP_TRY(e, join());
-      fused = try_fused_bottom_top(e, s, Mv, out, dp, &xs, &rc);
-      if (rc) return rc;
+    if (e->mlp_early && e->shared_stream == 2 && !x.piped && x.gstream == s.own_stream && Mv <= 512 && x.dp && s.early_stream &&
+        e->kind == DRS_MODEL_DLRM) {
+      bool staged = true;
+      for (int i = 0; i < x.q.n_q; ++i)
+        staged = staged && x.qb[i] >= e->batches.data() && x.qb[i] < e->batches.data() + e->batches.size();
+      x.done.wait_flag = staged ? s.d_gflag : nullptr;
+      x.done.wait_val = staged ? s.seq : 0;
+      fused = staged && fused_plan(e, s, Mv, out, x.dp, &x.xs, &p);   // (a waiting launch is planned only where it can wait)
+      if (!fused) { x.done.wait_flag = nullptr; x.done.wait_val = 0; }
     }
     if (fused) {
-      // nothing else to launch
-    } else if (e->bot.layers.empty()) {
-      // W&D / MT-WnD: Concat(dense, pooled embeddings) feeds the first top layer.  When that layer goes to a GEMM form
-      // that can read a split row ("gemm_split", launch_gemm) it takes the dense columns from the queries' own arrays;
-      // otherwise the dense rows are copied in front of the embeddings first.
-      XSrc xsp = xs;
+      HIP_TRY(e, hipStreamWriteValue32(x.gstream, s.d_gflag, s.seq, 0));
+      s.stream = s.early_stream;
+      log_launch(e->tune.log, "early");
+    }
+#endif
+    fused = fused || fused_plan(e, s, Mv, out, x.dp, &x.xs, &p);
+    if (fused) {
+      HIP_TRY(e, x.join());
+      HIP_TRY(e, launch_plan(p, e->tune, s.stream));
+      return DRS_OK;
+    }
+    if ((rc = run_mlp(e, s, e->bot, nullptr, e->m_den, Mv, s.T, e->ldT, nullptr, &x.xs))) return rc;
+  } else {
+    // W&D / MT-WnD: Concat(dense, pooled embeddings) feeds the first top layer.  When that layer goes to a GEMM form
+    // that can read a split row ("gemm_split", gemm_plan) it takes the dense columns from the queries' own arrays;
+    // otherwise the dense rows are copied in front of the embeddings first.
+    if (e->gemm_split && !e->top.layers.empty() && is_wide(e, e->top, 0)) {
+      XSrc xsp = x.xs;
       xsp.ksplit = e->m_den;
-      if (e->gemm_split && !e->top.layers.empty() && is_wide(e, e->top, 0) &&
-          gemm_split_applicable(s.T, e->ldT, Mv, e->top.ln[0], e->top.layers[0].W, e->top.ln[1], xsp, e->tune)) {
-        xs_top = xsp;
-        split_top = true;
-        s.split_last = true;
-      } else {
-        log_launch(e->tune.log, "copy_rows_multi_kernel");
-        HIP_TRY(e, launch_copy_rows_multi(xs, e->m_den, s.T, e->ldT, s.stream));
-        s.cur = s.stream;          // ("mlp_layout" 1: a wide first layer routed to the gather's stream must wait for this copy)
-      }
-    } else {
-      if ((rc = run_mlp(e, s, e->bot, nullptr, e->m_den, Mv, s.T, e->ldT, nullptr, &xs))) return rc;
+      // (the layer's output as run_mlp would place it: the model's output, or s.H ahead of further layers)
+      const bool one = e->top.layers.size() == 1, mt = e->kind == DRS_MODEL_MTWND;
+      float* y = !one ? s.H : mt ? s.H3 : out;
+      const int64_t ldy = !one ? e->ldH : mt ? e->top.ln.back() : e->n_out;
+      split = plan_layer(top_in, ld_top, Mv, e->top.ln[0], e->top.layers[0].W, e->top.layers[0].b, e->top.ln[1], act_of(e->top, 0),
+                         y, ldy, e->tune, one && !mt ? x.dp : nullptr, &xsp, &p);
     }
-    HIP_TRY(e, join());   // (the bottom MLP above ran beside the gather)
-    const float* top_in = s.T;
-    int64_t ld_top = e->ldT;
-    if (!fused && e->kind == DRS_MODEL_DLRM && e->interaction_op == DRS_INTERACT_DOT) {
-      HIP_TRY(e, rejoin_stream(e, s));
-      log_launch(e->tune.log, "interact_dot_kernel[%lld wg]", (long long)((Mv + 3) / 4));
-      HIP_TRY(e, launch_interact_dot(s.T, e->ldT, Mv, e->T + 1, e->D, e->itself, s.R, e->ldR, s.stream));
-      top_in = s.R;
-      ld_top = e->ldR;
+    s.split_last = split;
+    if (!split) {
+      log_launch(e->tune.log, "copy_rows_multi_kernel");
+      HIP_TRY(e, launch_copy_rows_multi(x.xs, e->m_den, s.T, e->ldT, s.stream));
+      s.cur = s.stream;          // ("mlp_layout" 1: a wide first layer routed to the gather's stream must wait for this copy)
     }
-    if (e->kind == DRS_MODEL_MTWND) {
-      // shared top MLP (all ReLU) -> H3, then every task head reads H3 and writes its block of
-      // the output row; the last head's last launch carries the completion hand-off
-      const int wt = e->top.ln.back(), wo = e->tasks[0].ln.back();
-      if ((rc = run_mlp(e, s, e->top, top_in, ld_top, Mv, s.H3, wt, nullptr, split_top ? &xs_top : nullptr))) return rc;
-      for (size_t k = 0; k < e->tasks.size(); ++k)
-        if ((rc = run_mlp(e, s, e->tasks[k], s.H3, wt, Mv, out + k * wo, e->n_out,
-                          k + 1 == e->tasks.size() ? dp : nullptr)))
-          return rc;
-    } else if (!fused && (rc = run_mlp(e, s, e->top, top_in, ld_top, Mv, out, e->n_out, dp, split_top ? &xs_top : nullptr))) return rc;
   }
+  HIP_TRY(e, x.join());   // (the bottom MLP above ran beside the gather)
+  if (dot) {
+    HIP_TRY(e, rejoin_stream(e, s));
+    log_launch(e->tune.log, "interact_dot_kernel[%lld wg]", (long long)((Mv + 3) / 4));
+    HIP_TRY(e, launch_interact_dot(s.T, e->ldT, Mv, e->T + 1, e->D, e->itself, s.R, e->ldR, s.stream));
+  }
+  const MlpPlan* first = split ? &p : nullptr;
+  if (e->kind != DRS_MODEL_MTWND) return run_mlp(e, s, e->top, top_in, ld_top, Mv, out, e->n_out, x.dp, nullptr, first);
+  // shared top MLP (all ReLU) -> H3, then every task head reads H3 and writes its block of
+  // the output row; the last head's last launch carries the completion hand-off
+  const int wt = e->top.ln.back(), wo = e->tasks[0].ln.back();
+  if ((rc = run_mlp(e, s, e->top, top_in, ld_top, Mv, s.H3, wt, nullptr, nullptr, first))) return rc;
+  for (size_t k = 0; k < e->tasks.size(); ++k)
+    if ((rc = run_mlp(e, s, e->tasks[k], s.H3, wt, Mv, out + k * wo, e->n_out, k + 1 == e->tasks.size() ? x.dp : nullptr)))
+      return rc;
+  return DRS_OK;
+}
+
+// the set's outputs to the host: behind its last launch, back on s.stream
+static int32_t hand_off(SetCtx& x) {
+  drs_engine* e = x.e;
+  Slot& s = x.s;
+  const int64_t Mv = x.Mv;
   HIP_TRY(e, rejoin_stream(e, s));     // ("mlp_layout" 1: the tail below is ordered behind a last launch on the gather's stream)
-  if (evts) {
+  if (e->profiling >= 2) {
     HIP_TRY(e, hipEventRecord(s.ev[2], s.stream));
     s.ev_pending = true;
   }
@@ -518,7 +533,7 @@ int32_t enqueue_forward(drs_engine* e, Slot& s, int n, const Batch* const* bts, 
                               hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(e, hipMemcpyAsync(s.h_out + 1, s.d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
   }
-  if (out_dma) {
+  if (x.out_dma) {
     log_launch(e->tune.log, "out_dma[%lld B]", (long long)(sizeof(float) * (size_t)Mv * e->n_out));
     // ... on the engine's copy stream, behind an event: queued on s.stream itself, the transfer (2 MB = ~40 us of PCIe
     // per MT-WnD set) held up the NEXT set's launches on that MLP stream -- the chip idled 13.5 % of the time
@@ -529,10 +544,48 @@ int32_t enqueue_forward(drs_engine* e, Slot& s, int n, const Batch* const* bts, 
                               hipMemcpyDeviceToHost, e->stream_dma));
     HIP_TRY(e, hipStreamWriteValue32(e->stream_dma, s.dm_out, s.seq, 0));
   }
-  s.on_dma = out_dma;
+  s.on_dma = x.out_dma;
   s.polled = e->zero_copy != 0;
   return DRS_OK;
 }
+
+// Enqueue n >= 1 coalesced queries (query i = first bs[i] samples of *bts[i]) as ONE set of
+// launches on the slot's stream.
+int32_t enqueue_forward(drs_engine* e, Slot& s, int n, const Batch* const* bts, const int32_t* bss) {
+  if (n < 1 || n > DRS_MAX_COALESCE) return fail(e, DRS_ERR_BAD_ARG, "1..%d queries per launch, got %d", DRS_MAX_COALESCE, n);
+  int32_t rc;
+  if ((rc = weights_ready(e)) || (rc = pack_weights(e))) return rc;
+  SetCtx x{e, s};
+  if ((rc = lay_out_set(x, n, bts, bss))) return rc;
+  s.last_n = n;
+  s.last_bs = x.c;
+  s.busy = true;
+  s.polled = false;
+  if (x.c == 0) return DRS_OK;
+  // Pipelined mode, small launch set (a single query: 256 rows = 16 MLP workgroups on a 256-CU
+  // chip): its latency-bound MLP launch goes on the SLOT's own stream, so the MLP launches of
+  // consecutive sets overlap each other instead of queueing on the one shared MLP stream
+  // (one query per launch set: 23 k -> see DESIGN 3.5).  Full sets (8 queries, 128 workgroups)
+  // keep the shared stream: there the extra concurrency only takes CUs from the gather.
+  // Safe: a slot is reused only after its previous job was observed complete on the host.
+  s.stream = job_stream(e, s, x.Mv);
+  s.cur = nullptr;               // (the set's first MLP launch needs no event: join() orders it behind the gather)
+  s.dlog.len = 0; s.dlog.text[0] = 0;
+  // ("dispatch_log" 1: the launch functions note what they choose for this set -- drs_last_dispatch; off by default: four
+  //  to eight vsnprintf per set are ~1 us of the ~11 us a small set costs the host)
+  e->tune.log = e->dispatch_log ? &s.dlog : nullptr;
+  e->tune.xbuf = s.xbuf; e->tune.xcnt = s.xcnt; e->tune.xbuf_rows = s.xrows; e->tune.xbuf_cols = s.xcols;
+  // (both belong to THIS slot: launches made outside this function -- the operator-level entry points -- must not see them)
+  struct TuneScope { Tune& t; ~TuneScope() { t.log = nullptr; t.xbuf = nullptr; t.xcnt = nullptr; } } tune_scope{e->tune};
+  if ((rc = launch_gather(x))) return rc;
+  arm_hand_off(x);
+  if (e->kind == DRS_MODEL_DIEN) rc = mlp_dien(x);
+  else if (e->kind == DRS_MODEL_DIN) rc = mlp_din(x);
+  else if (e->kind == DRS_MODEL_NCF) rc = mlp_ncf(x);
+  else rc = mlp_dense(x);
+  return rc ? rc : hand_off(x);
+}
+
 
 
 int32_t wait_slot(drs_engine* e, Slot& s, float* h_out, int64_t h_cap) {
@@ -789,7 +842,10 @@ int32_t drs_fc(drs_handle e, const float* d_x, int64_t M, int32_t K, const float
   if (!d_x || !d_W || !d_y || M < 0 || K <= 0 || N <= 0 || act < 0 || act > 2) return fail(e, DRS_ERR_BAD_ARG, "bad arguments");
   Slot& s = e->slots[0];
   if (s.busy && (rc = wait_slot(e, s, nullptr))) return rc;
-  HIP_TRY(e, launch_fc(d_x, K, M, K, d_W, d_b, N, act, d_y, N, e->tune, s.stream));
+  MlpPlan p;
+  if (M > 0 && !plan_layer(d_x, K, M, K, d_W, d_b, N, act, d_y, N, e->tune, nullptr, nullptr, &p))
+    return fail(e, DRS_ERR_HIP, "no kernel takes the %dx%d layer", K, N);
+  if (M > 0) HIP_TRY(e, launch_plan(p, e->tune, s.stream));
   HIP_TRY(e, hipStreamSynchronize(s.stream));
   return DRS_OK;
 }

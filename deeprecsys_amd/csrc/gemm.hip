@@ -25,7 +25,7 @@
 #include <type_traits>
 
 #include "drs_internal.h"
-#include "mlp_dev.h"
+#include "mlp_stream.h"
 
 namespace drs {
 namespace {
@@ -672,19 +672,16 @@ hipError_t gemm_set_attrs() {
 
 // tune.mlp_gemm ("mlp_gemm"): wide layers through gemm_kernel; tune.gemm_tile ("mlp_gemm_tile"):
 // force TM*10+TN (22 | 12 | 21 | 11), 0 = by block count
-// false = not applicable (caller falls back to fc_kernel)
-static bool launch_gemm_impl(const float* x, int64_t ldx, int64_t M, int32_t K, const float* W, const float* b,
-                             int32_t N, int32_t act, float* y, int64_t ldy, const Tune& tune,
-                             hipStream_t s, const Done& d, const XSrc& xs, hipError_t* err, bool dry) {
-  *err = hipSuccess;
-  auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-  const float* zero_page = tune.zero;
-  if (!tune.mlp_gemm || !zero_page || (K & 3) || (ldx & 3) || !al(x) || !al(W)) return false;
+// false = no GEMM form for the layer p->a (plan_layer falls back to fc_kernel)
+bool gemm_plan(const Tune& tune, MlpPlan* p) {
+  const ChainArgs& L = p->a;
+  const float* x = L.x;
+  const int64_t ldx = L.ldx, M = L.M;
+  const int K = L.width[0], N = L.width[1];
+  const XSrc& xs = p->xs;
+  auto al = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
+  if (!tune.mlp_gemm || !tune.zero || (K & 3) || (ldx & 3) || !al(x) || !al(L.W[0])) return false;
   for (int i = 0; i < xs.q.n_q; ++i) if (!al(xs.x[i])) return false;
-  GArgs a;
-  memset(&a, 0, sizeof a);
-  a.x = x; a.ldx = ldx; a.M = M; a.W = W; a.b = b; a.y = y; a.ldy = ldy; a.zero = zero_page;
-  a.K = K; a.N = N; a.act = act; a.sc1 = d.counter != nullptr;
   // largest tile that still gives every CU a workgroup (256 CUs); rows are halved first (the
   // weight panel is the shared operand, re-read once per row block)
   auto blocks = [&](int tm, int tn) { return ((M + 32 * tm - 1) / (32 * tm)) * (int64_t)((N + 64 * tn - 1) / (64 * tn)); };
@@ -720,64 +717,54 @@ static bool launch_gemm_impl(const float* x, int64_t ldx, int64_t M, int32_t K, 
              b32(tune.gemm32_small / 10, tune.gemm32_small % 10) >= tune.gemm32_small_blocks) w = tune.gemm32_small;
     if (w) {
       const int wm_ = w / 10, wn_ = w % 10;
-      const dim3 grid((unsigned)((M + 64 * wm_ - 1) / (64 * wm_)), (unsigned)((N + 64 * wn_ - 1) / (64 * wn_)));
-      const size_t lds = sizeof(float) * 2 * (64 * wm_ + 64 * wn_) * G3LD;
       // scalar-base requests when K is whole 32-k chunks and the row offsets fit 32 bits (gemm32_kernel, SPREAD == 2)
       // (offsets + a row's bytes stay below the descriptors' num_records of 0xfffff000)
       const bool sbase = !(K & 31) && ((uint64_t)M * (uint64_t)ldx + (uint64_t)K) * 4u < 0xfffff000ull && ((uint64_t)N + 1) * (uint64_t)K * 4u < 0xfffff000ull;
-      if (xs.ksplit > 0) {
-        // a split input row: the scalar-base forms 2 x 2 and 1 x 2 only (what W&D's and MT-WnD's first layer takes at
-        // full launch sets); the dense arrays' row offsets fit 32 bits like the others
-        const bool ok = sbase && (w == 22 || w == 12) && !(xs.ksplit & 31) && xs.ksplit >= 64 && xs.ksplit < K;
-        if (dry) return ok;
-        if (!ok) { *err = hipErrorInvalidValue; return true; }
-        log_launch(tune.log, "gemm32_kernel<%d,%d,sbase,split%d>[%u x %u wg, %dx%d]", wm_, wn_, xs.ksplit, grid.x, grid.y, K, N);
-        if (w == 22) hipLaunchKernelGGL((gemm32_kernel<2, 2, 2, 0, true>), grid, dim3(256), lds, s, a, d, xs);
-        else hipLaunchKernelGGL((gemm32_kernel<1, 2, 2, 0, true>), grid, dim3(256), lds, s, a, d, xs);
-        *err = hipGetLastError();
-        return true;
-      }
-      if (dry) return false;
-      log_launch(tune.log, "gemm32_kernel<%d,%d%s>[%u x %u wg, %dx%d]", wm_, wn_, sbase ? ",sbase" : "", grid.x, grid.y, K, N);
-#define DRS_G3LAUNCH(WM_, WN_)                                                                              \
-      if (sbase) hipLaunchKernelGGL((gemm32_kernel<WM_, WN_, 2>), grid, dim3(256), lds, s, a, d, xs);          \
-      else hipLaunchKernelGGL((gemm32_kernel<WM_, WN_>), grid, dim3(256), lds, s, a, d, xs);
-      if (w == 22) { DRS_G3LAUNCH(2, 2) } else if (w == 21) { DRS_G3LAUNCH(2, 1) } else if (w == 12) { DRS_G3LAUNCH(1, 2) } else { DRS_G3LAUNCH(1, 1) }
-#undef DRS_G3LAUNCH
-      *err = hipGetLastError();
+      // a split input row: the scalar-base forms 2 x 2 and 1 x 2 only (what W&D's and MT-WnD's first layer takes at
+      // full launch sets); the dense arrays' row offsets fit 32 bits like the others
+      if (xs.ksplit > 0 && !(sbase && (w == 22 || w == 12) && !(xs.ksplit & 31) && xs.ksplit >= 64 && xs.ksplit < K)) return false;
+      p->form = xs.ksplit > 0 ? MlpForm::gemm32_split : sbase ? MlpForm::gemm32_sbase : MlpForm::gemm32;
+      p->tm = wm_; p->tn = wn_;
+      p->grid_x = (unsigned)((M + 64 * wm_ - 1) / (64 * wm_));
+      p->grid_y = (unsigned)((N + 64 * wn_ - 1) / (64 * wn_));
+      p->lds = sizeof(float) * 2 * (64 * wm_ + 64 * wn_) * G3LD;
       return true;
     }
   }
-  if (dry) return false;
-  if (xs.ksplit > 0) { *err = hipErrorInvalidValue; return true; }   // (callers ask gemm_split_applicable first)
-  const dim3 grid((unsigned)((M + 32 * tm - 1) / (32 * tm)), (unsigned)((N + 64 * tn - 1) / (64 * tn)));
-  const size_t lds = sizeof(float) * 2 * (32 * tm + 64 * tn) * GLD;
-  log_launch(tune.log, "gemm_kernel<%d,%d%s>[%u x %u wg, %dx%d]", tm, tn, two_per_cu ? ",2cu" : "", grid.x, grid.y, K, N);
-#define DRS_GLAUNCH(TM_, TN_) \
-  if (tm == TM_ && tn == TN_) hipLaunchKernelGGL((gemm_kernel<TM_, TN_>), grid, dim3(kGThreads), lds, s, a, d, xs);
-  if (two_per_cu) hipLaunchKernelGGL((gemm_kernel<2, 1, 2, 4>), grid, dim3(kGThreads), lds, s, a, d, xs);
-  else { DRS_GLAUNCH(2, 2) DRS_GLAUNCH(1, 2) DRS_GLAUNCH(2, 1) DRS_GLAUNCH(1, 1) }
-#undef DRS_GLAUNCH
-  *err = hipGetLastError();
+  if (xs.ksplit > 0) return false;
+  p->form = two_per_cu ? MlpForm::gemm_2cu : MlpForm::gemm;
+  p->tm = tm; p->tn = tn;
+  p->grid_x = (unsigned)((M + 32 * tm - 1) / (32 * tm));
+  p->grid_y = (unsigned)((N + 64 * tn - 1) / (64 * tn));
+  p->lds = sizeof(float) * 2 * (32 * tm + 64 * tn) * GLD;
   return true;
 }
 
-bool launch_gemm(const float* x, int64_t ldx, int64_t M, int32_t K, const float* W, const float* b,
-                 int32_t N, int32_t act, float* y, int64_t ldy, const Tune& tune,
-                 hipStream_t s, const Done& d, const XSrc& xs, hipError_t* err) {
-  return launch_gemm_impl(x, ldx, M, K, W, b, N, act, y, ldy, tune, s, d, xs, err, false);
-}
-
-// the same decisions without a launch: true when the layer would go to a gemm32_kernel form that reads a split row
-bool gemm_split_applicable(const float* x, int64_t ldx, int64_t M, int32_t K, const float* W, int32_t N, const XSrc& xs,
-                           const Tune& tune) {
-  if (xs.ksplit <= 0 || N < 64 || K < 64) return false;
-  hipError_t err = hipSuccess;
-  Done d;
-  memset(&d, 0, sizeof d);
-  DispatchLog* keep = tune.log;
-  (void)keep;
-  return launch_gemm_impl(x, ldx, M, K, W, nullptr, N, 0, nullptr, 0, tune, nullptr, d, xs, &err, true) && err == hipSuccess;
+hipError_t launch_gemm(const MlpPlan& p, const float* zero, hipStream_t s) {
+  const ChainArgs& L = p.a;
+  GArgs a;
+  memset(&a, 0, sizeof a);
+  a.x = L.x; a.ldx = L.ldx; a.M = L.M; a.W = L.W[0]; a.b = L.b[0]; a.y = L.y; a.ldy = L.ldy; a.zero = zero;
+  a.K = L.width[0]; a.N = L.width[1]; a.act = L.act[0]; a.sc1 = p.done.counter != nullptr;
+  const dim3 grid(p.grid_x, p.grid_y);
+  const Done& d = p.done;
+  const XSrc& xs = p.xs;
+  const size_t lds = p.lds;
+#define DRS_G3LAUNCH(WM_, WN_, ...) \
+  if (p.tm == WM_ && p.tn == WN_) hipLaunchKernelGGL((gemm32_kernel<WM_, WN_, ##__VA_ARGS__>), grid, dim3(256), lds, s, a, d, xs);
+#define DRS_GLAUNCH(TM_, TN_) \
+  if (p.tm == TM_ && p.tn == TN_) hipLaunchKernelGGL((gemm_kernel<TM_, TN_>), grid, dim3(kGThreads), lds, s, a, d, xs);
+  switch (p.form) {
+    case MlpForm::gemm32_split: DRS_G3LAUNCH(2, 2, 2, 0, true) DRS_G3LAUNCH(1, 2, 2, 0, true) break;
+    case MlpForm::gemm32_sbase: DRS_G3LAUNCH(2, 2, 2) DRS_G3LAUNCH(2, 1, 2) DRS_G3LAUNCH(1, 2, 2) DRS_G3LAUNCH(1, 1, 2) break;
+    case MlpForm::gemm32: DRS_G3LAUNCH(2, 2) DRS_G3LAUNCH(2, 1) DRS_G3LAUNCH(1, 2) DRS_G3LAUNCH(1, 1) break;
+    case MlpForm::gemm_2cu: hipLaunchKernelGGL((gemm_kernel<2, 1, 2, 4>), grid, dim3(kGThreads), lds, s, a, d, xs); break;
+    case MlpForm::gemm: DRS_GLAUNCH(2, 2) DRS_GLAUNCH(1, 2) DRS_GLAUNCH(2, 1) DRS_GLAUNCH(1, 1) break;
+    default: return hipErrorInvalidValue;
+  }
+#undef DRS_GLAUNCH
+#undef DRS_G3LAUNCH
+  return hipGetLastError();
 }
 
 }  // namespace drs

@@ -543,43 +543,26 @@ hipError_t mlp_set_attrs() {
   return e;
 }
 
-hipError_t launch_fc(const float* x, int64_t ldx, int64_t M, int32_t K, const float* W,
-                     const float* b, int32_t N, int32_t act, float* y, int64_t ldy,
-                     const Tune& tune, hipStream_t s, const Done* done, const XSrc* xsrc) {
-  if (M <= 0) return hipSuccess;
-  Done d;
-  memset(&d, 0, sizeof d);
-  if (done) d = *done;
-  XSrc xs;
-  memset(&xs, 0, sizeof xs);
-  if (xsrc) xs = *xsrc;
-  if (N >= 64 && K >= 64) {
-    hipError_t ge = hipSuccess;
-    if (launch_gemm(x, ldx, M, K, W, b, N, act, y, ldy, tune, s, d, xs, &ge)) return ge;
-  }
-  int kc = 64, nbuf = 2;
-  if (!pick_kc(K, 0, 2, tune.mlp_kc, &kc, &nbuf)) return hipErrorInvalidValue;
-#ifdef DRS_TIMELINE
-  const size_t lds = stage_bytes(kc, nbuf, 2) + 8192;
-#else
-  const size_t lds = stage_bytes(kc, nbuf, 2);
-#endif
-  dim3 grid((unsigned)((M + 15) / 16), (unsigned)((N + PN - 1) / PN));
+// One layer: a GEMM form (gemm.hip) when the layer has one, else fc_kernel.  A split input row (XSrc::ksplit) is for
+// the GEMM forms only.
+bool plan_layer(const float* x, int64_t ldx, int64_t M, int32_t K, const float* W, const float* b, int32_t N, int32_t act,
+                float* y, int64_t ldy, const Tune& tune, const Done* done, const XSrc* xs, MlpPlan* p) {
+  memset(p, 0, sizeof *p);
+  if (done) p->done = *done;
+  if (xs) p->xs = *xs;
+  ChainArgs& L = p->a;
+  L.x = x; L.ldx = ldx; L.M = M; L.n_layers = 1; L.width[0] = K; L.width[1] = N;
+  L.W[0] = W; L.b[0] = b; L.act[0] = act; L.y = y; L.ldy = ldy;
+  if (N >= 64 && K >= 64 && gemm_plan(tune, p)) return true;
+  if (p->xs.ksplit > 0 || !pick_kc(K, 0, 2, tune.mlp_kc, &p->kc, &p->nbuf)) return false;
+  p->form = MlpForm::fc;
+  p->lds = stage_bytes(p->kc, p->nbuf, 2);
+  p->grid_x = (unsigned)((M + 15) / 16);
+  p->grid_y = (unsigned)((N + PN - 1) / PN);
   bool vec = aligned16(x) && aligned16(W) && (ldx & 3) == 0 && (K & 3) == 0;
-  for (int i = 0; i < xs.q.n_q; ++i) vec = vec && aligned16(xs.x[i]);
-  log_launch(tune.log, "fc_kernel<%s,%d>[%u x %u wg, %dx%d]", vec ? "vec" : "scalar", kc, grid.x, grid.y, K, N);
-#define LAUNCH(KC_)                                                                               \
-  if (kc == KC_) {                                                                                \
-    if (vec)                                                                                      \
-      hipLaunchKernelGGL((fc_kernel<true, KC_>), grid, dim3(kThreads), lds, s, x, ldx, M, K, W,   \
-                         (int64_t)K, b, N, act, y, ldy, nbuf, d, xs);                             \
-    else                                                                                          \
-      hipLaunchKernelGGL((fc_kernel<false, KC_>), grid, dim3(kThreads), lds, s, x, ldx, M, K, W,  \
-                         (int64_t)K, b, N, act, y, ldy, nbuf, d, xs);                             \
-  }
-  DRS_FOR_EACH_KC(LAUNCH)
-#undef LAUNCH
-  return hipGetLastError();
+  for (int i = 0; i < p->xs.q.n_q; ++i) vec = vec && aligned16(p->xs.x[i]);
+  p->vec = vec;
+  return true;
 }
 
 static int chain_slab_ld2(const ChainArgs& a, const ChainArgs* b) {
@@ -612,27 +595,16 @@ static bool chain_plan(const ChainArgs& a, const ChainArgs* b, const Tune& tune,
   return true;
 }
 
-size_t chain_lds_bytes(const ChainArgs& a, const Tune& tune) {
-  int kc, nbuf, lda;
-  size_t lds;
-  return chain_plan(a, nullptr, tune, &kc, &nbuf, &lds, &lda) ? lds : (size_t)1 << 30;
-}
-
-size_t chain2_lds_bytes(const ChainArgs& a, const ChainArgs& b, const Tune& tune) {
-  int kc, nbuf, lda;
-  size_t lds;
-  return chain_plan(a, &b, tune, &kc, &nbuf, &lds, &lda) ? lds : (size_t)1 << 30;
-}
-
 static inline int pad64(int n) { return (n + 63) & ~63; }
 
-// Lay the chain(s) out for stream_kernel.  false = not applicable (caller uses chain_kernel).
-static bool stream_plan(const ChainArgs& a, const ChainArgs* b, const Tune& tune, const XSrc& xs,
-                        bool publish, SArgs* out, size_t* lds_bytes, const DotArgs* dot = nullptr,
-                        const SumArgs* sum = nullptr, bool d_wait = false /* the launch polls Done::wait_flag */,
-                        NSplit* nsp = nullptr) {
-  SArgs& p = *out;
-  if (nsp) memset(nsp, 0, sizeof *nsp);
+// Lay the chain(s) out for a stream kernel (pl: its Done and XSrc set).  false = not applicable.
+static bool stream_plan(const ChainArgs& a, const ChainArgs* b, const Tune& tune, const DotArgs* dot, const SumArgs* sum,
+                        MlpPlan* pl) {
+  SArgs& p = pl->sa;
+  NSplit* nsp = &pl->ns;
+  const XSrc& xs = pl->xs;
+  const bool publish = pl->done.counter != nullptr, d_wait = pl->done.wait_flag != nullptr;   // (d_wait: the launch polls Done::wait_flag)
+  memset(nsp, 0, sizeof *nsp);
   memset(&p, 0, sizeof p);
   const int na = a.n_layers, nb = b ? b->n_layers : 0;
   if (na + nb > DRS_MAX_STREAM_LAYERS) return false;
@@ -732,7 +704,6 @@ static bool stream_plan(const ChainArgs& a, const ChainArgs* b, const Tune& tune
   if (sum && !f3 && pad64(b->width[0]) - sum->cols > ((d_out + 127) / 128) * 128) return false;   // zero pad must fall in an existing pass
   const int nwv = 8;
   const int passw = 16 * nwv;
-  p.packed = f3 ? 5 : pk ? 1 : 0;   // 1: stream_kernel on the packed twins | 5: stream4 (6: its 32-row form, set below)
   const int lpad = f3 ? 8 : 4;      // slab rows: 64 m + 8 floats apart in the b128 form, 64 m + 4 else
   // rows per workgroup: 16, or 32 for stream4_kernel's two-halves form ("mlp_rows32": launches of at
   // least that many rows, no summed input, slabs that still fit LDS)
@@ -790,9 +761,8 @@ static bool stream_plan(const ChainArgs& a, const ChainArgs* b, const Tune& tune
   p.tab_off = off; off += pk ? 4 * DRS_MAX_STREAM_TILES : 0;
   p.lay_off = off; off += pk ? (int)(sizeof(SLayer) / 4) * DRS_MAX_STREAM_LAYERS : 0;
   if (sizeof(float) * (size_t)off > kLdsBudget) return false;
-  *lds_bytes = sizeof(float) * (size_t)off;
+  pl->lds = sizeof(float) * (size_t)off;
   p.lds_floats = off;
-  if (SR == 32) p.packed = 6;
 
   int which = 0, cur_off = x0_off, cur_ld = x0_ld, n = 0, tiles = 0, boff = bias_off;
   auto add = [&](const ChainArgs& c, int l, bool last_of_chain, bool last_of_all) {
@@ -842,8 +812,8 @@ static bool stream_plan(const ChainArgs& a, const ChainArgs* b, const Tune& tune
       if (b && !sum && l == na) p.wait_tile = ti;
       if (split) {
         p.ns = ns;
-        if (nsp) { nsp->t0 = ti; nsp->t1 = ti + nch; nsp->tps = tpp; nsp->n = L.N; nsp->off = L.out_off; nsp->ld = L.out_ld;
-                   nsp->xbuf = tune.xbuf; nsp->xcnt = tune.xcnt; }
+        nsp->t0 = ti; nsp->t1 = ti + nch; nsp->tps = tpp; nsp->n = L.N; nsp->off = L.out_off; nsp->ld = L.out_ld;
+        nsp->xbuf = tune.xbuf; nsp->xcnt = tune.xcnt;
       }
       for (int ps = 0; ps < npass; ++ps)
         for (int c = 0; c < nch; ++c) {
@@ -927,101 +897,113 @@ static bool stream_plan(const ChainArgs& a, const ChainArgs* b, const Tune& tune
     p.inter_tile = 0;
     for (int l = 0; l < na; ++l) p.inter_tile += ((a.width[l + 1] + passw - 1) / passw) * ((a.width[l] + 63) / 64);
   }
+  // the kernel instance: stream4_kernel (the packed step table), else stream_kernel (packed twins | weights staged in LDS)
+  const bool two = tune.mlp_stream_2cu;
+  if (p.ns) pl->form = SR == 32 ? (p.ns == 4 ? MlpForm::stream4_rows32_nsplit4 : MlpForm::stream4_rows32_nsplit2)
+                                : (p.ns == 4 ? MlpForm::stream4_nsplit4 : MlpForm::stream4_nsplit2);
+  else if (f3) pl->form = SR == 32 ? MlpForm::stream4_rows32 : sum ? MlpForm::stream4_sum : two ? MlpForm::stream4_2cu : MlpForm::stream4;
+  else pl->form = !pk ? MlpForm::stream_lds : (two && p.n_table > 0) ? MlpForm::stream_packed_2cu : MlpForm::stream_packed;
+  pl->grid_x = (unsigned)((a.M + SR - 1) / SR) * (p.ns ? (unsigned)p.ns : 1u);
+  pl->grid_y = 1;
   return true;
 }
 
-bool stream_applicable(const ChainArgs& a, const ChainArgs& b, const Tune& tune, const XSrc* xsrc,
-                       const DotArgs* dot, const SumArgs* sum, bool* can_defer) {
-  if (!tune.mlp_stream || !tune.zero) return false;
-  XSrc xs;
-  memset(&xs, 0, sizeof xs);
-  if (xsrc) xs = *xsrc;
-  SArgs sp;
-  size_t lds = 0;
-  const bool ok = stream_plan(a, &b, tune, xs, true, &sp, &lds, dot, sum);
-  // (the 16-row one-workgroup-per-CU form only: the 2cu / 32-row builds have no registers to spare for the late fetch)
-  if (can_defer) *can_defer = ok && sp.packed == 5 && sp.wait_tile > 0 && !(tune.mlp_stream == 4 && tune.mlp_stream_2cu);
-  return ok;
-}
-
-hipError_t launch_chain2(const ChainArgs& a, const ChainArgs* b, const Tune& tune, hipStream_t s,
-                         const Done* done, const XSrc* xsrc, const DotArgs* dot, const SumArgs* sum) {
-  if (a.M <= 0) return hipSuccess;
-  Done d;
-  memset(&d, 0, sizeof d);
-  if (done) d = *done;
-  XSrc xs;
-  memset(&xs, 0, sizeof xs);
-  if (xsrc) xs = *xsrc;
+// One or two chains in one launch: the stream kernel when it takes them, else chain_kernel -- which has neither the
+// interaction nor the summed input nor the late start.  A single chain is planned only where chain_kernel holds it
+// (run_mlp cuts a run of layers shorter until it does).
+bool plan_chains(const ChainArgs& a, const ChainArgs* b, const Tune& tune, const Done* done, const XSrc* xs,
+                 const DotArgs* dot, const SumArgs* sum, MlpPlan* p) {
+  memset(p, 0, sizeof *p);
+  if (done) p->done = *done;
+  if (xs) p->xs = *xs;
   if (a.n_layers < 1 || a.n_layers > DRS_MAX_CHAIN || (b && (b->n_layers < 1 || b->n_layers > DRS_MAX_CHAIN)))
-    return hipErrorInvalidValue;
-  if (tune.mlp_stream && tune.zero) {
-    SArgs sp;
-    size_t slds = 0;
-    NSplit nsp;
-    if (stream_plan(a, b, tune, xs, d.counter != nullptr, &sp, &slds, dot, sum, d.wait_flag != nullptr, &nsp)) {
-#ifdef DRS_TIMELINE
-      slds += 8192;
-#endif
-      const dim3 g3((unsigned)((a.M + 15) / 16));
-      {
-        // which form serves this launch (drs_last_dispatch; DESIGN.md dispatch table)
-        const char* form = sp.ns ? (sp.packed == 6 ? (sp.ns == 4 ? "stream4_kernel<rows32,nsplit4>" : "stream4_kernel<rows32,nsplit2>")
-                                                    : (sp.ns == 4 ? "stream4_kernel<nsplit4>" : "stream4_kernel<nsplit2>")) :
-            sp.packed == 6 ? "stream4_kernel<rows32>" :
-            sp.packed == 5 ? (sp.in[1].col2 >= 0 ? "stream4_kernel<sum>" : (tune.mlp_stream == 4 && tune.mlp_stream_2cu) ? "stream4_kernel<2cu>" : "stream4_kernel") :
-            sp.packed ? ((tune.mlp_stream_2cu && sp.n_table > 0) ? "stream_kernel<packed,2cu>" : "stream_kernel<packed>") : "stream_kernel<lds>";
-        log_launch(tune.log, "%s[%u wg, %d layers%s, %zu B lds]", form, (sp.packed == 6 ? (unsigned)((a.M + 31) / 32) : g3.x) * (sp.ns ? sp.ns : 1),
-                   sp.n_layers, dot ? ", dot" : "", slds);
-      }
-      if (d.wait_flag) {   // early start: only the plain stream4_kernel form has the late fetch (callers ask stream_applicable)
-        const bool plain = sp.packed == 5 && sp.in[1].col2 < 0 && !(tune.mlp_stream == 4 && tune.mlp_stream_2cu) && sp.wait_tile > 0;
-        if (!plain) return hipErrorInvalidValue;
-      }
-      if (sp.packed >= 5) {
-        const bool rows32 = sp.packed == 6;
-        const unsigned grid = (rows32 ? (unsigned)((a.M + 31) / 32) : g3.x) * (sp.ns ? (unsigned)sp.ns : 1u);
-        return launch_stream4(sp.in[1].col2 >= 0, tune.mlp_stream == 4 && tune.mlp_stream_2cu, rows32 ? 32 : 16, sp.ns != 0, grid, slds, s,
-                              sp, d, xs, nsp);
-      }
-      return launch_stream8(!sp.packed ? 0 : (tune.mlp_stream_2cu && sp.n_table > 0) ? 2 : 1, g3.x, slds, s, sp, d, xs);
-    }
-  }
-  if (dot || sum || d.wait_flag) return hipErrorInvalidValue;   // only the stream kernel has these joins (callers check stream_applicable)
-  int kc = 64, nbuf = 2, lda = 0;
-  size_t lds = 0;
-  if (!chain_plan(a, b, tune, &kc, &nbuf, &lds, &lda)) return hipErrorInvalidValue;
-#ifdef DRS_TIMELINE
-  lds += 8192;
-#endif
+    return false;
+  p->a = a;
+  if (b) p->b = *b;
+  const bool chain_ok = !dot && !sum && !p->done.wait_flag && chain_plan(a, b, tune, &p->kc, &p->nbuf, &p->lds, &p->lda);
+  if (!b && !chain_ok) return false;
+  if (tune.mlp_stream && tune.zero && stream_plan(a, b, tune, dot, sum, p))
+    return !p->done.wait_flag || can_defer(*p);
+  if (!chain_ok) return false;
   bool vec = aligned16(a.x) && (a.ldx & 3) == 0;
   for (int l = 0; l < a.n_layers; ++l) vec = vec && aligned16(a.W[l]) && (a.width[l] & 3) == 0;
   if (b) {
     vec = vec && aligned16(b->x) && (b->ldx & 3) == 0;
     for (int l = 0; l < b->n_layers; ++l) vec = vec && aligned16(b->W[l]) && (b->width[l] & 3) == 0;
   }
-  for (int i = 0; i < xs.q.n_q; ++i) vec = vec && aligned16(xs.x[i]);
-  ChainArgs second;
-  memset(&second, 0, sizeof second);
-  if (b) second = *b;
-  const dim3 grid((unsigned)((a.M + 15) / 16));
-  const int sld = chain_slab_ld2(a, b);
-  log_launch(tune.log, "chain_kernel<%s,%d>[%u wg, %d layers]", vec ? "vec" : "scalar", kc, grid.x, a.n_layers + (b ? b->n_layers : 0));
-#define LAUNCH(KC_)                                                                               \
-  if (kc == KC_) {                                                                                \
-    if (vec)                                                                                      \
-      hipLaunchKernelGGL((chain_kernel<true, KC_>), grid, dim3(kThreads), lds, s, a, second, sld, nbuf, lda, d, xs);  \
-    else                                                                                          \
-      hipLaunchKernelGGL((chain_kernel<false, KC_>), grid, dim3(kThreads), lds, s, a, second, sld, nbuf, lda, d, xs); \
-  }
-  DRS_FOR_EACH_KC(LAUNCH)
-#undef LAUNCH
-  return hipGetLastError();
+  for (int i = 0; i < p->xs.q.n_q; ++i) vec = vec && aligned16(p->xs.x[i]);
+  p->form = MlpForm::chain;
+  p->vec = vec;
+  p->sld = chain_slab_ld2(a, b);
+  p->grid_x = (unsigned)((a.M + 15) / 16);
+  p->grid_y = 1;
+  return true;
 }
 
-hipError_t launch_chain(const ChainArgs& a, const Tune& tune, hipStream_t s, const Done* done,
-                        const XSrc* xsrc) {
-  return launch_chain2(a, nullptr, tune, s, done, xsrc, nullptr, nullptr);
+// DRS_TIMELINE builds: the mlp.hip / stream kernels stamp into 8 KB behind the LDS they use
+static size_t launch_lds(const MlpPlan& p) {
+#ifdef DRS_TIMELINE
+  if (p.form < MlpForm::gemm) return p.lds + 8192;
+#endif
+  return p.lds;
+}
+
+hipError_t launch_plan(const MlpPlan& p, const Tune& tune, hipStream_t s) {
+  static const char* const names[] = {
+      "stream4_kernel", "stream4_kernel<sum>", "stream4_kernel<2cu>", "stream4_kernel<rows32>", "stream4_kernel<nsplit2>",
+      "stream4_kernel<nsplit4>", "stream4_kernel<rows32,nsplit2>", "stream4_kernel<rows32,nsplit4>", "stream_kernel<packed>",
+      "stream_kernel<packed,2cu>", "stream_kernel<lds>", "chain_kernel", "fc_kernel", "gemm_kernel", "gemm_kernel",
+      "gemm32_kernel", "gemm32_kernel", "gemm32_kernel"};
+  const char* name = names[(int)p.form];
+  const size_t lds = launch_lds(p);
+  const int K = p.a.width[0], N = p.a.width[1];
+  // which form serves this launch (drs_last_dispatch; DESIGN.md dispatch table)
+  if (p.form < MlpForm::chain)
+    log_launch(tune.log, "%s[%u wg, %d layers%s, %zu B lds]", name, p.grid_x, p.sa.n_layers, p.sa.inter_on ? ", dot" : "", lds);
+  else if (p.form == MlpForm::chain)
+    log_launch(tune.log, "%s<%s,%d>[%u wg, %d layers]", name, p.vec ? "vec" : "scalar", p.kc, p.grid_x, p.a.n_layers + p.b.n_layers);
+  else if (p.form == MlpForm::fc)
+    log_launch(tune.log, "%s<%s,%d>[%u x %u wg, %dx%d]", name, p.vec ? "vec" : "scalar", p.kc, p.grid_x, p.grid_y, K, N);
+  else if (p.form == MlpForm::gemm32_split)
+    log_launch(tune.log, "%s<%d,%d,sbase,split%d>[%u x %u wg, %dx%d]", name, p.tm, p.tn, p.xs.ksplit, p.grid_x, p.grid_y, K, N);
+  else
+    log_launch(tune.log, "%s<%d,%d%s>[%u x %u wg, %dx%d]", name, p.tm, p.tn,
+               p.form == MlpForm::gemm_2cu ? ",2cu" : p.form == MlpForm::gemm32_sbase ? ",sbase" : "", p.grid_x, p.grid_y, K, N);
+  const dim3 grid(p.grid_x, p.grid_y);
+  switch (p.form) {
+    case MlpForm::chain:
+#define LAUNCH(KC_)                                                                                                        \
+  if (p.kc == KC_) {                                                                                                       \
+    if (p.vec)                                                                                                             \
+      hipLaunchKernelGGL((chain_kernel<true, KC_>), grid, dim3(kThreads), lds, s, p.a, p.b, p.sld, p.nbuf, p.lda, p.done, p.xs);  \
+    else                                                                                                                   \
+      hipLaunchKernelGGL((chain_kernel<false, KC_>), grid, dim3(kThreads), lds, s, p.a, p.b, p.sld, p.nbuf, p.lda, p.done, p.xs); \
+  }
+      DRS_FOR_EACH_KC(LAUNCH)
+#undef LAUNCH
+      return hipGetLastError();
+    case MlpForm::fc: {
+      const ChainArgs& L = p.a;
+#define LAUNCH(KC_)                                                                                                        \
+  if (p.kc == KC_) {                                                                                                       \
+    if (p.vec)                                                                                                             \
+      hipLaunchKernelGGL((fc_kernel<true, KC_>), grid, dim3(kThreads), lds, s, L.x, L.ldx, L.M, K, L.W[0], (int64_t)K,      \
+                         L.b[0], N, L.act[0], L.y, L.ldy, p.nbuf, p.done, p.xs);                                            \
+    else                                                                                                                   \
+      hipLaunchKernelGGL((fc_kernel<false, KC_>), grid, dim3(kThreads), lds, s, L.x, L.ldx, L.M, K, L.W[0], (int64_t)K,     \
+                         L.b[0], N, L.act[0], L.y, L.ldy, p.nbuf, p.done, p.xs);                                            \
+  }
+      DRS_FOR_EACH_KC(LAUNCH)
+#undef LAUNCH
+      return hipGetLastError();
+    }
+    case MlpForm::gemm: case MlpForm::gemm_2cu: case MlpForm::gemm32: case MlpForm::gemm32_sbase: case MlpForm::gemm32_split:
+      return launch_gemm(p, tune.zero, s);
+    case MlpForm::stream_packed: case MlpForm::stream_packed_2cu: case MlpForm::stream_lds:
+      return launch_stream8(p, lds, s);
+    default:
+      return launch_stream4(p, lds, s);
+  }
 }
 
 #ifdef DRS_TIMELINE

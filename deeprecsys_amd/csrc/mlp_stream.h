@@ -1,6 +1,6 @@
 // Shared by the MLP translation units (mlp.hip: planning, chain / fc kernels; mlp_stream8.hip: stream_kernel;
-// mlp_stream4.hip: stream4_kernel): the launch description a stream kernel receives, the step-table flags, device
-// helpers, and the launch functions each kernel translation unit exports.
+// mlp_stream4.hip: stream4_kernel; gemm.hip) and the engine: the launch description a stream kernel receives, the plan of
+// one MLP launch, the step-table flags, device helpers, and the launch functions each kernel translation unit exports.
 #pragma once
 #include "drs_internal.h"
 #include "mlp_dev.h"
@@ -106,12 +106,44 @@ static_assert(sizeof(SArgs) + sizeof(Done) + sizeof(XSrc) <= 4096, "kernel argum
 #define S3_OFF_3 "3072"
 #define S3_OFF(Q) S3_OFF_##Q
 
-// mlp_stream8.hip -- form: 0 LDS-staged | 1 packed twins | 2 packed twins, two workgroups per CU
-hipError_t launch_stream8(int form, unsigned grid, size_t lds, hipStream_t s, const SArgs& a, const Done& d, const XSrc& xs);
+// The kernel instance that serves an MLP launch: one value per instance (kc, vec and tile shapes: MlpPlan).
+enum class MlpForm : int32_t {
+  stream4, stream4_sum, stream4_2cu, stream4_rows32, stream4_nsplit2, stream4_nsplit4, stream4_rows32_nsplit2,
+  stream4_rows32_nsplit4,                            // stream4_kernel (mlp_stream4.hip)
+  stream_packed, stream_packed_2cu, stream_lds,      // stream_kernel (mlp_stream8.hip)
+  chain, fc,                                         // chain_kernel, fc_kernel (mlp.hip)
+  gemm, gemm_2cu, gemm32, gemm32_sbase, gemm32_split // gemm_kernel, gemm32_kernel (gemm.hip)
+};
+// One MLP launch, decided once (mlp.hip plan_chains / plan_layer) and run as it stands (launch_plan).
+struct MlpPlan {
+  MlpForm form;
+  unsigned grid_x, grid_y;
+  size_t lds;                   // dynamic LDS bytes (without the DRS_TIMELINE stamps)
+  Done done;
+  XSrc xs;
+  ChainArgs a, b;               // the chain(s) (b.n_layers 0: one); fc / GEMM forms: the layer as a one-layer chain a
+  int kc, nbuf, lda, sld, vec;  // chain_kernel / fc_kernel: K chunk, staging buffers, preloaded input / slab ld, float4 loads
+  int tm, tn;                   // gemm_kernel<tm, tn> | gemm32_kernel<tm, tn>
+  SArgs sa;                     // stream forms
+  NSplit ns;
+};
+// may the launch start before the gather is done (Done::wait_flag)?  Only the 16-row one-workgroup-per-CU stream4_kernel
+// has the late fetch of the second chain's input: the 2cu / 32-row builds have no registers to spare for it
+inline bool can_defer(const MlpPlan& p) { return p.form == MlpForm::stream4 && p.sa.wait_tile > 0; }
+// Planners (false: no form takes the launch), given the launch's Done and XSrc (null: none).  plan_chains: chain a, then
+// b (may be null) on the same rows, with the dot interaction or the summed input between them.  plan_layer: one layer.
+bool plan_chains(const ChainArgs& a, const ChainArgs* b, const Tune& tune, const Done* done, const XSrc* xs,
+                 const DotArgs* dot, const SumArgs* sum, MlpPlan* p);
+bool plan_layer(const float* x, int64_t ldx, int64_t M, int32_t K, const float* W, const float* b, int32_t N, int32_t act,
+                float* y, int64_t ldy, const Tune& tune, const Done* done, const XSrc* xs, MlpPlan* p);
+// the launch of a plan, noted in the dispatch log (tune.log)
+hipError_t launch_plan(const MlpPlan& p, const Tune& tune, hipStream_t s);
+bool gemm_plan(const Tune& tune, MlpPlan* p);   // gemm.hip: the GEMM form of the layer p->a, if it has one
+hipError_t launch_gemm(const MlpPlan& p, const float* zero, hipStream_t s);
+
+hipError_t launch_stream8(const MlpPlan& p, size_t lds, hipStream_t s);
 hipError_t stream8_set_attrs();
-// mlp_stream4.hip -- the six builds: (summed input) | (two per CU) | rows per workgroup 16 / 32 | column split
-hipError_t launch_stream4(bool sum1, bool two, int rows, bool split, unsigned grid, size_t lds, hipStream_t s, const SArgs& a,
-                          const Done& d, const XSrc& xs, const NSplit& ns);
+hipError_t launch_stream4(const MlpPlan& p, size_t lds, hipStream_t s);
 hipError_t stream4_set_attrs();
 #ifdef DRS_TIMELINE
 int tl_fetch_stream8(unsigned long long* out, int cap, int reset);

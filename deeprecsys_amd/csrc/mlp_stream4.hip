@@ -1,6 +1,6 @@
 // stream4_kernel: the four-wave stream kernel of the MLP chains (DLRM, W&D, DIEN, DIN) -- every (layer, pass) ONE hand-laid
 // instruction stream (seg_asm.inc), ring and accumulators in AGPRs; 16 / 32 rows per workgroup, two per CU, column split.
-// Planning and the launch decision: mlp.hip (stream_plan, launch_chain2).
+// Planning and the launch decision: mlp.hip (stream_plan, plan_chains, launch_plan).
 #include "mlp_stream.h"
 
 namespace drs {
@@ -545,15 +545,20 @@ __global__ __launch_bounds__(256, TWO ? 2 : 1) void stream4_kernel(SArgs a, Done
 }
 }  // namespace
 
-hipError_t launch_stream4(bool sum1, bool two, int rows, bool split, unsigned grid, size_t lds, hipStream_t s, const SArgs& a,
-                          const Done& d, const XSrc& xs, const NSplit& ns) {
-  const dim3 g(grid), b(256);
-  if (split && rows == 32) hipLaunchKernelGGL((stream4_kernel<false, false, 2, true>), g, b, lds, s, a, d, xs, ns);
-  else if (split) hipLaunchKernelGGL((stream4_kernel<false, false, 1, true>), g, b, lds, s, a, d, xs, ns);
-  else if (rows == 32) hipLaunchKernelGGL((stream4_kernel<false, false, 2>), g, b, lds, s, a, d, xs, ns);
-  else if (sum1) hipLaunchKernelGGL((stream4_kernel<true, false>), g, b, lds, s, a, d, xs, ns);
-  else if (two) hipLaunchKernelGGL((stream4_kernel<false, true>), g, b, lds, s, a, d, xs, ns);
-  else hipLaunchKernelGGL((stream4_kernel<false, false>), g, b, lds, s, a, d, xs, ns);
+hipError_t launch_stream4(const MlpPlan& p, size_t lds, hipStream_t s) {
+  const dim3 g(p.grid_x), b(256);
+  const SArgs& a = p.sa;
+  switch (p.form) {
+    case MlpForm::stream4_rows32_nsplit2:
+    case MlpForm::stream4_rows32_nsplit4: hipLaunchKernelGGL((stream4_kernel<false, false, 2, true>), g, b, lds, s, a, p.done, p.xs, p.ns); break;
+    case MlpForm::stream4_nsplit2:
+    case MlpForm::stream4_nsplit4: hipLaunchKernelGGL((stream4_kernel<false, false, 1, true>), g, b, lds, s, a, p.done, p.xs, p.ns); break;
+    case MlpForm::stream4_rows32: hipLaunchKernelGGL((stream4_kernel<false, false, 2>), g, b, lds, s, a, p.done, p.xs, p.ns); break;
+    case MlpForm::stream4_sum: hipLaunchKernelGGL((stream4_kernel<true, false>), g, b, lds, s, a, p.done, p.xs, p.ns); break;
+    case MlpForm::stream4_2cu: hipLaunchKernelGGL((stream4_kernel<false, true>), g, b, lds, s, a, p.done, p.xs, p.ns); break;
+    case MlpForm::stream4: hipLaunchKernelGGL((stream4_kernel<false, false>), g, b, lds, s, a, p.done, p.xs, p.ns); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

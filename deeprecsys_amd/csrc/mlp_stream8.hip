@@ -1,5 +1,5 @@
 // stream_kernel: the eight-wave stream kernel of the MLP chains (NCF, MT-WnD; the LDS-staged form in the lab build).
-// Planning and the launch decision: mlp.hip (stream_plan, launch_chain2).
+// Planning and the launch decision: mlp.hip (stream_plan, plan_chains, launch_plan).
 // Stream kernel: the same chain(s) of layers as chain_kernel, organised around ONE flat
 // stream of weight tiles instead of per-layer passes.
 //
@@ -23,7 +23,7 @@
 // so the MFMA body has no selects and no branches.
 // With a DotArgs the DLRM dot interaction runs between the two chains, in LDS (interact()).
 // Requires K % 4 == 0 and 16-B aligned operands on every layer and the slabs to fit in
-// LDS; launch_chain2 falls back to chain_kernel otherwise.
+// LDS; plan_chains falls back to chain_kernel otherwise.
 #include "mlp_stream.h"
 
 namespace drs {
@@ -596,10 +596,12 @@ __global__ __launch_bounds__(64 * NWV, RD3 ? 4 : 1) void stream_kernel(SArgs a, 
 
 }  // namespace
 
-hipError_t launch_stream8(int form, unsigned grid, size_t lds, hipStream_t s, const SArgs& a, const Done& d, const XSrc& xs) {
-  if (form == 2) hipLaunchKernelGGL((stream_kernel<true, 8, true>), dim3(grid), dim3(512), lds, s, a, d, xs);
-  else if (form == 1) hipLaunchKernelGGL((stream_kernel<true, 8>), dim3(grid), dim3(512), lds, s, a, d, xs);
-  else hipLaunchKernelGGL((stream_kernel<false, 8>), dim3(grid), dim3(512), lds, s, a, d, xs);
+hipError_t launch_stream8(const MlpPlan& p, size_t lds, hipStream_t s) {
+  const dim3 g(p.grid_x), b(512);
+  if (p.form == MlpForm::stream_packed_2cu) hipLaunchKernelGGL((stream_kernel<true, 8, true>), g, b, lds, s, p.sa, p.done, p.xs);
+  else if (p.form == MlpForm::stream_packed) hipLaunchKernelGGL((stream_kernel<true, 8>), g, b, lds, s, p.sa, p.done, p.xs);
+  else if (p.form == MlpForm::stream_lds) hipLaunchKernelGGL((stream_kernel<false, 8>), g, b, lds, s, p.sa, p.done, p.xs);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
