@@ -18,6 +18,7 @@ OK, ERR_BAD_ARG, ERR_OOM, ERR_HIP, ERR_INDEX_RANGE, ERR_LENGTHS_SUM, ERR_STATE, 
 MODEL_DLRM, MODEL_WND, MODEL_NCF, MODEL_MTWND, MODEL_DIN, MODEL_DIEN = 0, 1, 2, 3, 4, 5
 INTERACT_DOT, INTERACT_CAT = 0, 1
 TABLE_FP32, TABLE_FP16, TABLE_BF16 = 0, 1, 2   # option "table_dtype": element type of the stored tables
+TABLE_INT8_ROWWISE = 8                          # ... 8-bit codes with an fp32 scale and bias per row (Caffe2's Fused8BitRowwise)
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 MLP_BOT, MLP_TOP, MLP_FINAL = 0, 1, 2
 MLP_TASK0 = 16     # + k: task head k (MT-WnD)

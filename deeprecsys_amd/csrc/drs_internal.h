@@ -27,7 +27,7 @@ struct QTable {
 // models/dlrm_s_caffe2.py:337-342,358-360 with the dense slot in front.
 struct SlsArgs {
   const float* tables;        // base of the table arena
-  const int64_t* tab_off;     // [T] element offset of table t in the arena
+  const int64_t* tab_off;     // [T] offset of table t in the arena, in units of its type (table_unit_bytes)
   const int64_t* tab_rows;    // [T]
   QTable q;                   // which query a bag belongs to
   const int32_t* idx[DRS_MAX_COALESCE];   // per query: [T][idx_stride] int32 indices (Cast op done)
@@ -96,11 +96,21 @@ hipError_t gemm_set_attrs();   // gemm.hip's kernels, on the current device
 
 // launch on `stream`; exact != 0 selects the sequential-order variant.
 // stop_event (optional): recorded by the gather dispatch itself when it completes
-// dtype: element type of the tables a.tables points at (DRS_TABLE_*; a.tab_off counts elements of that type) -- the
-// same launch decisions and grids for every type, rows widened to fp32 before they are summed
+// dtype: element type of the tables a.tables points at (DRS_TABLE_*; a.tab_off counts units of that type:
+// table_unit_bytes) -- the same launch decisions and grids for every type, rows widened to fp32 before they are summed
 hipError_t launch_sls(const SlsArgs& a, int exact, const Tune& tune, hipStream_t stream,
                       hipEvent_t stop_event = nullptr, int dtype = DRS_TABLE_FP32);
-inline int64_t table_elem_bytes(int dtype) { return dtype == DRS_TABLE_FP32 ? 4 : 2; }
+// "table_dtype" layouts.  Stored bytes of one row: D elements of 4 (fp32) or 2 (fp16 / bf16) bytes; int8 rowwise: D codes,
+// zero padding to round_up(D, 8), fp32 scale, fp32 bias (every row 8-byte aligned)
+inline int64_t table_row_stride(int dtype, int64_t D) {
+  return dtype == DRS_TABLE_INT8_ROWWISE ? (D + 7) / 8 * 8 + 8 : D * (dtype == DRS_TABLE_FP32 ? 4 : 2);
+}
+// bytes a gathered row moves (the algorithmic count of drs_gather_bytes and of the launch-form choice): int8 rowwise D + 8
+inline int64_t table_row_bytes(int dtype, int64_t D) {
+  return dtype == DRS_TABLE_INT8_ROWWISE ? D + 8 : table_row_stride(dtype, D);
+}
+// what a table offset (SlsArgs::tab_off, drs_engine::tab_off) counts: elements (4 / 2 bytes), or bytes for int8 rowwise
+inline int64_t table_unit_bytes(int dtype) { return dtype == DRS_TABLE_FP32 ? 4 : dtype == DRS_TABLE_INT8_ROWWISE ? 1 : 2; }
 int64_t sls_grid_blocks(const SlsArgs& a, int exact, const Tune& tune);
 bool sls_flat_applicable(const SlsArgs& a, const Tune& tune);   // would a non-exact launch run the flat variant?
 
@@ -264,10 +274,14 @@ hipError_t probe_latency(const void* base, size_t chunk_bytes, int n_chunks, int
 
 hipError_t launch_fill_uniform(float* W, int64_t n, int32_t t, float lo, float hi, uint64_t seed,
                                hipStream_t stream);
-// the same values rounded to the element type `dtype` (DRS_TABLE_*; fp32: launch_fill_uniform)
-hipError_t launch_fill_uniform_dtype(void* W, int dtype, int64_t n, int32_t t, float lo, float hi, uint64_t seed,
+// the same values of a table of rows x D, stored as `dtype` (DRS_TABLE_*; fp32: launch_fill_uniform; fp16 / bf16: rounded;
+// int8 rowwise: each row quantized)
+hipError_t launch_fill_uniform_dtype(void* W, int dtype, int64_t rows, int D, int32_t t, float lo, float hi, uint64_t seed,
                                      hipStream_t stream);
-// n table elements of type src_dtype -> dst_dtype (rounded to nearest even; widening is exact)
+// n table elements of type src_dtype -> dst_dtype (rounded to nearest even; widening is exact); fp32 / fp16 / bf16 only
 hipError_t launch_convert_table(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, hipStream_t stream);
+// rows x D of one table, into or out of int8 rowwise (exactly one side is DRS_TABLE_INT8_ROWWISE): quantized per row, or
+// each row's value fmaf(scale, q, 0.0f + bias) rounded to dst_dtype
+hipError_t launch_convert_rows(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t rows, int D, hipStream_t stream);
 
 }  // namespace drs

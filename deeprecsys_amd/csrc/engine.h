@@ -3,7 +3,8 @@
 // counterpart, reference accelInferenceEngine.py:18-86).
 //
 // HBM layout (all hipMalloc'ed once in drs_create / first use):
-//   tables   one arena, table t at a 64-element aligned offset, rows*D row-major fp32 (or fp16 / bf16: "table_dtype")
+//   tables   one arena, rows row-major ("table_dtype": rows*D fp32, fp16 or bf16, table t at a 64-element aligned offset;
+//            int8 rowwise: rows of round_up(D, 8) + 8 bytes, table t at a 256-byte aligned offset -- table_layout)
 //   weights  one arena: all biases back to back (layer order, padded to 4 floats), then per
 //            layer W [N, K] dense row-major (as fed by the reference)
 //   batches  per staged batch: dense [max_batch, m_den] f32 | idx [T, cap] i32 |
@@ -172,13 +173,12 @@ struct drs_engine {
   int device = 0;
   int32_t kind = 0, T = 0, D = 0;
   std::vector<int64_t> rows;
-  std::vector<int64_t> tab_off;  // element offsets
+  std::vector<int64_t> tab_off;  // offsets in units of the arena's type (table_unit_bytes), also in d_tab_off: table_layout
   float* tables = nullptr;
   // "table_placement": further copies of the arena in other places of HBM; `tables` is the one in use (see drs_set_option)
   std::vector<Arena> arenas;
   std::vector<hipMemGenericAllocationHandle_t> spacers;   // "table_spacer": device memory taken (never mapped) between placement candidates
   size_t tables_bytes = 0;
-  int64_t table_elems = 0;          // elements of the arena (tables at tab_off, 64-element aligned)
   int table_dtype = DRS_TABLE_FP32; // "table_dtype": element type of the arena (DRS_TABLE_*); sums and outputs stay fp32
   // how the NEXT arena is built (drs_create's first one, "table_placement" -1 candidates)
   int table_alloc = 0;              // 0 hipMalloc | 1 virtual-memory API
@@ -296,6 +296,8 @@ namespace eng {
 
 // engine_create.hip
 void choose_launch_forms(drs_engine* e);
+// where the tables of an arena of type `dtype` start (*off, units of table_unit_bytes) and its bytes
+size_t table_layout(const drs_engine* e, int dtype, std::vector<int64_t>* off);
 int32_t fail(drs_engine* e, int32_t code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
 int32_t set_device(drs_engine* e);
 int32_t alloc_batch(drs_engine* e, Batch& b);

@@ -132,7 +132,7 @@ void drs::eng::choose_launch_forms(drs_engine* e) {
     for (size_t i = 0; i + 1 < mm->ln.size(); ++i) flop += 2.0 * mm->ln[i] * (mm->ln[i + 1] > 0 ? mm->ln[i + 1] : 64);
   // (DIEN: the recurrence, (T - 3) steps of two layers)
   for (const Mlp& rn : e->rnn) flop += 2.0 * (T - 3) * ((double)rn.ln[0] * rn.ln[1] + (double)rn.ln[1] * rn.ln[2]);
-  const double bytes = (double)T * e->max_lookups * D * (double)table_elem_bytes(e->table_dtype);
+  const double bytes = (double)T * e->max_lookups * (double)table_row_bytes(e->table_dtype, D);
   const bool mlp_bound = flop / bytes > 20.0;
   // How many streams, and how many sets in flight the engine asks its feeder for ("preferred_slots"), round 6, one box,
   // (sets in flight, streams) -> k queries/s:  RM3 config 3 (3,3) 34.1 (6,4) 35.0 (4,2) 31.7 | RM3 JSON 67.8 / 70.8 / 70.9 |
@@ -201,6 +201,17 @@ void drs::eng::choose_launch_forms(drs_engine* e) {
   // 8 / 12 / 16 equal; at 2 560-2 640 rows (10 x 256, or 16 queries of the run scripts' ~165 samples) the two kernels are
   // within 1 % of each other either way (profiles/r06_wnd_set_sizes.txt)
   if (e->kind == DRS_MODEL_WND) { e->tune.gemm32_small = 12; e->tune.gemm32_small_blocks = 384; }
+}
+
+size_t drs::eng::table_layout(const drs_engine* e, int dtype, std::vector<int64_t>* off) {
+  int64_t o = 0;
+  off->resize((size_t)e->T);
+  for (int t = 0; t < e->T; ++t) {
+    (*off)[(size_t)t] = o;
+    o += dtype == DRS_TABLE_INT8_ROWWISE ? round_up(e->rows[t] * table_row_stride(dtype, e->D), 256)   // bytes
+                                         : round_up(e->rows[t] * e->D, 64);                             // elements
+  }
+  return (size_t)o * (size_t)table_unit_bytes(dtype);
 }
 extern "C" {
 
@@ -356,12 +367,7 @@ int32_t drs_create(const drs_model_cfg* cfg, int32_t device_id, drs_handle* out)
       e->wall_clock_khz = khz;
   }
   // table arena
-  int64_t off = 0;
-  e->tab_off.resize(T);
-  for (int t = 0; t < T; ++t) {
-    e->tab_off[t] = off;
-    off += round_up(e->rows[t] * D, 64);  // 256-B aligned
-  }
+  const size_t arena_bytes = table_layout(e, DRS_TABLE_FP32, &e->tab_off);
   e->table_set.assign(T, false);
   hipError_t last_rr = hipSuccess;
   auto hip_ok = [&](hipError_t rr) { last_rr = rr; if (rr != hipSuccess) { e->err = hipGetErrorString(rr); return false; } return true; };
@@ -369,8 +375,7 @@ int32_t drs_create(const drs_model_cfg* cfg, int32_t device_id, drs_handle* out)
 #define CREATE_TRY(call) if (!hip_ok(call)) return bail(last_rr == hipErrorOutOfMemory ? DRS_ERR_OOM : DRS_ERR_HIP, (std::string(#call ": ") + e->err).c_str())
   e->tune.device = device_id;
   CREATE_TRY(device_init(device_id, &e->tune.zero));
-  e->table_elems = off;
-  e->tables_bytes = sizeof(float) * (size_t)off;
+  e->tables_bytes = arena_bytes;
   CREATE_TRY(hipMalloc(&e->d_tab_off, sizeof(int64_t) * T));
   CREATE_TRY(hipMalloc(&e->d_tab_rows, sizeof(int64_t) * T));
   CREATE_TRY(hipMalloc(&e->d_op_tab, sizeof(int64_t) * 2));
@@ -576,16 +581,20 @@ int32_t drs_set_table(drs_handle e, int32_t t, const float* h_W, int64_t rows) {
   if (e->table_dtype == DRS_TABLE_FP32) {
     HIP_TRY(e, hipMemcpy(e->tables + e->tab_off[t], h_W, sizeof(float) * (size_t)rows * e->D, hipMemcpyHostToDevice));
   } else {
-    // half tables: the fp32 rows cross the bus through a staging buffer, chunk by chunk, and are rounded on the device
-    const int64_t n = rows * e->D, chunk = std::min<int64_t>(n, (int64_t)16 << 20);
-    char* dst = reinterpret_cast<char*>(e->tables) + e->tab_off[t] * table_elem_bytes(e->table_dtype);
+    // half / int8 tables: the fp32 rows cross the bus through a staging buffer, chunk by chunk (whole rows of up to 16 M
+    // elements), and are rounded or quantized on the device
+    const int dt = e->table_dtype;
+    const int64_t D = e->D, chunk = std::min<int64_t>(rows, std::max<int64_t>(((int64_t)16 << 20) / D, 1));
+    char* dst = reinterpret_cast<char*>(e->tables) + e->tab_off[t] * table_unit_bytes(dt);
     float* stage = nullptr;
-    HIP_TRY(e, hipMalloc(&stage, sizeof(float) * (size_t)chunk));
+    HIP_TRY(e, hipMalloc(&stage, sizeof(float) * (size_t)(chunk * D)));
     hipError_t r = hipSuccess;
-    for (int64_t i = 0; i < n && r == hipSuccess; i += chunk) {
-      const int64_t m = std::min(chunk, n - i);
-      r = hipMemcpy(stage, h_W + i, sizeof(float) * (size_t)m, hipMemcpyHostToDevice);
-      if (r == hipSuccess) r = launch_convert_table(stage, DRS_TABLE_FP32, dst + i * table_elem_bytes(e->table_dtype), e->table_dtype, m, nullptr);
+    for (int64_t i = 0; i < rows && r == hipSuccess; i += chunk) {
+      const int64_t m = std::min(chunk, rows - i);
+      r = hipMemcpy(stage, h_W + i * D, sizeof(float) * (size_t)(m * D), hipMemcpyHostToDevice);
+      if (r == hipSuccess)
+        r = dt == DRS_TABLE_INT8_ROWWISE ? launch_convert_rows(stage, DRS_TABLE_FP32, dst + i * table_row_stride(dt, D), dt, m, (int)D, nullptr)
+                                         : launch_convert_table(stage, DRS_TABLE_FP32, dst + i * table_row_stride(dt, D), dt, m * D, nullptr);
       if (r == hipSuccess) r = hipStreamSynchronize(nullptr);    // (before the next chunk overwrites the staging buffer)
     }
     (void)hipFree(stage);
@@ -600,8 +609,8 @@ int32_t drs_fill_table_uniform(drs_handle e, int32_t t, float lo, float hi, uint
   if (rc) return rc;
   if (t < 0 || t >= e->T) return fail(e, DRS_ERR_BAD_ARG, "bad table id");
   if (e->arenas.size() > 1) { if ((rc = drs_sync(e))) return rc; drop_other_placements(e); }
-  HIP_TRY(e, launch_fill_uniform_dtype(reinterpret_cast<char*>(e->tables) + e->tab_off[t] * table_elem_bytes(e->table_dtype), e->table_dtype,
-                                       e->rows[t] * e->D, t, lo, hi, seed, e->slots[0].stream));
+  HIP_TRY(e, launch_fill_uniform_dtype(reinterpret_cast<char*>(e->tables) + e->tab_off[t] * table_unit_bytes(e->table_dtype), e->table_dtype,
+                                       e->rows[t], e->D, t, lo, hi, seed, e->slots[0].stream));
   HIP_TRY(e, hipStreamSynchronize(e->slots[0].stream));
   e->table_set[t] = true;
   return DRS_OK;

@@ -308,7 +308,7 @@ static int32_t launch_gather(SetCtx& x) {
     int64_t bytes = 0;
     for (int i = 0; i < q.n_q; ++i)
       for (int t = 0; t < e->T; ++t)
-        bytes += (int64_t)x.qb[i]->h_off[(size_t)t * (e->max_batch + 1) + q.bs[i]] * ((int64_t)e->D * table_elem_bytes(e->table_dtype) + 4) +
+        bytes += (int64_t)x.qb[i]->h_off[(size_t)t * (e->max_batch + 1) + q.bs[i]] * (table_row_bytes(e->table_dtype, e->D) + 4) +
                  (int64_t)q.bs[i] * (4 + (int64_t)e->D * 4);
     // (the fused DIN launch writes the 4 D floats of the top MLP's input row per sample instead
     // of T pooled vectors)

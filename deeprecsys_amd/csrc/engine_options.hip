@@ -93,31 +93,51 @@ int32_t set_table_spacer(drs_engine* e, int64_t value) {
 
 int32_t set_table_dtype(drs_engine* e, int64_t value) {
   // The tables in use are converted on the device into a new arena of the new element type (round to nearest even;
-  // widening is exact), which then replaces the old arena and every other placement candidate.  Refused (DRS_ERR_OOM,
-  // nothing changes) when the new arena would not leave 3/4 of the device's memory free -- the rule of "table_placement" -1.
-  // The launch forms that depend on the gathered bytes are chosen again (choose_launch_forms): set this one first.
+  // widening is exact; int8 rowwise: each row quantized, or each row's value written out), which then replaces the old
+  // arena and every other placement candidate.  Refused (DRS_ERR_OOM, nothing changes) when the new arena would not leave
+  // 3/4 of the device's memory free -- the rule of "table_placement" -1.  The launch forms that depend on the gathered
+  // bytes are chosen again (choose_launch_forms): set this one first.
   if (value == e->table_dtype) return DRS_OK;
   if (e->kind == DRS_MODEL_DIN || e->kind == DRS_MODEL_DIEN)
     return fail(e, DRS_ERR_UNSUPPORTED, "table_dtype %lld: DIN and DIEN gather fp32 tables only", (long long)value);
-  const int dt = (int)value;
-  const size_t bytes = (size_t)e->table_elems * (size_t)table_elem_bytes(dt);
+  const int dt = (int)value, from = e->table_dtype;
+  const bool rowwise = dt == DRS_TABLE_INT8_ROWWISE || from == DRS_TABLE_INT8_ROWWISE;
+  // the gather kernels address a row in 32-bit counts of 4-byte pieces: rows * S / 4 < 2^32 per int8 table
+  if (dt == DRS_TABLE_INT8_ROWWISE)
+    for (int t = 0; t < e->T; ++t)
+      if (e->rows[t] * (table_row_stride(dt, e->D) / 4) >= (1ll << 32))
+        return fail(e, DRS_ERR_UNSUPPORTED, "table_dtype 8: table %d (%lld rows of %lld bytes) is too large to address", t,
+                    (long long)e->rows[t], (long long)table_row_stride(dt, e->D));
+  std::vector<int64_t> off;
+  const size_t bytes = table_layout(e, dt, &off);
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 4)
     return fail(e, DRS_ERR_OOM, "table_dtype: no room for the converted tables (%zu bytes)", bytes);
   Arena fresh;
   hipError_t ar = arena_alloc(e, bytes, &fresh);
   if (ar != hipSuccess) { (void)hipGetLastError(); return fail(e, DRS_ERR_OOM, "table_dtype: arena allocation: %s", hipGetErrorString(ar)); }
-  if (launch_convert_table(e->tables, e->table_dtype, fresh.p, dt, e->table_elems, nullptr) != hipSuccess ||
-      hipStreamSynchronize(nullptr) != hipSuccess) {
+  hipError_t r = hipSuccess;
+  if (!rowwise) {    // (fp32 / fp16 / bf16 arenas share their element offsets: one pass over the whole arena)
+    r = launch_convert_table(e->tables, from, fresh.p, dt, (int64_t)(e->tables_bytes / (size_t)table_unit_bytes(from)), nullptr);
+  } else {
+    for (int t = 0; t < e->T && r == hipSuccess; ++t)
+      r = launch_convert_rows(reinterpret_cast<const char*>(e->tables) + e->tab_off[t] * table_unit_bytes(from), from,
+                              reinterpret_cast<char*>(fresh.p) + off[t] * table_unit_bytes(dt), dt, e->rows[t], e->D, nullptr);
+  }
+  if (r == hipSuccess) r = hipStreamSynchronize(nullptr);
+  if (r == hipSuccess && rowwise) r = hipMemcpy(e->d_tab_off, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice);
+  if (r != hipSuccess) {
     arena_free(fresh);
     (void)hipGetLastError();
-    return fail(e, DRS_ERR_HIP, "table_dtype: conversion");
+    if (rowwise) (void)hipMemcpy(e->d_tab_off, e->tab_off.data(), sizeof(int64_t) * e->tab_off.size(), hipMemcpyHostToDevice);
+    return fail(e, DRS_ERR_HIP, "table_dtype: conversion: %s", hipGetErrorString(r));
   }
   for (Arena& a : e->arenas) arena_free(a);
   drop_spacers(e);
   e->arenas.assign(1, fresh);
   e->tables = fresh.p;
   e->tables_bytes = bytes;
+  e->tab_off = off;
   e->table_dtype = dt;
   choose_launch_forms(e);
   apply_stream_mode(e);
@@ -174,7 +194,7 @@ const OptDesc kOptions[] = {
 #else
     OPT("table_alloc", 0, 2, nullptr, 0, table_alloc),
 #endif
-    {"table_dtype", 0, 2, nullptr, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_dtype; }, nullptr, set_table_dtype},
+    {"table_dtype", 0, 8, [](int64_t v) { return v <= DRS_TABLE_BF16 || v == DRS_TABLE_INT8_ROWWISE; }, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_dtype; }, nullptr, set_table_dtype},
     {"table_spacer", 0, kBig, nullptr, 0, [](drs_engine* e) -> int64_t { return (int64_t)e->spacers.size() << 30; }, nullptr, set_table_spacer},
     // what the engine tells its feeder (read only)
     OPT_RO("preferred_coalesce", return e->mlp_streams > 1 ? DRS_MAX_COALESCE : (e->kind == DRS_MODEL_DLRM ? 12 : 8);),
@@ -488,7 +508,7 @@ int32_t drs_gather_bytes(drs_handle e, int32_t batch_id, int32_t bs, int64_t* by
   int64_t total = 0;
   for (int t = 0; t < e->T; ++t) {
     const int64_t n = b.h_off[(size_t)t * (e->max_batch + 1) + bs];
-    total += n * ((int64_t)e->D * table_elem_bytes(e->table_dtype) + 4) + (int64_t)bs * (4 + (int64_t)e->D * 4);
+    total += n * (table_row_bytes(e->table_dtype, e->D) + 4) + (int64_t)bs * (4 + (int64_t)e->D * 4);
   }
   *bytes = total;
   return DRS_OK;

@@ -108,18 +108,34 @@ __device__ __forceinline__ uint2 ld_nt(const uint2* p) {
   return make_uint2(t.x, t.y);
 }
 
-// Row-element policies ("table_dtype"): what a table element is, and the PIECE a lane loads -- 4 elements, 16 B of fp32
-// or 8 B of fp16 / bf16, one load instruction -- widened to 4 fp32 values before they are summed.  Every fp16 / bf16
-// value is an fp32 value, so a half form sums exactly what its fp32 twin sums on the upcast table, in the same order:
-// the same bits.  tag: the dispatch log's dtype token (none for fp32).
-struct F32 {
+__device__ __forceinline__ uint32_t ld_nt(const uint32_t* p) { return __builtin_nontemporal_load(p); }
+
+// Row-element policies ("table_dtype"): what a table element is, the PIECE a lane loads -- 4 elements, 16 B of fp32,
+// 8 B of fp16 / bf16 or 4 B of int8 codes, one load instruction -- and how a piece of a row is added into the fp32
+// accumulator.  Every fp16 / bf16 value is an fp32 value, so a half form sums exactly what its fp32 twin sums on the
+// upcast table, in the same order: the same bits.  tag: the dispatch log's dtype token (none for fp32).
+//   sb: what a lane loads per row besides its piece (int8 rowwise: the row's fp32 scale and bias; nothing otherwise)
+//   pieces_per_row(D): the row stride in pieces; a.tab_off counts `elem`s
+//   add(acc, keep, piece, sb): acc += the row's values (keep == false: the row contributes +0)
+struct NoSb {};
+template <class Self>
+struct PlainRow {
+  static constexpr bool rowwise = false;
+  using sb = NoSb;
+  __host__ __device__ static constexpr uint32_t pieces_per_row(int D) { return (uint32_t)D >> 2; }
+  template <bool NT, class P>
+  __device__ static __forceinline__ NoSb load_sb(const P*, int) { return NoSb{}; }
+  template <class P>
+  __device__ static __forceinline__ void add(float4& acc, bool keep, const P& p, NoSb) { vadd(acc, vsel<4>(keep, Self::up(p))); }
+};
+struct F32 : PlainRow<F32> {
   using elem = float;
   using piece = float4;
   static constexpr const char* tag = "";
   __device__ static __forceinline__ float4 up(const float4& p) { return p; }
   __device__ static __forceinline__ float up1(float x) { return x; }
 };
-struct F16 {
+struct F16 : PlainRow<F16> {
   using elem = uint16_t;
   using piece = uint2;
   static constexpr const char* tag = "f16";
@@ -128,7 +144,7 @@ struct F16 {
     return make_float4(up1((uint16_t)p.x), up1((uint16_t)(p.x >> 16)), up1((uint16_t)p.y), up1((uint16_t)(p.y >> 16)));
   }
 };
-struct BF16 {
+struct BF16 : PlainRow<BF16> {
   using elem = uint16_t;
   using piece = uint2;
   static constexpr const char* tag = "bf16";
@@ -138,9 +154,43 @@ struct BF16 {
                        __uint_as_float(p.y & 0xffff0000u));
   }
 };
+// 8-bit rowwise ("table_dtype" 8, Caffe2's Fused8BitRowwise): a row is D uint8 codes, zero padding to round_up(D, 8)
+// bytes, then the fp32 scale and the fp32 bias (S = round_up(D, 8) + 8 bytes, every row 8-byte aligned).  a.tab_off
+// counts bytes.  A piece is one dword of codes (v_cvt_f32_ubyte0..3); the lanes of a row group load the same 8 bytes of
+// scale and bias beside it.  A row adds acc = fmaf(scale, q, acc + bias) per column: FBGEMM's and Caffe2's order, so the
+// sequential form is bit-identical to embedding_bag_byte_rowwise_offsets.  A masked row adds with scale = bias = 0:
+// acc + 0 + 0 * q == acc (acc is never -0: every step is an fma onto a sum with +0).
+struct I8 {
+  static constexpr bool rowwise = true;
+  using elem = uint8_t;
+  using piece = uint32_t;
+  using sb = float2;
+  static constexpr const char* tag = "i8";
+  __host__ __device__ static constexpr int padded(int D) { return (D + 7) & ~7; }
+  __host__ __device__ static constexpr uint32_t pieces_per_row(int D) { return ((uint32_t)padded(D) >> 2) + 2u; }
+  // code: the lane's piece of the row; delta: bytes from it to the row's scale (round_up(D, 8) - the lane's column)
+  template <bool NT>
+  __device__ static __forceinline__ float2 load_sb(const uint32_t* code, int delta) {
+    const float2* p = reinterpret_cast<const float2*>(reinterpret_cast<const uint8_t*>(code) + delta);
+    if constexpr (NT) return ld_nt(p); else return *p;
+  }
+  __device__ static __forceinline__ float row1(float s, float b, float q, float acc) { return __fmaf_rn(s, q, __fadd_rn(acc, b)); }
+  __device__ static __forceinline__ void add(float4& acc, bool keep, uint32_t p, float2 sb) {
+    const float s = keep ? sb.x : 0.f, b = keep ? sb.y : 0.f;
+    acc.x = row1(s, b, (float)(p & 0xffu), acc.x);
+    acc.y = row1(s, b, (float)((p >> 8) & 0xffu), acc.y);
+    acc.z = row1(s, b, (float)((p >> 16) & 0xffu), acc.z);
+    acc.w = row1(s, b, (float)(p >> 24), acc.w);
+  }
+};
 template <class E>
 __device__ __forceinline__ const typename E::elem* table_base(const float* tables) {
   return reinterpret_cast<const typename E::elem*>(tables);
+}
+// bytes from a lane's piece (at column `col`) to its row's scale: int8 rowwise only
+template <class E>
+__device__ __forceinline__ int sb_delta(int D, int col) {
+  if constexpr (E::rowwise) return E::padded(D) - col; else return 0;
 }
 
 // NT: the hint must be a COMPILE-TIME property of the load: a run-time `nt ? ld_nt(p) : *p` is if-converted
@@ -149,6 +199,7 @@ template <int G, int V, int U, bool EXACT, bool NT = false, class E = F32>
 __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
   using vec = typename Vec<V>::type;
   using piece = typename E::piece;
+  using sbt = typename E::sb;
   static_assert(V == 4, "a lane's piece of a row is 4 elements");
   constexpr int NG = 64 / G;                  // lane groups per wave
   constexpr int BAGS = EXACT ? NG : 1;        // bags per wave
@@ -212,7 +263,10 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
   const typename E::elem* __restrict__ W = table_base<E>(a.tables) + a.tab_off[t] + col;
   const uint32_t rows = (uint32_t)a.tab_rows[t];
   const int64_t D = a.D;
-  const uint32_t Dv = (uint32_t)a.D / V;   // row stride in load-width units: rows * D / V < 2^32 (rows * D < 2^33 is enforced at table creation)
+  // row stride in load-width units: rows * D / V < 2^32 (rows * D < 2^33 is enforced at table creation; int8 rowwise:
+  // rows * S / 4 < 2^32, enforced by the conversion)
+  const uint32_t Dv = E::pieces_per_row(a.D);
+  const int sbd = sb_delta<E>(a.D, col);
 
   int32_t* my_idx = s_idx[EXACT ? g : 0];
   const int me = EXACT ? gl : lane;           // my slot among the owners
@@ -248,7 +302,7 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
     __builtin_amdgcn_wave_barrier();
 
     // U independent, unconditional row loads
-    auto issue = [&](piece (&ring)[U], int pos) {
+    auto issue = [&](piece (&ring)[U], sbt (&rsb)[U], int pos) {
       uint32_t r[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) r[u] = (uint32_t)my_idx[min(pos + u * STEP, last)];
@@ -258,11 +312,12 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
         r[u] = r[u] < rows ? r[u] : 0u;
         const piece* rp_ = reinterpret_cast<const piece*>(W) + (uint64_t)(r[u] * Dv);
         if constexpr (NT) ring[u] = ld_nt(rp_); else ring[u] = *rp_;
+        rsb[u] = E::template load_sb<NT>(rp_, sbd);
       }
     };
-    auto consume = [&](const piece (&ring)[U], int pos) {
+    auto consume = [&](const piece (&ring)[U], const sbt (&rsb)[U], int pos) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) vadd(acc, vsel<V>(pos + u * STEP < n, E::up(ring[u])));
+      for (int u = 0; u < U; ++u) E::add(acc, pos + u * STEP < n, ring[u], rsb[u]);
     };
 
     // software pipeline over two register rings: while ring A (round k) is summed
@@ -271,27 +326,28 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
     // SimplifyCFG from sinking the common tails into a join.
     constexpr int R = U * STEP;
     piece ringA[U], ringB[U];
+    sbt sbA[U], sbB[U];
     int jj = first;                                 // per-lane row position
     int ju = 0;                                     // uniform round position
-    issue(ringA, jj);
+    issue(ringA, sbA, jj);
     for (;;) {
       if (ju + R < n_u) {
-        issue(ringB, jj + R);
+        issue(ringB, sbB, jj + R);
         __builtin_amdgcn_sched_barrier(0);   // loads first, then the sums
-        consume(ringA, jj);
+        consume(ringA, sbA, jj);
         asm volatile("; drs sls: A summed, B in flight" ::: "memory");
       } else {
-        consume(ringA, jj);
+        consume(ringA, sbA, jj);
         asm volatile("; drs sls: A summed, tail" ::: "memory");
         break;
       }
       if (ju + 2 * R < n_u) {
-        issue(ringA, jj + 2 * R);
+        issue(ringA, sbA, jj + 2 * R);
         __builtin_amdgcn_sched_barrier(0);
-        consume(ringB, jj + R);
+        consume(ringB, sbB, jj + R);
         asm volatile("; drs sls: B summed, A in flight" ::: "memory");
       } else {
-        consume(ringB, jj + R);
+        consume(ringB, sbB, jj + R);
         asm volatile("; drs sls: B summed, tail" ::: "memory");
         break;
       }
@@ -330,6 +386,7 @@ template <int G, int BW, class E = F32>
 __global__ __launch_bounds__(64) void sls_one_kernel(SlsArgs a, int tiles) {
   using piece = typename E::piece;
   constexpr int NG = 64 / G, PER = BW / NG;          // bags a lane group copies
+  constexpr uint32_t PR = E::pieces_per_row(4 * G);  // row stride in pieces (G: 4 elements per lane)
   constexpr int M = PER < 8 ? PER : 8;               // ... M at a time
   static_assert(PER >= 1 && PER % M == 0, "whole rounds");
   if (a.ts && threadIdx.x == 0) a.ts[2 * blockIdx.x] = wall_clock64();
@@ -367,9 +424,11 @@ __global__ __launch_bounds__(64) void sls_one_kernel(SlsArgs a, int tiles) {
   const int keep = bad ? 0 : 1;
   const piece* __restrict__ W = reinterpret_cast<const piece*>(table_base<E>(a.tables) + a.tab_off[t]) + gl;
   float* __restrict__ out = a.out + a.col0 + (int64_t)t * (4 * G) + gl * 4;
+  const int sbd = sb_delta<E>(4 * G, gl * 4);
 #pragma unroll
   for (int j0 = 0; j0 < PER; j0 += M) {
     piece v[M];
+    typename E::sb sb[M];
     int vr[M], kp[M];
 #pragma unroll
     for (int j = 0; j < M; ++j) {
@@ -377,14 +436,14 @@ __global__ __launch_bounds__(64) void sls_one_kernel(SlsArgs a, int tiles) {
       const uint32_t rj = (uint32_t)__shfl((int)r, src);
       vr[j] = __shfl(dst, src);
       kp[j] = __shfl(keep, src);
-      v[j] = W[(uint64_t)(rj * (uint32_t)G)];                // rows * D / 4 < 2^32 (enforced at table creation)
+      v[j] = W[(uint64_t)(rj * PR)];                          // rows * D / 4 < 2^32 (enforced at table creation)
+      sb[j] = E::template load_sb<false>(W + (uint64_t)(rj * PR), sbd);
     }
 #pragma unroll
     for (int j = 0; j < M; ++j)
       if (vr[j] >= 0) {
-        const float4 w = E::up(v[j]);
-        const float4 o = make_float4(0.f + (kp[j] ? w.x : 0.f), 0.f + (kp[j] ? w.y : 0.f),
-                                     0.f + (kp[j] ? w.z : 0.f), 0.f + (kp[j] ? w.w : 0.f));
+        float4 o = vzero4();                                  // 0.0f + row: the one-row bag's value
+        E::add(o, kp[j] != 0, v[j], sb[j]);
         *reinterpret_cast<float4*>(out + (int64_t)vr[j] * a.ld_out) = o;
       }
   }
@@ -450,7 +509,8 @@ __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_
     }
   }
   const int R = BPW * L;
-  const uint32_t D4 = (uint32_t)a.D >> 2;          // row stride in 16-byte units: rows * D / 4 < 2^32 (enforced at table creation)
+  const uint32_t D4 = E::pieces_per_row(a.D);      // row stride in pieces: rows * D / 4 < 2^32 (enforced at table creation)
+  const int sbd = sb_delta<E>(a.D, col);
   // table bases and row counts of the wave's BPW tables: scalar loads, issued now and waited
   // for only when the row addresses are formed, i.e. in the shadow of the index loads.  (Left
   // to the compiler they become vector loads -- it cannot prove the arrays are not written by
@@ -513,10 +573,12 @@ __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_
   // ---- phase 3: all row loads, back to back, nothing else in between --------------------------
   __builtin_amdgcn_sched_barrier(0);
   piece v[NL];
+  typename E::sb sb[NL];
 #pragma unroll
   for (int u = 0; u < NL; ++u) {
     if constexpr (NT) v[u] = ld_nt(reinterpret_cast<const piece*>(rp[u]));
     else v[u] = *reinterpret_cast<const piece*>(rp[u]);
+    sb[u] = E::template load_sb<NT>(reinterpret_cast<const piece*>(rp[u]), sbd);
   }
   __builtin_amdgcn_sched_barrier(0);
 
@@ -528,10 +590,10 @@ __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_
   for (int u = 0; u < NL; ++u) {
     const int j = g + NG * u;
     if (BPW == 1) {
-      vadd(acc[0], vsel<4>(j < R, E::up(v[u])));
+      E::add(acc[0], j < R, v[u], sb[u]);
     } else {
 #pragma unroll
-      for (int k = 0; k < BPW; ++k) vadd(acc[k], vsel<4>(j < R && kj[u] == k, E::up(v[u])));
+      for (int k = 0; k < BPW; ++k) E::add(acc[k], j < R && kj[u] == k, v[u], sb[u]);
     }
   }
 #pragma unroll
@@ -600,7 +662,8 @@ __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
     }
   }
   const int R = BPW * L;
-  const uint32_t D4 = (uint32_t)a.D >> 2;          // row stride in 16-byte units: rows * D / 4 < 2^32 (enforced at table creation)
+  const uint32_t D4 = E::pieces_per_row(a.D);      // row stride in pieces: rows * D / 4 < 2^32 (enforced at table creation)
+  const int sbd = sb_delta<E>(a.D, col);
   const elem* Wk[BPW];
   uint32_t rows_k[BPW];
 #pragma unroll
@@ -637,6 +700,7 @@ __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
 
   // every row load of the wave, back to back
   piece v[NL];
+  typename E::sb sb[NL];
 #pragma unroll
   for (int u = 0; u < NL; ++u) {
     const int j = g + NG * u;                      // (j >> 6) == (NG * u) >> 6: compile time
@@ -653,7 +717,11 @@ __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
     } else {
       v[u] = reinterpret_cast<const piece*>(W)[(uint64_t)ro];
     }
+    sb[u] = E::template load_sb<NT>(reinterpret_cast<const piece*>(W) + (uint64_t)ro, sbd);
   }
+  // int8 rowwise: every code and scale / bias load of the wave is issued before the first sum (left to the scheduler,
+  // the sums went in between and a vmcnt(0) drain put the last loads a second round trip behind the first)
+  if constexpr (E::rowwise) __builtin_amdgcn_sched_barrier(0);
 
   float4 acc[BPW];
 #pragma unroll
@@ -662,11 +730,11 @@ __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
   for (int u = 0; u < NL; ++u) {
     const int j = g + NG * u;
     if (BPW == 1) {
-      vadd(acc[0], vsel<4>(j < R, E::up(v[u])));
+      E::add(acc[0], j < R, v[u], sb[u]);
     } else {
       const int kj = bag_of(min(j, R - 1));
 #pragma unroll
-      for (int k = 0; k < BPW; ++k) vadd(acc[k], vsel<4>(j < R && kj == k, E::up(v[u])));
+      for (int k = 0; k < BPW; ++k) E::add(acc[k], j < R && kj == k, v[u], sb[u]);
     }
   }
 #pragma unroll
@@ -734,11 +802,22 @@ __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
       uint32_t r = (uint32_t)ip[j];
       bad |= r >= rows;
       r = r < rows ? r : 0u;
-      const typename E::elem* row = W + (int64_t)r * D;
+      if constexpr (E::rowwise) {
+        // byte loads of the codes; every lane of the wave reads the row's scale and bias
+        const uint8_t* row = W + (int64_t)r * (int64_t)E::pieces_per_row(D) * 4;
+        const float2 sb = *reinterpret_cast<const float2*>(row + E::padded(D));
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int c = c0 + lane + 64 * k;
-        acc[k] += c < D ? E::up1(row[c]) : 0.f;
+        for (int k = 0; k < 4; ++k) {
+          const int c = c0 + lane + 64 * k;
+          if (c < D) acc[k] = E::row1(sb.x, sb.y, (float)row[c], acc[k]);
+        }
+      } else {
+        const typename E::elem* row = W + (int64_t)r * D;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int c = c0 + lane + 64 * k;
+          acc[k] += c < D ? E::up1(row[c]) : 0.f;
+        }
       }
     }
 #pragma unroll
@@ -907,7 +986,7 @@ int64_t sls_grid_blocks(const SlsArgs& a, int exact, const Tune& tune) {
   return (n_bags + bags - 1) / bags;
 }
 
-// the launch for tables of element type E (F32 / F16 / BF16): the same decisions, the same grids for every E
+// the launch for tables of element type E (F32 / F16 / BF16 / I8): the same decisions, the same grids for every E
 template <class E>
 static hipError_t launch_sls_e(const SlsArgs& a, int exact, const Tune& tune, hipStream_t s, hipEvent_t stop) {
   const char* dt = E::tag;                // dispatch log: "" for fp32, else the dtype token
@@ -964,22 +1043,26 @@ static hipError_t launch_sls_e(const SlsArgs& a, int exact, const Tune& tune, hi
 hipError_t launch_sls(const SlsArgs& a, int exact, const Tune& tune, hipStream_t s, hipEvent_t stop, int dtype) {
   if (dtype == DRS_TABLE_FP16) return launch_sls_e<F16>(a, exact, tune, s, stop);
   if (dtype == DRS_TABLE_BF16) return launch_sls_e<BF16>(a, exact, tune, s, stop);
+  if (dtype == DRS_TABLE_INT8_ROWWISE) return launch_sls_e<I8>(a, exact, tune, s, stop);
   return launch_sls_e<F32>(a, exact, tune, s, stop);
 }
 
 // ---------------------------------------------------------------------------
 // device-side table fill, bit-identical to oracle/drs_oracle.c fill_value()
+__device__ __forceinline__ float fill_value(int64_t i, int32_t t, float lo, float span, uint64_t seed) {
+  uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)i + ((uint64_t)(uint32_t)t << 40) + 1ull);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  const float u = (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
+  return __fmaf_rn(u, span, lo);
+}
 __global__ void fill_uniform_kernel(float* W, int64_t n, int32_t t, float lo, float hi,
                                     uint64_t seed) {
   const float span = hi - lo;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)i + ((uint64_t)(uint32_t)t << 40) + 1ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    const float u = (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
-    W[i] = __fmaf_rn(u, span, lo);
+    W[i] = fill_value(i, t, lo, span, seed);
   }
 }
 
@@ -1006,13 +1089,66 @@ __global__ void fill_uniform_round_kernel(void* W, int dt, int64_t n, int32_t t,
   const float span = hi - lo;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)i + ((uint64_t)(uint32_t)t << 40) + 1ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    const float u = (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
-    store_elem(W, dt, i, __fmaf_rn(u, span, lo));
+    store_elem(W, dt, i, fill_value(i, t, lo, span, seed));
   }
+}
+
+// ---------------------------------------------------------------------------
+// "table_dtype" 8, 8-bit rowwise tables (layout: struct I8).  Quantizing a row, FBGEMM's embedding_bag_byte_prepack in
+// IEEE fp32 without contraction: mn = min, mx = max, range = mx - mn, scale = range / 255, bias = mn,
+// inv = 255 / (range + 1e-8), q = rint((x - mn) * inv).  One wave per row, any D; the row is read twice (the second
+// time from the cache).  Rows holding inf or NaN are outside the contract: the clamp keeps every code a byte.
+struct SrcElems {      // row r of a table of element type dt at src (D elements per row)
+  const void* src;
+  int dt;
+  __device__ __forceinline__ float operator()(int64_t r, int D, int c) const { return load_elem(src, dt, r * D + c); }
+};
+struct SrcFill {       // fill_uniform_kernel's values of table t
+  int32_t t;
+  float lo, span;
+  uint64_t seed;
+  __device__ __forceinline__ float operator()(int64_t r, int D, int c) const { return fill_value(r * D + c, t, lo, span, seed); }
+};
+template <class Src>
+__global__ __launch_bounds__(256) void quantize_rows_kernel(Src src, uint8_t* dst, int64_t rows, int D) {
+  const int lane = threadIdx.x & 63;
+  const int D8 = I8::padded(D);
+  const int64_t S = D8 + 8;
+  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
+    float mn = INFINITY, mx = -INFINITY;
+    for (int c = lane; c < D; c += 64) {
+      const float x = src(r, D, c);
+      mn = fminf(mn, x);
+      mx = fmaxf(mx, x);
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+      mn = fminf(mn, __shfl_xor(mn, m));
+      mx = fmaxf(mx, __shfl_xor(mx, m));
+    }
+    const float range = __fsub_rn(mx, mn);
+    const float inv = __fdiv_rn(255.0f, __fadd_rn(range, 1e-8f));
+    uint8_t* row = dst + r * S;
+    for (int c = lane; c < D8; c += 64) {
+      const float q = c < D ? rintf(__fmul_rn(__fsub_rn(src(r, D, c), mn), inv)) : 0.f;
+      row[c] = (uint8_t)fminf(fmaxf(q, 0.f), 255.f);
+    }
+    if (lane == 0) *reinterpret_cast<float2*>(row + D8) = make_float2(__fdiv_rn(range, 255.0f), mn);
+  }
+}
+// int8 rows -> elements of type dt: each row's value fmaf(scale, q, 0.0f + bias) (the one-row bag), rounded to dt
+__global__ __launch_bounds__(256) void dequantize_rows_kernel(const uint8_t* src, void* dst, int dt, int64_t rows, int D) {
+  const int lane = threadIdx.x & 63;
+  const int D8 = I8::padded(D);
+  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
+    const uint8_t* row = src + r * (D8 + 8);
+    const float2 sb = *reinterpret_cast<const float2*>(row + D8);
+    for (int c = lane; c < D; c += 64) store_elem(dst, dt, r * D + c, I8::row1(sb.x, sb.y, (float)row[c], 0.0f));
+  }
+}
+static unsigned row_grid(int64_t rows) {
+  const int64_t want = (rows + 3) / 4;
+  return (unsigned)(want < 16384 ? want : 16384);
 }
 
 #ifdef DRS_LAB   // probes of tools/placement_lab.py (libdrs_hip_lab.so: make lab-lib); not in the product library
@@ -1145,13 +1281,32 @@ hipError_t launch_fill_uniform(float* W, int64_t n, int32_t t, float lo, float h
   return hipGetLastError();
 }
 
-hipError_t launch_fill_uniform_dtype(void* W, int dtype, int64_t n, int32_t t, float lo, float hi, uint64_t seed,
+hipError_t launch_fill_uniform_dtype(void* W, int dtype, int64_t rows, int D, int32_t t, float lo, float hi, uint64_t seed,
                                      hipStream_t s) {
+  const int64_t n = rows * D;
   if (dtype == DRS_TABLE_FP32) return launch_fill_uniform(static_cast<float*>(W), n, t, lo, hi, seed, s);
   if (n <= 0) return hipSuccess;
+  if (dtype == DRS_TABLE_INT8_ROWWISE) {
+    hipLaunchKernelGGL(quantize_rows_kernel<SrcFill>, dim3(row_grid(rows)), dim3(256), 0, s, SrcFill{t, lo, hi - lo, seed},
+                       static_cast<uint8_t*>(W), rows, D);
+    return hipGetLastError();
+  }
   const int64_t want = (n + 255) / 256;
   const unsigned grid = (unsigned)(want < 8192 ? want : 8192);
   hipLaunchKernelGGL(fill_uniform_round_kernel, dim3(grid), dim3(256), 0, s, W, dtype, n, t, lo, hi, seed);
+  return hipGetLastError();
+}
+
+hipError_t launch_convert_rows(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t rows, int D, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  if (dst_dtype == DRS_TABLE_INT8_ROWWISE && src_dtype != DRS_TABLE_INT8_ROWWISE)
+    hipLaunchKernelGGL(quantize_rows_kernel<SrcElems>, dim3(row_grid(rows)), dim3(256), 0, s, SrcElems{src, src_dtype},
+                       static_cast<uint8_t*>(dst), rows, D);
+  else if (src_dtype == DRS_TABLE_INT8_ROWWISE && dst_dtype != DRS_TABLE_INT8_ROWWISE)
+    hipLaunchKernelGGL(dequantize_rows_kernel, dim3(row_grid(rows)), dim3(256), 0, s, static_cast<const uint8_t*>(src), dst,
+                       dst_dtype, rows, D);
+  else
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

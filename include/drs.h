@@ -77,8 +77,10 @@ enum {
 /* feature interaction (models/dlrm_s_caffe2.py:331-365) */
 enum { DRS_INTERACT_DOT = 0, DRS_INTERACT_CAT = 1 };
 
-/* element type of the stored embedding tables (option "table_dtype"); sums and outputs are fp32 in every case */
-enum { DRS_TABLE_FP32 = 0, DRS_TABLE_FP16 = 1, DRS_TABLE_BF16 = 2 };
+/* element type of the stored embedding tables (option "table_dtype"); sums and outputs are fp32 in every case.
+ * DRS_TABLE_INT8_ROWWISE: Caffe2's Fused8BitRowwise -- a row is D uint8 codes, zero padding to a multiple of 8 bytes, an
+ * fp32 scale and an fp32 bias; a row's value is fmaf(scale, q, 0.0f + bias) */
+enum { DRS_TABLE_FP32 = 0, DRS_TABLE_FP16 = 1, DRS_TABLE_BF16 = 2, DRS_TABLE_INT8_ROWWISE = 8 };
 
 /* FC epilogue (Relu / Sigmoid ops, models/dlrm_s_caffe2.py:268-272) */
 enum { DRS_ACT_NONE = 0, DRS_ACT_RELU = 1, DRS_ACT_SIGMOID = 2 };
@@ -276,7 +278,8 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
 /* ---- tuning ------------------------------------------------------------------
  * Integer options of a handle; every key, its values, default and the measurement behind it: docs/OPTIONS.md.
  * Results never depend on an option except where noted (sls_exact: the gather's fp32 summation order; table_dtype:
- * the tables are stored in fp16 / bf16, rounded to nearest even, and still summed in fp32 into fp32 outputs).
+ * the tables are stored in fp16 / bf16, rounded to nearest even, or quantized to 8 bits per value with a per-row scale
+ * and bias, and still summed in fp32 into fp32 outputs).
  * The product library takes the keys below; unknown key or value -> DRS_ERR_BAD_ARG.
  *   gather        "sls_exact" 0|1 (1: sequential order, bit-identical to Caffe2's SparseLengthsSum)
  *                 "sls_flat" 0|1|2   "sls_bpw" 0|1|2|4   "sls_nt" 0|1   "sls_one" 0|1|16|64
@@ -288,8 +291,9 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  *   streams, host "shared_stream" 0|1|2   "mlp_streams" 1..8   "host_threads" -1..64
  *                 "zero_copy_inputs" 1|2|3   "out_dma" bytes   "dispatch_log" 0|1
  *   table arena   "table_placement" -1|-2|k   "table_alloc" 0|1|2   "table_spacer" bytes
- *                 "table_dtype" 0|1|2 (DRS_TABLE_FP32 | DRS_TABLE_FP16 | DRS_TABLE_BF16: converts the arena in use;
- *                 DLRM, W&D, MT-WnD and NCF only)
+ *                 "table_dtype" 0|1|2|8 (DRS_TABLE_FP32 | DRS_TABLE_FP16 | DRS_TABLE_BF16 | DRS_TABLE_INT8_ROWWISE:
+ *                 converts the arena in use; DLRM, W&D, MT-WnD and NCF only.  8: FBGEMM's embedding_bag_byte_prepack
+ *                 quantization, and with sls_exact 1 the pooled sums of embedding_bag_byte_rowwise_offsets, bit for bit)
  *   read only     "preferred_coalesce"  "preferred_slots"  "gather_bound"  "device"
  *                 "table_placements"  "table_bytes"  "table_address"
  * Options belong to the handle: two engines in one process (the mixed-model accelerator engine) keep their own.
