@@ -14,6 +14,7 @@
 
 #include "drs_internal.h"
 #include "mlp_dev.h"
+#include "owner_dev.h"
 #include "rnn_dev.h"
 
 namespace drs {
@@ -118,38 +119,6 @@ __global__ __launch_bounds__(256) void din_attention_kernel(const float* __restr
     out[2 * D + j] = ad[j];
     out[3 * D + j] = e[(int64_t)(Tn - 1) * D + j];
   }
-}
-
-// Who owns valid-sample number `smp` of a coalesced launch set (select chain over <= DRS_MAX_COALESCE entries,
-// wave-uniform: no dynamic indexing of the kernel-argument arrays).
-struct Owner {
-  int b, vrow, ulen;
-  const int32_t* idx;
-  const int32_t* off;
-};
-__device__ __forceinline__ Owner owner_of(const SlsArgs& a, int smp) {
-  Owner o = {smp, a.q.vstart[0] + smp, a.uniform_len[0], a.idx[0], a.off[0]};
-#pragma unroll
-  for (int i = 1; i < 8; ++i) {
-    const bool in = i < a.q.n_q && smp >= a.q.cum[i];
-    o.b = in ? smp - a.q.cum[i] : o.b;
-    o.vrow = in ? a.q.vstart[i] + smp - a.q.cum[i] : o.vrow;
-    o.ulen = in ? a.uniform_len[i] : o.ulen;
-    o.idx = in ? a.idx[i] : o.idx;
-    o.off = in ? a.off[i] : o.off;
-  }
-  if (a.q.n_q > 8) {   // (launch sets of 9 .. 16 queries only: smaller ones never touch the upper half of the argument arrays)
-#pragma unroll
-    for (int i = 8; i < DRS_MAX_COALESCE; ++i) {
-      const bool in = i < a.q.n_q && smp >= a.q.cum[i];
-      o.b = in ? smp - a.q.cum[i] : o.b;
-      o.vrow = in ? a.q.vstart[i] + smp - a.q.cum[i] : o.vrow;
-      o.ulen = in ? a.uniform_len[i] : o.ulen;
-      o.idx = in ? a.idx[i] : o.idx;
-      o.off = in ? a.off[i] : o.off;
-    }
-  }
-  return o;
 }
 
 // FUSED gather + attention units + Concat.  A workgroup of NW waves serves S samples; its waves
@@ -889,23 +858,7 @@ __global__ __launch_bounds__(256) void dien_rnn_kernel(const float* __restrict__
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int smp = blockIdx.x * 4 + wave;
   if (smp >= q.cum[q.n_q]) return;                       // (no workgroup barrier below)
-  int b = smp, bs = q.bs[0], v0 = q.vstart[0];
-#pragma unroll
-  for (int i = 1; i < 8; ++i) {
-    const bool in = i < q.n_q && smp >= q.cum[i];
-    b = in ? smp - q.cum[i] : b;
-    bs = in ? q.bs[i] : bs;
-    v0 = in ? q.vstart[i] : v0;
-  }
-  if (q.n_q > 8) {   // (launch sets of 9 .. 16 queries only: smaller ones never touch the upper half of the argument arrays)
-#pragma unroll
-    for (int i = 8; i < DRS_MAX_COALESCE; ++i) {
-      const bool in = i < q.n_q && smp >= q.cum[i];
-      b = in ? smp - q.cum[i] : b;
-      bs = in ? q.bs[i] : bs;
-      v0 = in ? q.vstart[i] : v0;
-    }
-  }
+  DRS_QOWNER_OF(q, smp, b, bs, v0)
   const int U = Tn - 3;
   const int j = min(lane, H - 1);
   float wi0[D], wg0[H], wi1[H], wg1[H];
@@ -1015,23 +968,7 @@ __global__ __launch_bounds__(64 * (SPLIT ? 2 : 1) * (H / 16)) void dien_rnn_mfma
   const int smp_base = (int)blockIdx.x * 16;
   const int smp = min(smp_base + r, n_smp - 1);
   const bool live = smp_base + r < n_smp;
-  int b = smp, bs = q.bs[0], v0 = q.vstart[0];
-#pragma unroll
-  for (int i = 1; i < 8; ++i) {
-    const bool in = i < q.n_q && smp >= q.cum[i];
-    b = in ? smp - q.cum[i] : b;
-    bs = in ? q.bs[i] : bs;
-    v0 = in ? q.vstart[i] : v0;
-  }
-  if (q.n_q > 8) {   // (launch sets of 9 .. 16 queries only: smaller ones never touch the upper half of the argument arrays)
-#pragma unroll
-    for (int i = 8; i < DRS_MAX_COALESCE; ++i) {
-      const bool in = i < q.n_q && smp >= q.cum[i];
-      b = in ? smp - q.cum[i] : b;
-      bs = in ? q.bs[i] : bs;
-      v0 = in ? q.vstart[i] : v0;
-    }
-  }
+  DRS_QOWNER_OF(q, smp, b, bs, v0)
   const int U = Tn - 3;
   // A operands: lane (r, g) holds W[16 w + r][4 s + g] of every MFMA step s -- the i2h and gates_t
   // rows of the layer(s) this wave runs
@@ -1085,23 +1022,7 @@ __global__ __launch_bounds__(64 * (SPLIT ? 2 : 1) * (H / 16)) void dien_rnn_mfma
       const int f = min(wave * 64 + lane + i * NLD, NF - 1);
       const int ls = f / (D / 4), piece = f - ls * (D / 4);
       const int sm = min(smp_base + ls, n_smp - 1);
-      int bb = sm, bsz = q.bs[0], vv = q.vstart[0];
-#pragma unroll
-      for (int k = 1; k < 8; ++k) {
-        const bool in = k < q.n_q && sm >= q.cum[k];
-        bb = in ? sm - q.cum[k] : bb;
-        bsz = in ? q.bs[k] : bsz;
-        vv = in ? q.vstart[k] : vv;
-      }
-      if (q.n_q > 8) {
-#pragma unroll
-        for (int k = 8; k < DRS_MAX_COALESCE; ++k) {
-          const bool in = k < q.n_q && sm >= q.cum[k];
-          bb = in ? sm - q.cum[k] : bb;
-          bsz = in ? q.bs[k] : bsz;
-          vv = in ? q.vstart[k] : vv;
-        }
-      }
+      DRS_QOWNER_OF(q, sm, bb, bsz, vv)
       xb_[i] = bb; xbs[i] = bsz;
       xsrc[i] = T + (int64_t)vv * ldt + D + 4 * piece;
     }
@@ -1218,21 +1139,7 @@ __global__ __launch_bounds__(64 * (SPLIT ? 2 : 1) * (H / 16)) void dien_rnn_mfma
   for (int i = threadIdx.x; i < 16 * 3 * D; i += NT) {
     const int smp_i = smp_base + i / (3 * D), c = i % (3 * D);
     if (smp_i >= n_smp) break;
-    int bi = smp_i, vi = q.vstart[0];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-      const bool in = k < q.n_q && smp_i >= q.cum[k];
-      bi = in ? smp_i - q.cum[k] : bi;
-      vi = in ? q.vstart[k] : vi;
-    }
-    if (q.n_q > 8) {   // (launch sets of 9 .. 16 queries only: smaller ones never touch the upper half of the argument arrays)
-#pragma unroll
-      for (int k = 8; k < DRS_MAX_COALESCE; ++k) {
-        const bool in = k < q.n_q && smp_i >= q.cum[k];
-        bi = in ? smp_i - q.cum[k] : bi;
-        vi = in ? q.vstart[k] : vi;
-      }
-    }
+    DRS_QOWNER_OF(q, smp_i, bi, bsi, vi)
     const int tab = c < D ? 0 : c < 2 * D ? Tn - 2 : Tn - 1;
     const float ev = T[(int64_t)(vi + bi) * ldt + (int64_t)tab * D + c % D];
     R[(int64_t)(vi + bi) * ldr + H + c] = ev;

@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include "drs_internal.h"
+#include "owner_dev.h"
 #include "rnn_dev.h"
 
 namespace drs {
@@ -81,14 +82,7 @@ __global__ __launch_bounds__(256) void dien_rnn_any_kernel(const float* __restri
   float* s1 = s0 + 2 * (size_t)H;
   const int tid = threadIdx.x;
   const int smp = blockIdx.x;
-  int b = smp, bs = q.bs[0], v0 = q.vstart[0];
-#pragma unroll
-  for (int i = 1; i < DRS_MAX_COALESCE; ++i) {          // whose sample this is (select chain: the argument arrays are never indexed dynamically)
-    const bool in = i < q.n_q && smp >= q.cum[i];
-    b = in ? smp - q.cum[i] : b;
-    bs = in ? q.bs[i] : bs;
-    v0 = in ? q.vstart[i] : v0;
-  }
+  DRS_QOWNER_OF(q, smp, b, bs, v0)                      // whose sample this is
   const int U = Tn - 3;
   const float* wi0 = packed;
   const float* wg0 = wi0 + (int64_t)D * H;

@@ -94,12 +94,28 @@ hipError_t device_init(int device, const float** zero_page);
 hipError_t mlp_set_attrs();    // mlp.hip's kernels, on the current device
 hipError_t gemm_set_attrs();   // gemm.hip's kernels, on the current device
 
-// launch on `stream`; exact != 0 selects the sequential-order variant.
+// One gather launch, decided once by plan_sls and run by launch_sls (sls.hip).  Host-only.
+//   form: any (any row width) | ring (sls_kernel) | one (one lookup per bag) | flat | flatc (fixed-length bags)
+//   exact: the sequential summation order (bit-identical to Caffe2's SparseLengthsSum)
+//   G, NL, BPW, BW, L, nt: the instance -- lanes per row, loads per lane, bags per wave, samples per wave, bag length,
+//   non-temporal row loads; tiles: one-lookup sample tiles per table; grid: workgroups (0: nothing to launch)
+//   dtype: element type of the tables a.tables points at (DRS_TABLE_*; a.tab_off counts units of that type:
+//   table_unit_bytes) -- the same decisions and grids for every type, rows widened to fp32 before they are summed
+enum class SlsForm { any, ring, one, flat, flatc };
+struct SlsPlan {
+  SlsForm form = SlsForm::ring;
+  bool exact = false;
+  int G = 0, NL = 0, BPW = 1, BW = 0, L = 0, nt = 0;
+  int tiles = 0;
+  int64_t grid = 0;
+  int dtype = DRS_TABLE_FP32;
+};
+// exact: the caller asks for the sequential order ("sls_exact", drs_sls's exact_order); short_bags: every bag of the
+// launch is short ("sls_short_bag"), so the sequential order is taken unless the flat variant takes the launch
+SlsPlan plan_sls(const SlsArgs& a, bool exact, bool short_bags, const Tune& tune, int dtype);
 // stop_event (optional): recorded by the gather dispatch itself when it completes
-// dtype: element type of the tables a.tables points at (DRS_TABLE_*; a.tab_off counts units of that type:
-// table_unit_bytes) -- the same launch decisions and grids for every type, rows widened to fp32 before they are summed
-hipError_t launch_sls(const SlsArgs& a, int exact, const Tune& tune, hipStream_t stream,
-                      hipEvent_t stop_event = nullptr, int dtype = DRS_TABLE_FP32);
+hipError_t launch_sls(const SlsArgs& a, const SlsPlan& plan, const Tune& tune, hipStream_t stream,
+                      hipEvent_t stop_event = nullptr);
 // "table_dtype" layouts.  Stored bytes of one row: D elements of 4 (fp32) or 2 (fp16 / bf16) bytes; int8 rowwise: D codes,
 // zero padding to round_up(D, 8), fp32 scale, fp32 bias (every row 8-byte aligned)
 inline int64_t table_row_stride(int dtype, int64_t D) {
@@ -111,8 +127,6 @@ inline int64_t table_row_bytes(int dtype, int64_t D) {
 }
 // what a table offset (SlsArgs::tab_off, drs_engine::tab_off) counts: elements (4 / 2 bytes), or bytes for int8 rowwise
 inline int64_t table_unit_bytes(int dtype) { return dtype == DRS_TABLE_FP32 ? 4 : dtype == DRS_TABLE_INT8_ROWWISE ? 1 : 2; }
-int64_t sls_grid_blocks(const SlsArgs& a, int exact, const Tune& tune);
-bool sls_flat_applicable(const SlsArgs& a, const Tune& tune);   // would a non-exact launch run the flat variant?
 
 // Completion hand-off to the host without a copy or a stream sync: the LAST kernel of a
 // query stores its outputs straight into host-mapped pinned memory and, once every one

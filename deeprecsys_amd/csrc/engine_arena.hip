@@ -100,14 +100,14 @@ hipError_t probe_gather(drs_engine* e, const float* base, size_t bytes, double* 
   a.out = e->probe_out; a.ld_out = D; a.col0 = 0; a.T = 1; a.D = D; a.err = e->probe_err; a.ts = nullptr;
   Tune t = e->tune;
   t.log = nullptr;
-  const int exact = L <= e->sls_short_bag && !sls_flat_applicable(a, t);
+  const SlsPlan plan = plan_sls(a, false, L <= e->sls_short_bag, t, DRS_TABLE_FP32);
   hipEvent_t e0, e1;
   if ((r = hipEventCreate(&e0)) != hipSuccess) return r;
   if ((r = hipEventCreate(&e1)) != hipSuccess) { (void)hipEventDestroy(e0); return r; }
   const int warm = 2, reps = 6;
   for (int i = 0; i < warm + reps && r == hipSuccess; ++i) {
     if (i == warm) r = hipEventRecord(e0, nullptr);
-    if (r == hipSuccess) r = launch_sls(a, exact, t, nullptr);
+    if (r == hipSuccess) r = launch_sls(a, plan, t, nullptr);
   }
   if (r == hipSuccess) r = hipEventRecord(e1, nullptr);
   if (r == hipSuccess) r = hipEventSynchronize(e1);

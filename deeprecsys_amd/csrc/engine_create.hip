@@ -102,7 +102,7 @@ const char* drs_last_error(drs_handle h) { return h ? h->err.c_str() : g_create_
 
 // ---- which launch forms a model's sets take ------------------------------------------------------------
 // Decided ONCE per engine, here and nowhere else, from the model's shape; what each launch then becomes also depends
-// on its row count (mlp.hip stream_plan, gemm.hip launch_gemm, sls.hip flat_plan) -- the resulting table is
+// on its row count (mlp.hip stream_plan, gemm.hip launch_gemm, sls.hip plan_sls) -- the resulting table is
 // DESIGN.md 3 / profiles/r05_dispatch.md, read back through drs_last_dispatch and asserted by
 // test_dispatch_table_of_the_bench_workloads.  The numbers behind every choice are same-session A/Bs
 // (docs/DESIGN_rounds_1-4.md).

@@ -291,17 +291,15 @@ static int32_t launch_gather(SetCtx& x) {
   a.out = s.T; a.ld_out = e->ldT; a.col0 = e->kind == DRS_MODEL_NCF ? 0 : e->w0;
   a.T = e->T; a.D = e->D; a.err = reinterpret_cast<int32_t*>(s.d_err);
   a.ts = prof ? s.d_ts : nullptr;
-  // Bags of a few rows (W&D / NCF: one lookup per table) would leave most of a wave idle in the
-  // wave-per-bag variant: a lane group per bag is both faster there and bit-exact.
+  // short bags (W&D / NCF: one lookup per table) take the sequential lane-group-per-bag form (plan_sls); the queries'
+  // own bag lengths count here, also when "sls_uniform" 0 keeps them from the kernels
   bool short_bags = true;
   for (int i = 0; i < q.n_q; ++i) short_bags = short_bags && x.qb[i]->uniform_len >= 0 && x.qb[i]->uniform_len <= e->sls_short_bag;
-  // ... unless the flat variant takes the launch (fixed-length bags of >= 2 rows: several short
-  // bags share a wave and all of its row loads are in flight at once)
-  const int exact_now = e->sls_exact || (short_bags && !sls_flat_applicable(a, e->tune));
+  const SlsPlan plan = plan_sls(a, e->sls_exact, short_bags, e->tune, e->table_dtype);
   // DIN, default mode: the attention units are fused into the gather launch (din.hip)
   const bool din_fused = x.din_fused = e->kind == DRS_MODEL_DIN && !e->sls_exact && e->din_fused && !e->din_any &&
                                        din_fused_applicable(e->D, e->att[0].ln[1]);
-  s.ts_blocks = prof ? (din_fused ? din_fused_grid(a, e->tune) : sls_grid_blocks(a, exact_now, e->tune)) : 0;
+  s.ts_blocks = prof ? (din_fused ? din_fused_grid(a, e->tune) : plan.grid) : 0;
   if (prof) {
     // algorithmic bytes of THIS launch (rows + int32 indices + length + pooled output
     // per bag), so that achieved GB/s = sum(bytes) / sum(duration) over exactly the timed launches
@@ -321,7 +319,7 @@ static int32_t launch_gather(SetCtx& x) {
   if (din_fused)
     HIP_TRY(e, launch_din_fused(a, e->att[0].ln[1], e->d_att_packed, s.R, e->ldR, e->tune, gstream, piped ? s.ev_sls : nullptr));
   else
-    HIP_TRY(e, launch_sls(a, exact_now, e->tune, gstream, piped ? s.ev_sls : nullptr, e->table_dtype));
+    HIP_TRY(e, launch_sls(a, plan, e->tune, gstream, piped ? s.ev_sls : nullptr));
   if (evts) HIP_TRY(e, hipEventRecord(s.ev[1], gstream));
   x.joined = !piped;
   return DRS_OK;
@@ -824,7 +822,7 @@ int32_t drs_sls(drs_handle e, const float* d_W, int64_t rows, int32_t D, const i
     a.q.n_q = 1; a.q.vstart[1] = (int32_t)n_bags; a.q.cum[1] = (int32_t)n_bags; a.q.bs[0] = (int32_t)n_bags;
     a.idx[0] = d_idx; a.off[0] = d_off; a.uniform_len[0] = -1;
     a.out = d_out; a.ld_out = D; a.col0 = 0; a.T = 1; a.D = D; a.err = d_err; a.ts = nullptr;
-    r = launch_sls(a, exact_order, e->tune, s.stream);
+    r = launch_sls(a, plan_sls(a, exact_order != 0, false, e->tune, DRS_TABLE_FP32), e->tune, s.stream);
   }
   if (r == hipSuccess) r = hipStreamSynchronize(s.stream);
   if (r == hipSuccess) r = hipMemcpy(&h_err, d_err, sizeof(int32_t), hipMemcpyDeviceToHost);

@@ -6,7 +6,7 @@
 // D*4-byte read (128 B at D=32, 256 B at D=64) out of multi-GB tables.
 //
 // Mapping to CDNA4
-//   - a row is read by G = D/V adjacent lanes, V floats (16 B for V=4) per lane:
+//   - a row is read by G = D/4 adjacent lanes, 4 floats (16 B) per lane:
 //     one global_load_dwordx4 per lane, 64/G whole rows per wave-instruction,
 //     each row a single contiguous, aligned segment (tables are 256-B aligned and
 //     D*4 is a multiple of 16).
@@ -37,59 +37,29 @@
 //     raises bit 0 of *err and contributes zero instead of faulting.
 #include <hip/hip_ext.h>
 
+#include <cassert>
+#include <type_traits>
+
 #include "drs_internal.h"
+#include "owner_dev.h"
 
 namespace drs {
 namespace {
 
-template <int V>
-struct Vec;
-template <>
-struct Vec<4> {
-  using type = float4;
-};
-template <>
-struct Vec<2> {
-  using type = float2;
-};
-
 __device__ __forceinline__ float4 vzero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float2 vzero2() { return make_float2(0.f, 0.f); }
-template <int V>
-__device__ __forceinline__ typename Vec<V>::type vzero();
-template <>
-__device__ __forceinline__ float4 vzero<4>() { return vzero4(); }
-template <>
-__device__ __forceinline__ float2 vzero<2>() { return vzero2(); }
-
 __device__ __forceinline__ void vadd(float4& a, const float4& b) {
   a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-}
-__device__ __forceinline__ void vadd(float2& a, const float2& b) {
-  a.x += b.x; a.y += b.y;
 }
 __device__ __forceinline__ float4 vshfl_xor(const float4& a, int m) {
   return make_float4(__shfl_xor(a.x, m), __shfl_xor(a.y, m), __shfl_xor(a.z, m),
                      __shfl_xor(a.w, m));
 }
-__device__ __forceinline__ float2 vshfl_xor(const float2& a, int m) {
-  return make_float2(__shfl_xor(a.x, m), __shfl_xor(a.y, m));
+__device__ __forceinline__ float4 vsel(bool keep, const float4& v) {
+  return make_float4(keep ? v.x : 0.f, keep ? v.y : 0.f, keep ? v.z : 0.f, keep ? v.w : 0.f);
 }
 
 constexpr int kChunk = 128;  // indices staged in LDS per bag per round
 
-template <int V>
-__device__ __forceinline__ typename Vec<V>::type vsel(bool keep, const typename Vec<V>::type& v);
-template <>
-__device__ __forceinline__ float4 vsel<4>(bool keep, const float4& v) {
-  return make_float4(keep ? v.x : 0.f, keep ? v.y : 0.f, keep ? v.z : 0.f, keep ? v.w : 0.f);
-}
-template <>
-__device__ __forceinline__ float2 vsel<2>(bool keep, const float2& v) {
-  return make_float2(keep ? v.x : 0.f, keep ? v.y : 0.f);
-}
-
-// G lanes per row, V floats per lane, U row loads in flight per lane.
 // table rows are read once per launch (~1 % reuse inside a batch): "sls_nt" reads them with the
 // non-temporal hint (same-session A/B on RMC1, two boxes: +1.5 % queries/s)
 typedef float f4v_nt __attribute__((ext_vector_type(4)));
@@ -126,7 +96,7 @@ struct PlainRow {
   template <bool NT, class P>
   __device__ static __forceinline__ NoSb load_sb(const P*, int) { return NoSb{}; }
   template <class P>
-  __device__ static __forceinline__ void add(float4& acc, bool keep, const P& p, NoSb) { vadd(acc, vsel<4>(keep, Self::up(p))); }
+  __device__ static __forceinline__ void add(float4& acc, bool keep, const P& p, NoSb) { vadd(acc, vsel(keep, Self::up(p))); }
 };
 struct F32 : PlainRow<F32> {
   using elem = float;
@@ -195,12 +165,14 @@ __device__ __forceinline__ int sb_delta(int D, int col) {
 
 // NT: the hint must be a COMPILE-TIME property of the load: a run-time `nt ? ld_nt(p) : *p` is if-converted
 // into one plain load (the hint is metadata the merge drops): measured in the ISA, 0 of 5 / 2 of 14 loads kept it.
-template <int G, int V, int U, bool EXACT, bool NT = false, class E = F32>
+// G lanes per row, 4 elements per lane.  U (row loads per register ring and lane) is 4: two rings, so 4..8 loads in
+// flight per lane, the waves per CU provide the rest of the memory-level parallelism.  (8, 16 and 20 were options until
+// round 4 -- measured equal or slower on every shape -- as was a 16-lane x 8-byte form for D == 32.)
+template <int G, bool EXACT, bool NT = false, class E = F32>
 __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
-  using vec = typename Vec<V>::type;
   using piece = typename E::piece;
   using sbt = typename E::sb;
-  static_assert(V == 4, "a lane's piece of a row is 4 elements");
+  constexpr int U = 4;
   constexpr int NG = 64 / G;                  // lane groups per wave
   constexpr int BAGS = EXACT ? NG : 1;        // bags per wave
   constexpr int STEP = EXACT ? 1 : NG;        // row stride between a lane's loads
@@ -214,39 +186,15 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
   const int lane = threadIdx.x;
   const int g = lane / G;
   const int gl = lane - g * G;
-  const int col = min(gl * V, a.D - V);       // clamp idle lanes onto valid columns
-  const bool col_ok = gl * V < a.D;
+  const int col = min(gl * 4, a.D - 4);       // clamp idle lanes onto valid columns
+  const bool col_ok = gl * 4 < a.D;
 
   const int64_t n_bags = (int64_t)a.q.cum[a.q.n_q] * a.T;
   const int64_t bag = (int64_t)blockIdx.x * BAGS + (EXACT ? g : 0);
   const bool bag_ok = bag < n_bags;
   const int smp = bag_ok ? (int)(bag / a.T) : 0;            // valid-sample number over all queries
   const int t = bag_ok ? (int)(bag - (int64_t)smp * a.T) : 0;
-  // which coalesced query owns this sample: select chain over <= DRS_MAX_COALESCE entries (no dynamic
-  // indexing of the kernel-argument arrays)
-  int b = smp, vrow = a.q.vstart[0] + smp, ulen = a.uniform_len[0];
-  const int32_t* qidx = a.idx[0];
-  const int32_t* qoff = a.off[0];
-#pragma unroll
-  for (int i = 1; i < 8; ++i) {
-    const bool in = i < a.q.n_q && smp >= a.q.cum[i];
-    b = in ? smp - a.q.cum[i] : b;
-    vrow = in ? a.q.vstart[i] + smp - a.q.cum[i] : vrow;
-    ulen = in ? a.uniform_len[i] : ulen;
-    qidx = in ? a.idx[i] : qidx;
-    qoff = in ? a.off[i] : qoff;
-  }
-  if (a.q.n_q > 8) {   // (launch sets of 9 .. 16 queries only: smaller ones never touch the upper half of the argument arrays)
-#pragma unroll
-    for (int i = 8; i < DRS_MAX_COALESCE; ++i) {
-      const bool in = i < a.q.n_q && smp >= a.q.cum[i];
-      b = in ? smp - a.q.cum[i] : b;
-      vrow = in ? a.q.vstart[i] + smp - a.q.cum[i] : vrow;
-      ulen = in ? a.uniform_len[i] : ulen;
-      qidx = in ? a.idx[i] : qidx;
-      qoff = in ? a.off[i] : qoff;
-    }
-  }
+  DRS_OWNER_OF(a, smp, b, vrow, ulen, qidx, qoff)   // which coalesced query owns this sample
 
   // fixed-length bags (every shipped reference config: num_indices_per_lookup_fixed) need
   // no offsets: one dependent HBM round trip less before the first row load can issue
@@ -263,7 +211,7 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
   const typename E::elem* __restrict__ W = table_base<E>(a.tables) + a.tab_off[t] + col;
   const uint32_t rows = (uint32_t)a.tab_rows[t];
   const int64_t D = a.D;
-  // row stride in load-width units: rows * D / V < 2^32 (rows * D < 2^33 is enforced at table creation; int8 rowwise:
+  // row stride in load-width units: rows * D / 4 < 2^32 (rows * D < 2^33 is enforced at table creation; int8 rowwise:
   // rows * S / 4 < 2^32, enforced by the conversion)
   const uint32_t Dv = E::pieces_per_row(a.D);
   const int sbd = sb_delta<E>(a.D, col);
@@ -271,7 +219,7 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
   int32_t* my_idx = s_idx[EXACT ? g : 0];
   const int me = EXACT ? gl : lane;           // my slot among the owners
   const int first = EXACT ? 0 : g;            // first row (within a chunk) of this lane
-  vec acc = vzero<V>();
+  float4 acc = vzero4();
   bool bad = false;
 
   // Control flow is kept WAVE-UNIFORM: every lane runs as many rounds as the
@@ -364,7 +312,7 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
   if (bad) atomicOr(a.err, 1);
   if (bag_ok && col_ok && (EXACT || g == 0)) {
     float* o = a.out + (int64_t)vrow * a.ld_out + a.col0 + (int64_t)t * D + col;
-    *reinterpret_cast<vec*>(o) = acc;
+    *reinterpret_cast<float4*>(o) = acc;
   }
   if (a.ts) {
     __builtin_amdgcn_s_waitcnt(0);   // include the output store in the span
@@ -396,24 +344,7 @@ __global__ __launch_bounds__(64) void sls_one_kernel(SlsArgs a, int tiles) {
   const int t = (int)blockIdx.x / tiles;                   // (uniform: table bases and row counts are scalar loads)
   const int smp = ((int)blockIdx.x - t * tiles) * BW + lane;
   const bool ok = lane < BW && smp < n_smp;
-  int b = smp, vrow = a.q.vstart[0] + smp;
-  const int32_t* qidx = a.idx[0];
-#pragma unroll
-  for (int i = 1; i < 8; ++i) {
-    const bool in = i < a.q.n_q && smp >= a.q.cum[i];
-    b = in ? smp - a.q.cum[i] : b;
-    vrow = in ? a.q.vstart[i] + smp - a.q.cum[i] : vrow;
-    qidx = in ? a.idx[i] : qidx;
-  }
-  if (a.q.n_q > 8) {
-#pragma unroll
-    for (int i = 8; i < DRS_MAX_COALESCE; ++i) {
-      const bool in = i < a.q.n_q && smp >= a.q.cum[i];
-      b = in ? smp - a.q.cum[i] : b;
-      vrow = in ? a.q.vstart[i] + smp - a.q.cum[i] : vrow;
-      qidx = in ? a.idx[i] : qidx;
-    }
-  }
+  DRS_OWNER_OF(a, smp, b, vrow, ulen, qidx, qoff)
   const uint32_t rows = (uint32_t)a.tab_rows[t];
   uint32_t r = ok ? (uint32_t)qidx[(int64_t)t * a.idx_stride + b] : 0u;
   const bool bad = r >= rows;                               // Caffe2's ENFORCE: flag it, contribute zero
@@ -456,7 +387,7 @@ __global__ __launch_bounds__(64) void sls_one_kernel(SlsArgs a, int tiles) {
 // ---------------------------------------------------------------------------
 // FLAT variant: fixed-length bags, G lanes per row (16 B per lane), NL loads per lane, BPW
 // bags (same sample, consecutive tables) per wave.  Requires L * BPW <= NL * (64 / G) and
-// T % BPW == 0 (checked by launch_sls).
+// T % BPW == 0 (checked by plan_sls).
 template <int G, int NL, int BPW, bool NT = false, class E = F32>
 __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_order) {
   using elem = typename E::elem;
@@ -490,24 +421,7 @@ __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_
 
   const int smp = (int)(w - tg * n_smp);
   const int t0 = (int)tg * BPW;
-  int b = smp, vrow = a.q.vstart[0] + smp;
-  const int32_t* qidx = a.idx[0];
-#pragma unroll
-  for (int i = 1; i < 8; ++i) {
-    const bool in = i < a.q.n_q && smp >= a.q.cum[i];
-    b = in ? smp - a.q.cum[i] : b;
-    vrow = in ? a.q.vstart[i] + smp - a.q.cum[i] : vrow;
-    qidx = in ? a.idx[i] : qidx;
-  }
-  if (a.q.n_q > 8) {   // (launch sets of 9 .. 16 queries only: smaller ones never touch the upper half of the argument arrays)
-#pragma unroll
-    for (int i = 8; i < DRS_MAX_COALESCE; ++i) {
-      const bool in = i < a.q.n_q && smp >= a.q.cum[i];
-      b = in ? smp - a.q.cum[i] : b;
-      vrow = in ? a.q.vstart[i] + smp - a.q.cum[i] : vrow;
-      qidx = in ? a.idx[i] : qidx;
-    }
-  }
+  DRS_OWNER_OF(a, smp, b, vrow, ulen, qidx, qoff)
   const int R = BPW * L;
   const uint32_t D4 = E::pieces_per_row(a.D);      // row stride in pieces: rows * D / 4 < 2^32 (enforced at table creation)
   const int sbd = sb_delta<E>(a.D, col);
@@ -643,24 +557,7 @@ __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
   const int64_t bag0 = (int64_t)blockIdx.x * BPW;
   const int smp = (int)(bag0 / a.T);
   const int t0 = (int)(bag0 - (int64_t)smp * a.T);
-  int b = smp, vrow = a.q.vstart[0] + smp;
-  const int32_t* qidx = a.idx[0];
-#pragma unroll
-  for (int i = 1; i < 8; ++i) {
-    const bool in = i < a.q.n_q && smp >= a.q.cum[i];
-    b = in ? smp - a.q.cum[i] : b;
-    vrow = in ? a.q.vstart[i] + smp - a.q.cum[i] : vrow;
-    qidx = in ? a.idx[i] : qidx;
-  }
-  if (a.q.n_q > 8) {   // (launch sets of 9 .. 16 queries only: smaller ones never touch the upper half of the argument arrays)
-#pragma unroll
-    for (int i = 8; i < DRS_MAX_COALESCE; ++i) {
-      const bool in = i < a.q.n_q && smp >= a.q.cum[i];
-      b = in ? smp - a.q.cum[i] : b;
-      vrow = in ? a.q.vstart[i] + smp - a.q.cum[i] : vrow;
-      qidx = in ? a.idx[i] : qidx;
-    }
-  }
+  DRS_OWNER_OF(a, smp, b, vrow, ulen, qidx, qoff)
   const int R = BPW * L;
   const uint32_t D4 = E::pieces_per_row(a.D);      // row stride in pieces: rows * D / 4 < 2^32 (enforced at table creation)
   const int sbd = sb_delta<E>(a.D, col);
@@ -769,18 +666,7 @@ __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
   const int64_t bag = blockIdx.x;
   const int smp = (int)(bag / a.T);
   const int t = (int)(bag - (int64_t)smp * a.T);
-  int b = smp, vrow = a.q.vstart[0] + smp, ulen = a.uniform_len[0];
-  const int32_t* qidx = a.idx[0];
-  const int32_t* qoff = a.off[0];
-#pragma unroll
-  for (int i = 1; i < DRS_MAX_COALESCE; ++i) {
-    const bool in = i < a.q.n_q && smp >= a.q.cum[i];
-    b = in ? smp - a.q.cum[i] : b;
-    vrow = in ? a.q.vstart[i] + smp - a.q.cum[i] : vrow;
-    ulen = in ? a.uniform_len[i] : ulen;
-    qidx = in ? a.idx[i] : qidx;
-    qoff = in ? a.off[i] : qoff;
-  }
+  DRS_OWNER_OF(a, smp, b, vrow, ulen, qidx, qoff)
   int beg, end;
   if (ulen >= 0) {
     beg = b * ulen;
@@ -845,54 +731,103 @@ void launch_k(K kernel, dim3 grid, hipStream_t s, hipEvent_t stop, const X&... x
   launch_kb(kernel, grid, dim3(64), s, stop, x...);
 }
 
-template <int G, int V, int U, class E>
-hipError_t launch_variant(const SlsArgs& a, int exact, int nt, hipStream_t s, hipEvent_t stop) {
-  const int64_t n_bags = (int64_t)a.q.cum[a.q.n_q] * a.T;
-  if (n_bags == 0) return hipSuccess;
-  if (exact) {
-    constexpr int BAGS = 64 / G;
-    const unsigned grid = (unsigned)((n_bags + BAGS - 1) / BAGS);
-    launch_k(sls_kernel<G, V, U, true, false, E>, grid, s, stop, a);
-  } else if (nt) {
-    launch_k(sls_kernel<G, V, U, false, true, E>, (unsigned)n_bags, s, stop, a);
-  } else {
-    launch_k(sls_kernel<G, V, U, false, false, E>, (unsigned)n_bags, s, stop, a);
-  }
-  return hipGetLastError();
-}
-
-// U (row loads per register ring and lane) is 4: two rings, so 4..8 loads in flight per lane, the waves per
-// CU provide the rest of the memory-level parallelism.  (8, 16 and 20 were options until round 4 -- measured
-// equal or slower on every shape -- as was a 16-lane x 8-byte form for D == 32.)
-template <int G, int V, class E>
-hipError_t launch_u(const SlsArgs& a, int exact, int nt, hipStream_t s, hipEvent_t stop) {
-  return launch_variant<G, V, 4, E>(a, exact, nt, s, stop);
+// f(std::integral_constant<int, V>) for the V of the list equal to v: one instance parameter of a launch, from its
+// run-time value.  plan_sls only plans instantiated values: one it does not is a planner bug, caught here
+template <int V, int... Vs, class F>
+void with_int(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) {
+    assert(v == V && "plan_sls planned a gather instance that is not instantiated");
+    f(std::integral_constant<int, V>{});
+  } else if (v == V) f(std::integral_constant<int, V>{});
+  else with_int<Vs...>(v, f);
 }
 
 int lanes_per_row(int D) { return D <= 8 ? 2 : D <= 16 ? 4 : D <= 32 ? 8 : D <= 64 ? 16 : D <= 128 ? 32 : 64; }
 
-// Shape of the flat variant for this launch, or ok == false: every coalesced query must have
-// the same fixed bag length L >= 1, G must be one of the instantiated widths, BPW must divide T
-// (a wave's bags belong to one sample) and BPW * L rows must fit NL loads per lane.
-struct FlatPlan {
-  bool ok = false;
-  int G = 0, NL = 0, BPW = 1, L = 0, xcd = 1, coal = 0, nt = 0;
-  unsigned grid = 0;
-};
-FlatPlan flat_plan(const SlsArgs& a, const Tune& tune) {
-  FlatPlan p;
-  if (!tune.sls_flat || a.q.n_q < 1) return p;
-  const int L = a.uniform_len[0];
-  for (int i = 1; i < a.q.n_q; ++i) if (a.uniform_len[i] != L) return p;
-  if (L < 2) return p;                      // L == 1 is a copy: the lane-group-per-bag kernel
-  const int G = lanes_per_row(a.D);
-  if (G != 8 && G != 16 && G != 32) return p;
-  const int NG = 64 / G;
+// the launch for tables of element type E (F32 / F16 / BF16 / I8): the plan's dispatch-log line, then its instance
+template <class E>
+hipError_t launch_sls_e(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hipStream_t s, hipEvent_t stop) {
+  const char* dt = E::tag;                // dispatch log: "" for fp32, else the dtype token
+  const char* sep = *dt ? "," : "";
+  const long long wg = (long long)p.grid;
+  if (!wg && (p.form == SlsForm::any || p.form == SlsForm::one)) return hipSuccess;   // (an empty launch of these is not logged)
+  switch (p.form) {
+    case SlsForm::any:
+      log_launch(tune.log, "sls_any_kernel%s%s%s[%lld wg, D=%d]", *dt ? "<" : "", dt, *dt ? ">" : "", wg, a.D);
+      break;
+    case SlsForm::flat:
+    case SlsForm::flatc:
+      log_launch(tune.log, "%s<%d,%d%s%s%s%s>[%lld wg, L=%d]", p.form == SlsForm::flatc ? "sls_flatc_kernel" : "sls_flat_kernel",
+                 p.G, p.NL, p.form == SlsForm::flatc ? "" : (p.BPW == 4 ? ",bpw4" : p.BPW == 2 ? ",bpw2" : ",bpw1"),
+                 p.nt ? ",nt" : "", sep, dt, wg, p.L);
+      break;
+    case SlsForm::one:
+      log_launch(tune.log, "sls_one_kernel<%d,%d%s%s>[%lld wg]", p.G, p.BW, sep, dt, wg);
+      break;
+    case SlsForm::ring:
+      log_launch(tune.log, "sls_kernel<%d,%s%s%s>[%lld wg]", p.G, p.exact ? "sequential" : (p.nt ? "split,nt" : "split"), sep, dt, wg);
+      break;
+  }
+  if (!wg) return hipSuccess;             // an empty launch enqueues nothing
+  const dim3 grid((unsigned)p.grid);
+  switch (p.form) {
+    case SlsForm::any:
+      launch_k(sls_any_kernel<E>, grid, s, stop, a);
+      break;
+    case SlsForm::flatc:
+      with_int<8, 16, 32>(p.G, [&](auto G) { with_int<5, 10, 20>(p.NL, [&](auto NL) { with_int<0, 1>(p.nt, [&](auto NT) {
+        launch_k(sls_flatc_kernel<G, NL, NT != 0, E>, grid, s, stop, a, p.L);
+      }); }); });
+      break;
+    case SlsForm::flat:   // (xcd_order 1: every launch deals the work list to the XCDs in slices)
+      with_int<8, 16, 32>(p.G, [&](auto G) { with_int<5, 10, 20>(p.NL, [&](auto NL) { with_int<0, 1>(p.nt, [&](auto NT) {
+        with_int<1, 2, 4>(p.BPW, [&](auto BPW) {
+          if constexpr (BPW == 1 || NL <= 10) launch_k(sls_flat_kernel<G, NL, BPW, NT != 0, E>, grid, s, stop, a, p.L, 1);
+        });
+      }); }); });
+      break;
+    case SlsForm::one:
+      with_int<4, 8, 16, 32>(p.G, [&](auto G) { with_int<64, 16>(p.BW, [&](auto BW) {
+        launch_k(sls_one_kernel<G, BW, E>, grid, s, stop, a, p.tiles);
+      }); });
+      break;
+    case SlsForm::ring:
+      with_int<2, 4, 8, 16, 32, 64>(p.G, [&](auto G) { with_int<0, 1>(p.exact, [&](auto EXACT) { with_int<0, 1>(p.nt, [&](auto NT) {
+        if constexpr (!(EXACT && NT)) launch_k(sls_kernel<G, EXACT != 0, NT != 0, E>, grid, s, stop, a);
+      }); }); });
+      break;
+  }
+  return hipGetLastError();
+}
+
+}  // namespace
+
+// Tunables (drs_set_option, kept per engine in Tune): "sls_flat" / "sls_bpw" the flat variant and its bags
+// per wave (0 = auto), "sls_nt" non-temporal row loads, "sls_one" the one-lookup copy form and its samples per wave.
+SlsPlan plan_sls(const SlsArgs& a, bool exact, bool short_bags, const Tune& tune, int dtype) {
+  SlsPlan p;
+  p.dtype = dtype;
+  const int D = a.D, n_q = a.q.n_q, n_smp = a.q.cum[n_q];
+  const int64_t n_bags = (int64_t)n_smp * a.T;
+  // widths that are not whole 16-byte pieces, or wider than a wave: the generic form (sequential order)
+  if ((D & 3) || D > 256) {
+    p.form = SlsForm::any;
+    p.exact = true;
+    p.grid = n_bags;
+    return p;
+  }
+  // the flat variant, in split order only: every coalesced query must have the same fixed bag length L >= 2 (L == 1
+  // is a copy), G must be one of the instantiated widths, BPW must divide T (a wave's bags belong to one sample) and
+  // BPW * L rows must fit NL loads per lane
+  const int G = lanes_per_row(D), NG = 64 / G;
+  const int L = n_q >= 1 ? a.uniform_len[0] : -1;
+  bool flat = !exact && tune.sls_flat && n_q >= 1 && L >= 2 && (G == 8 || G == 16 || G == 32);
+  for (int i = 1; flat && i < n_q; ++i) flat = a.uniform_len[i] == L;
   int bpw = 1;
-  if (tune.sls_bpw > 0) {
+  if (flat && tune.sls_bpw > 0) {
     bpw = tune.sls_bpw;
-    if ((bpw != 1 && bpw != 2 && bpw != 4) || a.T % bpw) return p;
-  } else {
+    flat = (bpw == 1 || bpw == 2 || bpw == 4) && a.T % bpw == 0;
+  } else if (flat) {
     // short bags share a wave until it has five loads per lane to issue (measured on RM3,
     // 12 x 10M x 32, L = 20, beside its GEMM launches: 2 bags per wave 0.48 of peak, 1 or 4 bags
     // 0.44; the chip to itself: 0.60 / 0.55 / 0.59)
@@ -903,148 +838,45 @@ FlatPlan flat_plan(const SlsArgs& a, const Tune& tune) {
   // (30 loads per lane -- RM2: L = 120, D = 64 -- in the one-bag-per-wave form was measured in round 4: 497.6 us per
   // launch against the ring walk's 497.4 us; not kept)
   const int nl = need <= 5 ? 5 : need <= 10 ? 10 : need <= 20 ? 20 : 0;
-  if (!nl || (bpw > 1 && nl > 10)) return p;
-  p.ok = true; p.G = G; p.NL = nl; p.BPW = bpw; p.L = L; p.xcd = 1;
-  p.coal = bpw == 1 && tune.sls_flat == 1;      // "sls_flat" 2 forces the phased form
-  p.nt = tune.sls_nt;
-  const unsigned n_work = (unsigned)a.q.cum[a.q.n_q] * (unsigned)(a.T / bpw);
-  p.grid = p.coal ? n_work : (p.xcd ? 8u * ((n_work + 7u) / 8u) : n_work);
+  if (flat && nl && (bpw == 1 || nl <= 10)) {
+    p.form = bpw == 1 && tune.sls_flat == 1 ? SlsForm::flatc : SlsForm::flat;   // "sls_flat" 2 forces the phased form
+    p.G = G; p.NL = nl; p.BPW = bpw; p.L = L; p.nt = tune.sls_nt != 0;
+    const unsigned n_work = (unsigned)n_smp * (unsigned)(a.T / bpw);
+    p.grid = p.form == SlsForm::flatc ? n_work : 8u * ((n_work + 7u) / 8u);   // (the phased form: whole rounds of 8 XCDs)
+    return p;
+  }
+  // Bags of a few rows (W&D / NCF: one lookup per table) would leave most of a wave idle in the wave-per-bag variant: a
+  // lane group per bag is both faster there and bit-exact -- unless the flat variant took the launch above
+  p.exact = exact || short_bags;
+  // the one-lookup copy form: every coalesced query has fixed bags of ONE row, a row is 4 / 8 / 16 / 32 lanes x 16 B
+  bool one = p.exact && tune.sls_one && n_q >= 1 && (D == 16 || D == 32 || D == 64 || D == 128);
+  for (int i = 0; one && i < n_q; ++i) one = a.uniform_len[i] == 1;
+  if (one) {
+    p.form = SlsForm::one;
+    p.G = D / 4;
+    // samples per wave: 64, unless that leaves the launch under 1 024 waves ("sls_one" 64 / 16 force one)
+    p.BW = tune.sls_one == 64 || tune.sls_one == 16 ? tune.sls_one : (int64_t)a.T * ((n_smp + 63) / 64) < 1024 ? 16 : 64;
+    p.tiles = (n_smp + p.BW - 1) / p.BW;
+    p.grid = (int64_t)a.T * p.tiles;
+    return p;
+  }
+  // the ring walk.  The non-temporal hint is for bags of many rows out of big tables; the one-lookup models (W&D, NCF,
+  // MT-WnD: the sequential form) keep their rows cacheable -- NCF's tables live in the Infinity Cache (measured: -3 % with it)
+  p.form = SlsForm::ring;
+  p.G = G;
+  p.nt = !p.exact && tune.sls_nt;
+  p.grid = p.exact ? (n_bags + NG - 1) / NG : n_bags;
   return p;
 }
 
-template <int G, int NL, class E>
-hipError_t launch_flat_b(const SlsArgs& a, const FlatPlan& p, dim3 grid, hipStream_t s, hipEvent_t stop) {
-  if (p.coal && p.nt) launch_k(sls_flatc_kernel<G, NL, true, E>, grid, s, stop, a, p.L);
-  else if (p.coal) launch_k(sls_flatc_kernel<G, NL, false, E>, grid, s, stop, a, p.L);
-  else if (p.nt) {
-    if (p.BPW == 1) launch_k(sls_flat_kernel<G, NL, 1, true, E>, grid, s, stop, a, p.L, p.xcd);
-    else if constexpr (NL <= 10) {
-      if (p.BPW == 2) launch_k(sls_flat_kernel<G, NL, 2, true, E>, grid, s, stop, a, p.L, p.xcd);
-      else launch_k(sls_flat_kernel<G, NL, 4, true, E>, grid, s, stop, a, p.L, p.xcd);
-    }
+hipError_t launch_sls(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hipStream_t s, hipEvent_t stop) {
+  if (a.D <= 0) return hipErrorInvalidValue;
+  switch (p.dtype) {
+    case DRS_TABLE_FP16: return launch_sls_e<F16>(a, p, tune, s, stop);
+    case DRS_TABLE_BF16: return launch_sls_e<BF16>(a, p, tune, s, stop);
+    case DRS_TABLE_INT8_ROWWISE: return launch_sls_e<I8>(a, p, tune, s, stop);
+    default: return launch_sls_e<F32>(a, p, tune, s, stop);
   }
-  else if (p.BPW == 1) launch_k(sls_flat_kernel<G, NL, 1, false, E>, grid, s, stop, a, p.L, p.xcd);
-  else if constexpr (NL <= 10) {
-    if (p.BPW == 2) launch_k(sls_flat_kernel<G, NL, 2, false, E>, grid, s, stop, a, p.L, p.xcd);
-    else launch_k(sls_flat_kernel<G, NL, 4, false, E>, grid, s, stop, a, p.L, p.xcd);
-  }
-  return hipGetLastError();
-}
-template <int G, class E>
-hipError_t launch_flat_g(const SlsArgs& a, const FlatPlan& p, dim3 grid, hipStream_t s, hipEvent_t stop) {
-  switch (p.NL) {
-    case 5: return launch_flat_b<G, 5, E>(a, p, grid, s, stop);
-    case 10: return launch_flat_b<G, 10, E>(a, p, grid, s, stop);
-    default: return launch_flat_b<G, 20, E>(a, p, grid, s, stop);
-  }
-}
-template <class E>
-hipError_t launch_flat(const SlsArgs& a, const FlatPlan& p, hipStream_t s, hipEvent_t stop) {
-  const int64_t n_bags = (int64_t)a.q.cum[a.q.n_q] * a.T;
-  if (n_bags == 0) return hipSuccess;
-  const dim3 grid(p.grid);
-  switch (p.G) {
-    case 8: return launch_flat_g<8, E>(a, p, grid, s, stop);
-    case 16: return launch_flat_g<16, E>(a, p, grid, s, stop);
-    default: return launch_flat_g<32, E>(a, p, grid, s, stop);
-  }
-}
-
-}  // namespace
-
-// Tunables (drs_set_option, kept per engine in Tune): "sls_flat" / "sls_bpw" the flat variant and its bags
-// per wave (0 = auto), "sls_nt" non-temporal row loads.
-static inline bool any_width(int D) { return (D & 3) || D > 256; }      // widths only sls_any_kernel takes
-// the one-lookup copy form: every coalesced query has fixed bags of ONE row, a row is 4 / 8 / 16 / 32 lanes x 16 B
-static inline bool one_lookup(const SlsArgs& a, const Tune& tune) {
-  if (!tune.sls_one || a.q.n_q < 1 || !(a.D == 16 || a.D == 32 || a.D == 64 || a.D == 128)) return false;
-  for (int i = 0; i < a.q.n_q; ++i) if (a.uniform_len[i] != 1) return false;
-  return true;
-}
-// samples per wave: 64, unless that leaves the launch under 1 024 waves ("sls_one" 64 / 16 force one)
-static inline int one_lookup_tile(const SlsArgs& a, const Tune& tune) {
-  if (tune.sls_one == 64 || tune.sls_one == 16) return tune.sls_one;
-  return (int64_t)a.T * ((a.q.cum[a.q.n_q] + 63) / 64) < 1024 ? 16 : 64;
-}
-static inline int64_t one_lookup_grid(const SlsArgs& a, const Tune& tune) {
-  const int bw = one_lookup_tile(a, tune);
-  return (int64_t)a.T * ((a.q.cum[a.q.n_q] + bw - 1) / bw);
-}
-
-bool sls_flat_applicable(const SlsArgs& a, const Tune& tune) { return !any_width(a.D) && flat_plan(a, tune).ok; }
-
-int64_t sls_grid_blocks(const SlsArgs& a, int exact, const Tune& tune) {
-  const int64_t n_bags = (int64_t)a.q.cum[a.q.n_q] * a.T;
-  if (any_width(a.D)) return n_bags;
-  if (!exact) {
-    const FlatPlan p = flat_plan(a, tune);
-    return p.ok ? (int64_t)p.grid : n_bags;
-  }
-  if (one_lookup(a, tune)) return one_lookup_grid(a, tune);
-  int G = lanes_per_row(a.D);
-  const int bags = 64 / G;
-  return (n_bags + bags - 1) / bags;
-}
-
-// the launch for tables of element type E (F32 / F16 / BF16 / I8): the same decisions, the same grids for every E
-template <class E>
-static hipError_t launch_sls_e(const SlsArgs& a, int exact, const Tune& tune, hipStream_t s, hipEvent_t stop) {
-  const char* dt = E::tag;                // dispatch log: "" for fp32, else the dtype token
-  const char* sep = *dt ? "," : "";
-  const int D = a.D;
-  if (D <= 0) return hipErrorInvalidValue;
-  if (any_width(D)) {            // the generic form: any width, sequential order
-    const int64_t n_bags = (int64_t)a.q.cum[a.q.n_q] * a.T;
-    if (n_bags == 0) return hipSuccess;
-    log_launch(tune.log, "sls_any_kernel%s%s%s[%lld wg, D=%d]", *dt ? "<" : "", dt, *dt ? ">" : "", (long long)n_bags, D);
-    launch_k(sls_any_kernel<E>, dim3((unsigned)n_bags), s, stop, a);
-    return hipGetLastError();
-  }
-  if (!exact) {
-    const FlatPlan p = flat_plan(a, tune);
-    if (p.ok) {
-      log_launch(tune.log, "%s<%d,%d%s%s%s%s>[%u wg, L=%d]", p.coal ? "sls_flatc_kernel" : "sls_flat_kernel", p.G, p.NL,
-                 p.coal ? "" : (p.BPW == 4 ? ",bpw4" : p.BPW == 2 ? ",bpw2" : ",bpw1"), p.nt ? ",nt" : "", sep, dt, p.grid, p.L);
-      return launch_flat<E>(a, p, s, stop);
-    }
-  }
-  if (exact && one_lookup(a, tune)) {
-    const int bw = one_lookup_tile(a, tune);
-    const int tiles = (a.q.cum[a.q.n_q] + bw - 1) / bw;
-    if (tiles == 0) return hipSuccess;
-    const dim3 grid((unsigned)one_lookup_grid(a, tune));
-    log_launch(tune.log, "sls_one_kernel<%d,%d%s%s>[%u wg]", D / 4, bw, sep, dt, grid.x);
-    if (bw == 64) {
-      if (D == 16) launch_k(sls_one_kernel<4, 64, E>, grid, s, stop, a, tiles);
-      else if (D == 32) launch_k(sls_one_kernel<8, 64, E>, grid, s, stop, a, tiles);
-      else if (D == 64) launch_k(sls_one_kernel<16, 64, E>, grid, s, stop, a, tiles);
-      else launch_k(sls_one_kernel<32, 64, E>, grid, s, stop, a, tiles);
-    } else {
-      if (D == 16) launch_k(sls_one_kernel<4, 16, E>, grid, s, stop, a, tiles);
-      else if (D == 32) launch_k(sls_one_kernel<8, 16, E>, grid, s, stop, a, tiles);
-      else if (D == 64) launch_k(sls_one_kernel<16, 16, E>, grid, s, stop, a, tiles);
-      else launch_k(sls_one_kernel<32, 16, E>, grid, s, stop, a, tiles);
-    }
-    return hipGetLastError();
-  }
-  log_launch(tune.log, "sls_kernel<%d,%s%s%s>[%lld wg]", lanes_per_row(D), exact ? "sequential" : (tune.sls_nt ? "split,nt" : "split"), sep, dt,
-             (long long)sls_grid_blocks(a, exact, tune));
-  // the non-temporal hint is for bags of many rows out of big tables; the one-lookup models (W&D, NCF, MT-WnD:
-  // the sequential form) keep their rows cacheable -- NCF's tables live in the Infinity Cache (measured: -3 % with it)
-  const int nt = exact ? 0 : tune.sls_nt;
-  if (D <= 8) return launch_u<2, 4, E>(a, exact, nt, s, stop);
-  if (D <= 16) return launch_u<4, 4, E>(a, exact, nt, s, stop);
-  if (D <= 32) return launch_u<8, 4, E>(a, exact, nt, s, stop);
-  if (D <= 64) return launch_u<16, 4, E>(a, exact, nt, s, stop);
-  if (D <= 128) return launch_u<32, 4, E>(a, exact, nt, s, stop);
-  return launch_u<64, 4, E>(a, exact, nt, s, stop);
-}
-
-hipError_t launch_sls(const SlsArgs& a, int exact, const Tune& tune, hipStream_t s, hipEvent_t stop, int dtype) {
-  if (dtype == DRS_TABLE_FP16) return launch_sls_e<F16>(a, exact, tune, s, stop);
-  if (dtype == DRS_TABLE_BF16) return launch_sls_e<BF16>(a, exact, tune, s, stop);
-  if (dtype == DRS_TABLE_INT8_ROWWISE) return launch_sls_e<I8>(a, exact, tune, s, stop);
-  return launch_sls_e<F32>(a, exact, tune, s, stop);
 }
 
 // ---------------------------------------------------------------------------
