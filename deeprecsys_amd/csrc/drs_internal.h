@@ -76,6 +76,7 @@ struct Tune {
   int gemm32_small_blocks = 0;   // ... when that shape gives at least this many workgroups
   int gemm32_small = 0;          // ... and smaller launches this gemm32 shape (0 = gemm_kernel | 22 | 21 | 12 | 11)
   int gemm32_blocks = 512;       // ... when its 128 x 128 workgroups number at least this many (two per CU)
+  int bf16_tile = 0;             // gemm_bf16_kernel's tile shape (0 = by workgroup count | 44 | 22 | 12; gemm_bf16.hip gemm_bf16_plan)
   int64_t mlp_rows32 = 0;        // stream4_kernel: launches of at least this many rows take 32 rows per workgroup (0 = never)
   DispatchLog* log = nullptr;    // where the launch functions note what they chose (the slot being enqueued; may be null)
   // stream4_kernel's column-split form (mlp.hip SArgs::ns): launches of at most mlp_nsplit_rows rows spread the first
@@ -93,6 +94,7 @@ struct Tune {
 hipError_t device_init(int device, const float** zero_page);
 hipError_t mlp_set_attrs();    // mlp.hip's kernels, on the current device
 hipError_t gemm_set_attrs();   // gemm.hip's kernels, on the current device
+hipError_t gemm_bf16_set_attrs();   // gemm_bf16.hip's kernels, on the current device
 
 // One gather launch, decided once by plan_sls and run by launch_sls (sls.hip).  Host-only.
 //   form: any (any row width) | ring (sls_kernel) | one (one lookup per bag) | flat | flatc (fixed-length bags)
@@ -277,6 +279,11 @@ hipError_t launch_dien_rnn(const float* T, int64_t ldt, const QTable& q, int32_t
 // per 128-column pass and 64-k chunk, per wave (16 columns), four float4 per lane.
 int64_t stream_packed_floats(int K, int N);
 hipError_t launch_pack_stream_weights(const float* W, int32_t K, int32_t N, float* Wp, hipStream_t stream);
+
+// "mlp_dtype" 2: the bf16 twin of one FC layer (gemm_bf16.hip): W [N, K] fp32 -> Wb [N, bf16_kpad(K)] bf16, rounded to
+// nearest even (NaN stays NaN), zeros from K on
+inline int32_t bf16_kpad(int32_t K) { return (K + 63) / 64 * 64; }
+hipError_t launch_bf16_twin(const float* W, int32_t K, int32_t N, uint16_t* Wb, hipStream_t stream);
 
 // random 128- / 256- / 512-byte row reads over [base, base + bytes) in the gather's access shape, timed with events on `s`
 // (sls.hip probe_rows_kernel); sink: >= 1 KiB of device memory nobody reads

@@ -60,6 +60,7 @@ struct Layer {
   int32_t m = 0, n = 0;  // W is [m, n]
   bool set = false;
   bool packed = false;   // a packed twin (MFMA operand order, mlp.hip) follows W in the arena
+  uint16_t* Wb = nullptr;  // "mlp_dtype" 2, K >= 64 and N >= 64: the bf16 twin [m, bf16_kpad(n)] (an allocation of its own)
 };
 
 struct Mlp {
@@ -179,6 +180,7 @@ struct drs_engine {
   std::vector<Arena> arenas;
   std::vector<hipMemGenericAllocationHandle_t> spacers;   // "table_spacer": device memory taken (never mapped) between placement candidates
   size_t tables_bytes = 0;
+  int mlp_dtype = DRS_MLP_FP32;     // "mlp_dtype": DRS_MLP_BF16 -- the FC layers with K >= 64 and N >= 64 on the bf16 matrix cores (bf16_layer)
   int table_dtype = DRS_TABLE_FP32; // "table_dtype": element type of the arena (DRS_TABLE_*); sums and outputs stay fp32
   // how the NEXT arena is built (drs_create's first one, "table_placement" -1 candidates)
   int table_alloc = 0;              // 0 hipMalloc | 1 virtual-memory API
@@ -296,6 +298,12 @@ namespace eng {
 
 // engine_create.hip
 void choose_launch_forms(drs_engine* e);
+// "mlp_dtype" 2: is the K x N layer a bf16 layer?  By the layer's shape alone -- never by the launch set or another option
+inline bool bf16_shape(const drs_engine* e, int64_t K, int64_t N) { return e->mlp_dtype == DRS_MLP_BF16 && K >= 64 && N >= 64; }
+// every MLP the launch sets run (bottom, top, final, task heads; not DIN's units or DIEN's recurrent layers) ...
+std::vector<Mlp*> served_mlps(drs_engine* e);
+// ... and the bf16 twin of one of their layers, built from its weights on the device (hipErrorOutOfMemory: nothing changed)
+hipError_t build_bf16_twin(Layer& L);
 // where the tables of an arena of type `dtype` start (*off, units of table_unit_bytes) and its bytes
 size_t table_layout(const drs_engine* e, int dtype, std::vector<int64_t>* off);
 int32_t fail(drs_engine* e, int32_t code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));

@@ -17,6 +17,7 @@ hipError_t device_init(int device, const float** zero_page) {
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = mlp_set_attrs();
     if (e == hipSuccess) e = gemm_set_attrs();
+    if (e == hipSuccess) e = gemm_bf16_set_attrs();
     if (e == hipSuccess && !zero[device]) {
       e = hipMalloc(reinterpret_cast<void**>(&zero[device]), 256);
       if (e == hipSuccess) e = hipMemset(zero[device], 0, 256);
@@ -60,6 +61,22 @@ int32_t fail(drs_engine* e, int32_t code, const char* fmt, ...) {
 int32_t set_device(drs_engine* e) {
   HIP_TRY(e, hipSetDevice(e->device));
   return DRS_OK;
+}
+
+std::vector<Mlp*> served_mlps(drs_engine* e) {
+  std::vector<Mlp*> v = {&e->bot, &e->top, &e->fin};
+  for (auto& tk : e->tasks) v.push_back(&tk);
+  return v;
+}
+
+hipError_t build_bf16_twin(Layer& L) {
+  const bool fresh = !L.Wb;
+  hipError_t r = fresh ? hipMalloc(&L.Wb, sizeof(uint16_t) * (size_t)L.m * bf16_kpad(L.n)) : hipSuccess;
+  if (r != hipSuccess) { L.Wb = nullptr; return r; }
+  r = launch_bf16_twin(L.W, L.n, L.m, L.Wb, nullptr);
+  if (r == hipSuccess) r = hipStreamSynchronize(nullptr);
+  if (r != hipSuccess && fresh) { (void)hipFree(L.Wb); L.Wb = nullptr; }
+  return r;
 }
 
 int32_t alloc_batch(drs_engine* e, Batch& b) {
@@ -544,6 +561,8 @@ int32_t drs_destroy(drs_handle e) {
   }
   DTR("slots freed");
   for (auto& b : e->batches) free_batch(b);
+  for (Mlp* m : served_mlps(e))
+    for (auto& l : m->layers) { if (l.Wb) (void)hipFree(l.Wb); l.Wb = nullptr; }
   for (Mlp* m : {&e->bot, &e->top, &e->fin})
     for (auto& l : m->layers) { l.W = l.b = nullptr; }
   e->tasks.clear();
@@ -679,6 +698,13 @@ int32_t drs_set_fc(drs_handle e, int32_t mlp, int32_t layer, const float* h_W, c
     }
     e->w_arena_used = woff;
   }
+  // a bf16 layer ("mlp_dtype" 2) keeps a bf16 twin: its memory first, so that a failure leaves the layer as it was
+  const bool twin = L.packed && bf16_shape(e, n, m);
+  if (twin && !L.Wb && hipMalloc(&L.Wb, sizeof(uint16_t) * (size_t)m * bf16_kpad(n)) != hipSuccess) {
+    (void)hipGetLastError();
+    L.Wb = nullptr;
+    return fail(e, DRS_ERR_OOM, "no room for the bf16 twin of the %dx%d layer", n, m);
+  }
   HIP_TRY(e, hipMemcpy(L.W, h_W, sizeof(float) * (size_t)m * n, hipMemcpyHostToDevice));
   HIP_TRY(e, hipMemcpy(L.b, h_b, sizeof(float) * (size_t)m, hipMemcpyHostToDevice));
   if (L.packed) {
@@ -687,6 +713,7 @@ int32_t drs_set_fc(drs_handle e, int32_t mlp, int32_t layer, const float* h_W, c
     HIP_TRY(e, hipStreamSynchronize(nullptr));
   }
   L.m = m; L.n = n; L.set = true;
+  if (twin) HIP_TRY(e, build_bf16_twin(L));
   return DRS_OK;
 }
 

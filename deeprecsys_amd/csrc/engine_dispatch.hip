@@ -20,6 +20,9 @@ bool is_wide(const drs_engine* e, const Mlp& m, int l) {
   return e->mlp_split && (int64_t)m.ln[l] * m.ln[l + 1] >= e->mlp_wide_kn;
 }
 
+// "mlp_dtype" 2: layer l of m runs on the bf16 matrix cores, always as a launch of its own (gemm_bf16.hip)
+bool is_bf16(const drs_engine* e, const Mlp& m, int l) { return bf16_shape(e, m.ln[l], m.ln[l + 1]); }
+
 void fill_chain(ChainArgs& c, const Mlp& m, int l0, int cnt, const float* x, int64_t ldx, int64_t M,
                 float* y, int64_t ldy) {
   memset(&c, 0, sizeof c);
@@ -59,8 +62,8 @@ hipError_t rejoin_stream(drs_engine* e, Slot& s) {
 }
 
 
-// Run all layers of `m` on x -> y.  A huge layer runs as its own 2-D launch; runs of
-// ordinary layers are fused into one LDS-resident chain.  Segment outputs that are not
+// Run all layers of `m` on x -> y.  A huge layer and a bf16 layer ("mlp_dtype" 2) run as their own 2-D launch; runs of
+// ordinary layers between them are fused into one LDS-resident chain.  Segment outputs that are not
 // the final one ping-pong between s.H and s.Hb.  first (optional): the caller's plan of layer 0 alone.
 int32_t run_mlp(drs_engine* e, Slot& s, const Mlp& m, const float* x, int64_t ldx, int64_t M, float* y, int64_t ldy,
                 const Done* done = nullptr, const XSrc* xs = nullptr, const MlpPlan* first = nullptr) {
@@ -78,15 +81,16 @@ int32_t run_mlp(drs_engine* e, Slot& s, const Mlp& m, const float* x, int64_t ld
       const XSrc* x0 = l0 == 0 ? xs : nullptr;
       if (!n)
         return plan_layer(in, ldin, M, m.ln[l0], m.layers[l0].W, m.layers[l0].b, m.ln[l0 + 1], act_of(m, l0), out, ldo,
-                          e->tune, d, x0, &own);
+                          e->tune, d, x0, &own, is_bf16(e, m, l0) ? m.layers[l0].Wb : nullptr);
       ChainArgs c;
       fill_chain(c, m, l0, n, in, ldin, M, out, ldo);
       return plan_chains(c, nullptr, e->tune, d, x0, nullptr, nullptr, &own);
     };
     const bool given = l0 == 0 && first;
     cnt = 0;
-    if (!given && !is_wide(e, m, l0))
-      while (l0 + cnt < n_layers && cnt < DRS_MAX_CHAIN && !is_wide(e, m, l0 + cnt)) ++cnt;
+    auto alone = [&](int l) { return is_wide(e, m, l) || is_bf16(e, m, l); };
+    if (!given && !alone(l0))
+      while (l0 + cnt < n_layers && cnt < DRS_MAX_CHAIN && !alone(l0 + cnt)) ++cnt;
     while (cnt > 0 && !plan(cnt)) --cnt;   // the longest run that a chain kernel holds, else the layer alone
     const bool ok = given || cnt > 0 || plan(0);
     cnt = cnt > 0 ? cnt : 1;
@@ -107,8 +111,8 @@ bool fused_plan(const drs_engine* e, const Slot& s, int64_t Mv, float* out, cons
   if (!e->mlp_fuse || Mv < e->mlp_fuse_rows || e->kind != DRS_MODEL_DLRM) return false;
   const int nb = (int)e->bot.layers.size(), nt = (int)e->top.layers.size();
   if (nb < 1 || nt < 1 || nb > DRS_MAX_CHAIN || nt > DRS_MAX_CHAIN) return false;
-  for (int l = 0; l < nb; ++l) if (is_wide(e, e->bot, l)) return false;
-  for (int l = 0; l < nt; ++l) if (is_wide(e, e->top, l)) return false;
+  for (int l = 0; l < nb; ++l) if (is_wide(e, e->bot, l) || is_bf16(e, e->bot, l)) return false;
+  for (int l = 0; l < nt; ++l) if (is_wide(e, e->top, l) || is_bf16(e, e->top, l)) return false;
   ChainArgs a, b;
   fill_chain(a, e->bot, 0, nb, nullptr, e->m_den, Mv, s.T, e->ldT);
   if (e->interaction_op == DRS_INTERACT_CAT) {
@@ -419,8 +423,8 @@ static int32_t mlp_ncf(SetCtx& x) {
     fill_chain(ca, e->top, 0, nt, s.T + 2 * D, e->ldT, Mv, s.H2 + D, ldc);
     fill_chain(cb, e->fin, 0, 1, s.H2, ldc, Mv, x.out, e->n_out);
     const SumArgs sum = {s.T, e->ldT, 0, D, D, s.H2, ldc};
-    bool wide = is_wide(e, e->fin, 0);
-    for (int l = 0; l < nt; ++l) wide = wide || is_wide(e, e->top, l);
+    bool wide = is_wide(e, e->fin, 0) || is_bf16(e, e->fin, 0);
+    for (int l = 0; l < nt; ++l) wide = wide || is_wide(e, e->top, l) || is_bf16(e, e->top, l);
     MlpPlan p;
     if (!wide && plan_chains(ca, &cb, e->tune, x.dp, nullptr, nullptr, &sum, &p)) {
       HIP_TRY(e, launch_plan(p, e->tune, s.stream));
@@ -480,8 +484,9 @@ static int32_t mlp_dense(SetCtx& x) {
   } else {
     // W&D / MT-WnD: Concat(dense, pooled embeddings) feeds the first top layer.  When that layer goes to a GEMM form
     // that can read a split row ("gemm_split", gemm_plan) it takes the dense columns from the queries' own arrays;
-    // otherwise the dense rows are copied in front of the embeddings first.
-    if (e->gemm_split && !e->top.layers.empty() && is_wide(e, e->top, 0)) {
+    // otherwise the dense rows are copied in front of the embeddings first (so does a bf16 first layer: gemm_bf16_kernel
+    // reads whole rows).
+    if (e->gemm_split && !e->top.layers.empty() && is_wide(e, e->top, 0) && !is_bf16(e, e->top, 0)) {
       XSrc xsp = x.xs;
       xsp.ksplit = e->m_den;
       // (the layer's output as run_mlp would place it: the model's output, or s.H ahead of further layers)
@@ -841,10 +846,23 @@ int32_t drs_fc(drs_handle e, const float* d_x, int64_t M, int32_t K, const float
   Slot& s = e->slots[0];
   if (s.busy && (rc = wait_slot(e, s, nullptr))) return rc;
   MlpPlan p;
-  if (M > 0 && !plan_layer(d_x, K, M, K, d_W, d_b, N, act, d_y, N, e->tune, nullptr, nullptr, &p))
-    return fail(e, DRS_ERR_HIP, "no kernel takes the %dx%d layer", K, N);
-  if (M > 0) HIP_TRY(e, launch_plan(p, e->tune, s.stream));
-  HIP_TRY(e, hipStreamSynchronize(s.stream));
+  // "mlp_dtype" 2: a bf16 layer by its shape, as in a launch set -- d_W rounded into a scratch twin first
+  uint16_t* wb = nullptr;
+  if (M > 0 && bf16_shape(e, K, N)) {
+    if (hipMalloc(&wb, sizeof(uint16_t) * (size_t)N * bf16_kpad(K)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(e, DRS_ERR_OOM, "drs_fc: no room for the bf16 twin of the %dx%d layer", K, N);
+    }
+    hipError_t r = launch_bf16_twin(d_W, K, N, wb, s.stream);
+    if (r != hipSuccess) { (void)hipFree(wb); return fail(e, DRS_ERR_HIP, "drs_fc: %s", hipGetErrorString(r)); }
+  }
+  hipError_t r = hipSuccess;
+  const bool ok = M <= 0 || plan_layer(d_x, K, M, K, d_W, d_b, N, act, d_y, N, e->tune, nullptr, nullptr, &p, wb);
+  if (ok && M > 0) r = launch_plan(p, e->tune, s.stream);
+  if (r == hipSuccess) r = hipStreamSynchronize(s.stream);
+  if (wb) (void)hipFree(wb);
+  if (!ok) return fail(e, DRS_ERR_HIP, "no kernel takes the %dx%d layer", K, N);
+  HIP_TRY(e, r);
   return DRS_OK;
 }
 

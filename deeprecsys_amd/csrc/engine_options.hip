@@ -144,6 +144,32 @@ int32_t set_table_dtype(drs_engine* e, int64_t value) {
   return DRS_OK;
 }
 
+int32_t set_mlp_dtype(drs_engine* e, int64_t value) {
+  // DRS_MLP_BF16: every layer already set that is a bf16 layer by its shape (bf16_shape) gets its bf16 twin now, layers
+  // set later get theirs in drs_set_fc; back to DRS_MLP_FP32 the twins are freed.  All twins or none: on a failed
+  // allocation the ones just built are freed again and nothing has changed.
+  if (value == e->mlp_dtype) return DRS_OK;
+  if (e->kind == DRS_MODEL_DIN || e->kind == DRS_MODEL_DIEN)
+    return fail(e, DRS_ERR_UNSUPPORTED, "mlp_dtype %lld: the DIN and DIEN launches run their FC layers in fp32 only", (long long)value);
+  const int from = e->mlp_dtype;
+  e->mlp_dtype = (int)value;
+  std::vector<Layer*> built;
+  hipError_t r = hipSuccess;
+  for (Mlp* m : served_mlps(e))
+    for (Layer& L : m->layers) {
+      if (value != DRS_MLP_BF16) { if (L.Wb) (void)hipFree(L.Wb); L.Wb = nullptr; continue; }
+      if (r != hipSuccess || !L.set || L.Wb || !bf16_shape(e, L.n, L.m)) continue;
+      if ((r = build_bf16_twin(L)) == hipSuccess) built.push_back(&L);
+    }
+  if (r != hipSuccess) {
+    (void)hipGetLastError();
+    for (Layer* L : built) { (void)hipFree(L->Wb); L->Wb = nullptr; }
+    e->mlp_dtype = from;
+    return fail(e, r == hipErrorOutOfMemory ? DRS_ERR_OOM : DRS_ERR_HIP, "mlp_dtype: the layers' bf16 twins: %s", hipGetErrorString(r));
+  }
+  return DRS_OK;
+}
+
 int64_t arena_in_use(drs_engine* e) {
   return (int64_t)(std::find_if(e->arenas.begin(), e->arenas.end(), [&](const Arena& a) { return a.p == e->tables; }) - e->arenas.begin());
 }
@@ -176,6 +202,9 @@ const OptDesc kOptions[] = {
     OPT("mlp_nsplit", 0, 4, [](int64_t v) { return v == 0 || v == 2 || v == 4; }, 0, tune.mlp_nsplit),
     OPT("mlp_nsplit_rows", 0, kBig, nullptr, 0, tune.mlp_nsplit_rows),
     OPT("mlp_gemm_tile", 0, 322, [](int64_t v) { return v == 0 || v == 22 || v == 12 || v == 21 || v == 11 || v == 214 || v == 322 || v == 321 || v == 312 || v == 311; }, 0, tune.gemm_tile),
+    // DRS_MLP_BF16: the FC layers with K >= 64 and N >= 64 on the bf16 matrix cores (gemm_bf16.hip); "mlp_bf16_tile": force a tile shape
+    {"mlp_dtype", 0, 2, [](int64_t v) { return v == DRS_MLP_FP32 || v == DRS_MLP_BF16; }, O_SYNC, [](drs_engine* e) -> int64_t { return e->mlp_dtype; }, nullptr, set_mlp_dtype},
+    OPT("mlp_bf16_tile", 0, 44, [](int64_t v) { return v == 0 || v == 44 || v == 22 || v == 12; }, 0, tune.bf16_tile),
     // streams, host side
     OPT("shared_stream", 0, 2, nullptr, O_SYNC | O_STREAMS, shared_stream),
     OPT("mlp_streams", 1, 8, nullptr, O_SYNC | O_STREAMS, mlp_streams),

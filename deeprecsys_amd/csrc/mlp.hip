@@ -544,15 +544,16 @@ hipError_t mlp_set_attrs() {
 }
 
 // One layer: a GEMM form (gemm.hip) when the layer has one, else fc_kernel.  A split input row (XSrc::ksplit) is for
-// the GEMM forms only.
+// the GEMM forms only.  Wb: a bf16 layer ("mlp_dtype" 2) -- the bf16 GEMM form (gemm_bf16.hip) and no other.
 bool plan_layer(const float* x, int64_t ldx, int64_t M, int32_t K, const float* W, const float* b, int32_t N, int32_t act,
-                float* y, int64_t ldy, const Tune& tune, const Done* done, const XSrc* xs, MlpPlan* p) {
+                float* y, int64_t ldy, const Tune& tune, const Done* done, const XSrc* xs, MlpPlan* p, const uint16_t* Wb) {
   memset(p, 0, sizeof *p);
   if (done) p->done = *done;
   if (xs) p->xs = *xs;
   ChainArgs& L = p->a;
   L.x = x; L.ldx = ldx; L.M = M; L.n_layers = 1; L.width[0] = K; L.width[1] = N;
   L.W[0] = W; L.b[0] = b; L.act[0] = act; L.y = y; L.ldy = ldy;
+  if (Wb) { p->wb = Wb; return gemm_bf16_plan(tune, p); }
   if (N >= 64 && K >= 64 && gemm_plan(tune, p)) return true;
   if (p->xs.ksplit > 0 || !pick_kc(K, 0, 2, tune.mlp_kc, &p->kc, &p->nbuf)) return false;
   p->form = MlpForm::fc;
@@ -953,7 +954,7 @@ hipError_t launch_plan(const MlpPlan& p, const Tune& tune, hipStream_t s) {
       "stream4_kernel", "stream4_kernel<sum>", "stream4_kernel<2cu>", "stream4_kernel<rows32>", "stream4_kernel<nsplit2>",
       "stream4_kernel<nsplit4>", "stream4_kernel<rows32,nsplit2>", "stream4_kernel<rows32,nsplit4>", "stream_kernel<packed>",
       "stream_kernel<packed,2cu>", "stream_kernel<lds>", "chain_kernel", "fc_kernel", "gemm_kernel", "gemm_kernel",
-      "gemm32_kernel", "gemm32_kernel", "gemm32_kernel"};
+      "gemm32_kernel", "gemm32_kernel", "gemm32_kernel", "gemm_bf16_kernel"};
   const char* name = names[(int)p.form];
   const size_t lds = launch_lds(p);
   const int K = p.a.width[0], N = p.a.width[1];
@@ -964,6 +965,8 @@ hipError_t launch_plan(const MlpPlan& p, const Tune& tune, hipStream_t s) {
     log_launch(tune.log, "%s<%s,%d>[%u wg, %d layers]", name, p.vec ? "vec" : "scalar", p.kc, p.grid_x, p.a.n_layers + p.b.n_layers);
   else if (p.form == MlpForm::fc)
     log_launch(tune.log, "%s<%s,%d>[%u x %u wg, %dx%d]", name, p.vec ? "vec" : "scalar", p.kc, p.grid_x, p.grid_y, K, N);
+  else if (p.form == MlpForm::gemm_bf16)
+    log_launch(tune.log, "%s<%dx%d%s>[%u x %u wg, %dx%d]", name, 32 * p.tm, 32 * p.tn, p.vec ? "" : ",scalar", p.grid_x, p.grid_y, K, N);
   else if (p.form == MlpForm::gemm32_split)
     log_launch(tune.log, "%s<%d,%d,sbase,split%d>[%u x %u wg, %dx%d]", name, p.tm, p.tn, p.xs.ksplit, p.grid_x, p.grid_y, K, N);
   else
@@ -999,6 +1002,8 @@ hipError_t launch_plan(const MlpPlan& p, const Tune& tune, hipStream_t s) {
     }
     case MlpForm::gemm: case MlpForm::gemm_2cu: case MlpForm::gemm32: case MlpForm::gemm32_sbase: case MlpForm::gemm32_split:
       return launch_gemm(p, tune.zero, s);
+    case MlpForm::gemm_bf16:
+      return launch_gemm_bf16(p, s);
     case MlpForm::stream_packed: case MlpForm::stream_packed_2cu: case MlpForm::stream_lds:
       return launch_stream8(p, lds, s);
     default:

@@ -112,7 +112,8 @@ enum class MlpForm : int32_t {
   stream4_rows32_nsplit4,                            // stream4_kernel (mlp_stream4.hip)
   stream_packed, stream_packed_2cu, stream_lds,      // stream_kernel (mlp_stream8.hip)
   chain, fc,                                         // chain_kernel, fc_kernel (mlp.hip)
-  gemm, gemm_2cu, gemm32, gemm32_sbase, gemm32_split // gemm_kernel, gemm32_kernel (gemm.hip)
+  gemm, gemm_2cu, gemm32, gemm32_sbase, gemm32_split,// gemm_kernel, gemm32_kernel (gemm.hip)
+  gemm_bf16                                          // gemm_bf16_kernel (gemm_bf16.hip): a bf16 layer ("mlp_dtype" 2)
 };
 // One MLP launch, decided once (mlp.hip plan_chains / plan_layer) and run as it stands (launch_plan).
 struct MlpPlan {
@@ -123,7 +124,8 @@ struct MlpPlan {
   XSrc xs;
   ChainArgs a, b;               // the chain(s) (b.n_layers 0: one); fc / GEMM forms: the layer as a one-layer chain a
   int kc, nbuf, lda, sld, vec;  // chain_kernel / fc_kernel: K chunk, staging buffers, preloaded input / slab ld, float4 loads
-  int tm, tn;                   // gemm_kernel<tm, tn> | gemm32_kernel<tm, tn>
+  int tm, tn;                   // gemm_kernel<tm, tn> | gemm32_kernel<tm, tn> | gemm_bf16_kernel<tm, tn>
+  const uint16_t* wb;           // gemm_bf16: the layer's bf16 twin [N, bf16_kpad(K)]
   SArgs sa;                     // stream forms
   NSplit ns;
 };
@@ -134,12 +136,16 @@ inline bool can_defer(const MlpPlan& p) { return p.form == MlpForm::stream4 && p
 // b (may be null) on the same rows, with the dot interaction or the summed input between them.  plan_layer: one layer.
 bool plan_chains(const ChainArgs& a, const ChainArgs* b, const Tune& tune, const Done* done, const XSrc* xs,
                  const DotArgs* dot, const SumArgs* sum, MlpPlan* p);
+// Wb (optional): the layer's bf16 twin -- the layer is a bf16 layer and takes the bf16 GEMM form or none
 bool plan_layer(const float* x, int64_t ldx, int64_t M, int32_t K, const float* W, const float* b, int32_t N, int32_t act,
-                float* y, int64_t ldy, const Tune& tune, const Done* done, const XSrc* xs, MlpPlan* p);
+                float* y, int64_t ldy, const Tune& tune, const Done* done, const XSrc* xs, MlpPlan* p,
+                const uint16_t* Wb = nullptr);
 // the launch of a plan, noted in the dispatch log (tune.log)
 hipError_t launch_plan(const MlpPlan& p, const Tune& tune, hipStream_t s);
 bool gemm_plan(const Tune& tune, MlpPlan* p);   // gemm.hip: the GEMM form of the layer p->a, if it has one
 hipError_t launch_gemm(const MlpPlan& p, const float* zero, hipStream_t s);
+bool gemm_bf16_plan(const Tune& tune, MlpPlan* p);   // gemm_bf16.hip: the bf16 GEMM form of the layer p->a with the twin p->wb
+hipError_t launch_gemm_bf16(const MlpPlan& p, hipStream_t s);
 
 hipError_t launch_stream8(const MlpPlan& p, size_t lds, hipStream_t s);
 hipError_t stream8_set_attrs();

@@ -46,6 +46,17 @@ def _table_dtype(args):
     return _TABLE_DTYPES[name]
 
 
+_MLP_DTYPES = {"fp32": N.MLP_FP32, "bf16": N.MLP_BF16}
+
+
+def _mlp_dtype(args):
+    """--accel_mlp_dtype -> the engine's "mlp_dtype" value (fp32 when the flag is absent)."""
+    name = str(getattr(args, "accel_mlp_dtype", "fp32") or "fp32")
+    if name not in _MLP_DTYPES:
+        raise ValueError("--accel_mlp_dtype %r: one of %s" % (name, ", ".join(_MLP_DTYPES)))
+    return _MLP_DTYPES[name]
+
+
 def _init_table(n, m):
     # models/dlrm_s_caffe2.py:297-299
     return np.random.uniform(low=-np.sqrt(1 / n), high=np.sqrt(1 / n), size=(n, m)).astype(np.float32)
@@ -97,6 +108,7 @@ class _HipNet(object):
         n_stage = max(int(getattr(a, "num_batches", 0)), 1)
         max_batch = max(int(getattr(a, "max_mini_batch_size", 1)), int(getattr(a, "mini_batch_size", 1)), 1)
         dtype = _table_dtype(a)
+        mlp_dtype = _mlp_dtype(a)
         def make(n_slots):
             eng = N.Engine(self.kind, self.ln_emb, self.m_spa, ln_bot_cfg, ln_top_cfg,
                            interaction_op=interaction_op, interaction_itself=itself,
@@ -109,6 +121,10 @@ class _HipNet(object):
             # forms (and "preferred_slots") for the element size, and every table write below is rounded on the device
             if dtype != N.TABLE_FP32:
                 eng.set_option("table_dtype", dtype)
+            # --accel_mlp_dtype: the layers set below get their bf16 twins as they arrive (only when asked for: an fp32
+            # engine is never told)
+            if mlp_dtype != N.MLP_FP32:
+                eng.set_option("mlp_dtype", mlp_dtype)
             return eng
         eng = make(self._num_slots())
         if int(getattr(a, "accel_slots", 0) or 0) <= 0 and eng.get_option("preferred_slots") != eng.num_slots:

@@ -82,6 +82,11 @@ enum { DRS_INTERACT_DOT = 0, DRS_INTERACT_CAT = 1 };
  * fp32 scale and an fp32 bias; a row's value is fmaf(scale, q, 0.0f + bias) */
 enum { DRS_TABLE_FP32 = 0, DRS_TABLE_FP16 = 1, DRS_TABLE_BF16 = 2, DRS_TABLE_INT8_ROWWISE = 8 };
 
+/* arithmetic of the wide FC layers (option "mlp_dtype").  DRS_MLP_BF16: a layer of the bottom, top, final or task MLP
+ * with K >= 64 and N >= 64 rounds its input and its weights to bf16 (nearest even, NaN stays NaN) and accumulates the
+ * exact products in fp32 on the bf16 matrix cores; bias, activation, outputs and every other layer stay fp32 */
+enum { DRS_MLP_FP32 = 0, DRS_MLP_BF16 = 2 };
+
 /* FC epilogue (Relu / Sigmoid ops, models/dlrm_s_caffe2.py:268-272) */
 enum { DRS_ACT_NONE = 0, DRS_ACT_RELU = 1, DRS_ACT_SIGMOID = 2 };
 
@@ -279,7 +284,8 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  * Integer options of a handle; every key, its values, default and the measurement behind it: docs/OPTIONS.md.
  * Results never depend on an option except where noted (sls_exact: the gather's fp32 summation order; table_dtype:
  * the tables are stored in fp16 / bf16, rounded to nearest even, or quantized to 8 bits per value with a per-row scale
- * and bias, and still summed in fp32 into fp32 outputs).
+ * and bias, and still summed in fp32 into fp32 outputs; mlp_dtype: the FC layers with K >= 64 and N >= 64 take bf16
+ * operands on the matrix cores, accumulated in fp32 -- the operator-level FC call follows the handle's setting).
  * The product library takes the keys below; unknown key or value -> DRS_ERR_BAD_ARG.
  *   gather        "sls_exact" 0|1 (1: sequential order, bit-identical to Caffe2's SparseLengthsSum)
  *                 "sls_flat" 0|1|2   "sls_bpw" 0|1|2|4   "sls_nt" 0|1   "sls_one" 0|1|16|64
@@ -288,6 +294,7 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  *   MLP side      "mlp_fuse" 0|1   "mlp_split" 0|1   "mlp_wide_kn" n   "gemm_split" 0|1
  *                 "mlp_stream" 2|4   "mlp_stream_2cu" 0|1   "mlp_rows32" n
  *                 "mlp_nsplit" 0|2|4   "mlp_nsplit_rows" n   "mlp_gemm_tile" 0|22|12|21|11|214|322|321|312|311
+ *                 "mlp_dtype" 0|2 (DRS_MLP_FP32 | DRS_MLP_BF16; DLRM, W&D, MT-WnD and NCF only)   "mlp_bf16_tile" 0|44|22|12
  *   streams, host "shared_stream" 0|1|2   "mlp_streams" 1..8   "host_threads" -1..64
  *                 "zero_copy_inputs" 1|2|3   "out_dma" bytes   "dispatch_log" 0|1
  *   table arena   "table_placement" -1|-2|k   "table_alloc" 0|1|2   "table_spacer" bytes
