@@ -3,12 +3,12 @@
 // The reference builds both models from whatever widths its command line names: an attention unit is
 // create_mlp over "3*D - <arch_mlp_bot> - D" with any number of hidden layers of any width
 // (models/din.py:255-277), the recurrence is rnn_cell.BasicRNN(dim_in = arch_sparse_feature_size,
-// dim_out = hidden_size) for any two integers (models/dien.py:308-380).  din.hip's kernels are instantiated for the
+// dim_out = hidden_size) for any two integers (models/dien.py:308-380).  din.hip's and dien.hip's kernels are instantiated for the
 // shapes the shipped configs use (one hidden layer of <= 64 units; D in {16, 32, 64}, hidden_size in {8, 16, 32,
 // 64}); every other shape takes the kernels below, so that the boundary accepts what the reference accepts.
 // They are plain: one workgroup per sample, activations in LDS, each output its own k-ordered fmaf chain with the
 // bias added behind it -- the oracle's order (oracle/drs_oracle.c fc_impl), hence the attention output bit-identical
-// to it after a sequential-order gather, and the recurrence bit-identical to din.hip's two forms on the shapes all
+// to it after a sequential-order gather, and the recurrence bit-identical to dien.hip's two forms on the shapes all
 // three serve (tests/test_gpu_parity.py).  Not tuned: weights stream from L2 per sample.
 #include <hip/hip_runtime.h>
 #include <string.h>

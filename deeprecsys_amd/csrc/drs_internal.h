@@ -240,7 +240,7 @@ int64_t din_fused_grid(const SlsArgs& a, const Tune& tune);
 hipError_t launch_din_fused(const SlsArgs& a, int32_t h, const float* packed, float* R, int64_t ldr,
                             const Tune& tune, hipStream_t stream, hipEvent_t stop);
 
-// DIEN (din.hip; models/dien.py:308-432).  w: 8 device pointers {i2h_w, i2h_b, gates_t_w, gates_t_b} of
+// DIEN (dien.hip; models/dien.py:308-432).  w: 8 device pointers {i2h_w, i2h_b, gates_t_w, gates_t_b} of
 // layer 1 then layer 2; launch_dien_rnn: T [rows, Tn*D] pooled rows of the coalesced queries q ->
 // R [rows, H + 3*D] = [ last state of layer 2 | profile | ad | context ].
 // Any-shape forms (din_any.hip): attention units of any depth and width -- d_ln: the unit's n_ln widths on the device,

@@ -338,7 +338,7 @@ int32_t drs_create(const drs_model_cfg* cfg, int32_t device_id, drs_handle* out)
     case DRS_MODEL_DIEN: {
       if (T < 4) return bail(DRS_ERR_BAD_ARG, "DIEN needs at least 4 embedding tables");
       if (cfg->n_bot != 2 || e->bot.ln[0] != D || e->bot.ln[1] < 1) return bail(DRS_ERR_BAD_ARG, "DIEN: ln_bot must be [D, hidden_size]");
-      // D in {16, 32, 64} with hidden_size in {8, 16, 32, 64}: din.hip's forms; any other pair: din_any.hip
+      // D in {16, 32, 64} with hidden_size in {8, 16, 32, 64}: dien.hip's forms; any other pair: din_any.hip
       if (!dien_applicable(D, e->bot.ln[1]) && !dien_any_fits(D, e->bot.ln[1]))
         return bail(DRS_ERR_UNSUPPORTED, "DIEN: D + 4*hidden_size floats must fit 160 KB of LDS");
       const int H = e->bot.ln[1];

@@ -370,7 +370,7 @@ static int32_t mlp_dien(SetCtx& x) {
   DienTop tp;
   memset(&tp, 0, sizeof tp);
   const int nt = (int)e->top.layers.size();
-  // 3: the any-shape form (din_any.hip) -- every shape without an instance in din.hip, or on request
+  // 3: the any-shape form (din_any.hip) -- every shape without an instance in dien.hip, or on request
   const int form = dien_applicable(e->D, Hh) ? e->dien_mfma : 3;
   const bool mfma_form = form != 3 && form && Hh % 16 == 0;
   if (e->dien_fuse_top && mfma_form && nt >= 1 && nt <= 4 && e->top.layers[0].packed &&

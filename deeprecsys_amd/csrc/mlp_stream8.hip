@@ -394,7 +394,7 @@ __global__ __launch_bounds__(64 * NWV, RD3 ? 4 : 1) void stream_kernel(SArgs a, 
 // Where a packed round's time goes (in-kernel timeline, RMC1): the 16 MFMAs of the two waves of a
 // SIMD run as one phase at the pipe's rate (32 MFMAs in ~1 100 cycles) and the per-round
 // bookkeeping of both (~1 000 cycles: tile addresses, iterator state, epilogue tests) as another
-// -- a lone wave issues an fp32 MFMA only every ~75 cycles (also measured in din.hip's
+// -- a lone wave issues an fp32 MFMA only every ~75 cycles (also measured in dien.hip's
 // recurrence), so skewing the two waves against each other buys nothing (tried: s_sleep on waves
 // 4..7 after every barrier, 0..1 000 cycles: 33.3-33.7 us throughout), and prefetching the next
 // round's activation operands under the MFMAs neither (34.4 us).  The lever left is more MFMAs

@@ -1,4 +1,4 @@
-// Device helper shared by the DIEN recurrence's translation units (din.hip, din_any.hip).
+// Device helper shared by the DIEN recurrence's translation units (dien.hip, din_any.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

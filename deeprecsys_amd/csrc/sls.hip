@@ -35,12 +35,8 @@
 //     all 256 CUs; workgroups never cooperate.
 //   - index range is checked per row (Caffe2 ENFORCEs it): an out-of-range index
 //     raises bit 0 of *err and contributes zero instead of faulting.
-#include <hip/hip_ext.h>
-
-#include <cassert>
-#include <type_traits>
-
 #include "drs_internal.h"
+#include "launch_host.h"
 #include "owner_dev.h"
 
 namespace drs {
@@ -717,29 +713,6 @@ __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
     __builtin_amdgcn_s_waitcnt(0);
     if (threadIdx.x == 0) a.ts[2 * blockIdx.x + 1] = wall_clock64();
   }
-}
-
-// stop: optional event recorded BY the kernel dispatch itself (its completion signal) -- no
-// separate marker packet between this launch and the next one on the stream
-template <typename K, typename... X>
-void launch_kb(K kernel, dim3 grid, dim3 block, hipStream_t s, hipEvent_t stop, const X&... x) {
-  if (stop) hipExtLaunchKernelGGL(kernel, grid, block, 0, s, nullptr, stop, 0, x...);
-  else hipLaunchKernelGGL(kernel, grid, block, 0, s, x...);
-}
-template <typename K, typename... X>
-void launch_k(K kernel, dim3 grid, hipStream_t s, hipEvent_t stop, const X&... x) {
-  launch_kb(kernel, grid, dim3(64), s, stop, x...);
-}
-
-// f(std::integral_constant<int, V>) for the V of the list equal to v: one instance parameter of a launch, from its
-// run-time value.  plan_sls only plans instantiated values: one it does not is a planner bug, caught here
-template <int V, int... Vs, class F>
-void with_int(int v, F&& f) {
-  if constexpr (sizeof...(Vs) == 0) {
-    assert(v == V && "plan_sls planned a gather instance that is not instantiated");
-    f(std::integral_constant<int, V>{});
-  } else if (v == V) f(std::integral_constant<int, V>{});
-  else with_int<Vs...>(v, f);
 }
 
 int lanes_per_row(int D) { return D <= 8 ? 2 : D <= 16 ? 4 : D <= 32 ? 8 : D <= 64 ? 16 : D <= 128 ? 32 : 64; }

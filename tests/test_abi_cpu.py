@@ -235,7 +235,7 @@ def test_product_binding_refuses_anything_but_the_hip_build(monkeypatch):
 @pytest.mark.parametrize("kind,over", [
     ("din", dict(arch_sparse_feature_size=10, arch_mlp_bot="8-4")),         # a unit with two hidden layers over 40-byte rows
     ("din", dict(arch_sparse_feature_size=16, arch_mlp_bot="100")),         # a hidden layer wider than 64
-    ("dien", dict(arch_sparse_feature_size=24, hidden_size=100)),           # neither one of din.hip's instances
+    ("dien", dict(arch_sparse_feature_size=24, hidden_size=100)),           # neither one of dien.hip's instances
     ("dlrm", dict(arch_sparse_feature_size=10, arch_mlp_bot="7-12-10", arch_mlp_top="9-1")),
 ])
 def test_boundary_takes_the_shapes_the_reference_takes(cpu_abi, kind, over):

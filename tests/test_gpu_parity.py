@@ -819,7 +819,7 @@ def test_din_fused_and_two_launch_forms_match_oracle(D, h, U, ragged):
 
 @pytest.mark.parametrize("D,Hs,U,init", [(32, 64, 40, "xavier"), (16, 8, 5, "fed"), (64, 32, 9, "xavier"), (32, 16, 3, "xavier")])
 def test_dien_recurrent_layers_match_oracle(D, Hs, U, init):
-    """DIEN's two BasicRNN layers (din.hip) against the oracle: the pass-through features bitwise,
+    """DIEN's two BasicRNN layers (dien.hip) against the oracle: the pass-through features bitwise,
     the recurrent state within the tanhf tolerance; query sizes 1 .. B (the reference's Reshape makes
     a sample's sequence depend on its query's batch size), ragged bags, 8 coalesced queries of
     different sizes equal to the same queries served alone."""
@@ -938,15 +938,15 @@ def test_din_attention_units_of_any_shape_match_oracle(D, bot, U):
         eng.close()
 
 
-@pytest.mark.parametrize("D,Hs,U", [(32, 100, 7),      # hidden size beyond din.hip's 64
-                                    (24, 40, 5),        # neither is one of din.hip's instances
+@pytest.mark.parametrize("D,Hs,U", [(32, 100, 7),      # hidden size beyond dien.hip's 64
+                                    (24, 40, 5),        # neither is one of dien.hip's instances
                                     (10, 7, 4),         # rows that are not 16-byte pieces, odd hidden size
                                     (64, 128, 6),       # a multiple of 16 the matrix-core form has no instance for
                                     (300, 20, 3),       # rows wider than 256 columns
                                     (16, 600, 3)])      # more hidden units than a workgroup has threads
 def test_dien_recurrence_of_any_shape_matches_oracle(D, Hs, U):
     """rnn_cell.BasicRNN(arch_sparse_feature_size -> hidden_size) for any two integers (models/dien.py:308-380): the
-    pairs din.hip has no instance for take dien_rnn_any_kernel (din_any.hip).  Pass-through features bitwise, the
+    pairs dien.hip has no instance for take dien_rnn_any_kernel (din_any.hip).  Pass-through features bitwise, the
     recurrent state within the tanh tolerance of test_dien_recurrent_layers_match_oracle; query sizes 1 .. B (the
     Reshape makes a sample's sequence depend on its query's size), ragged bags, coalesced = alone."""
     rng = np.random.RandomState(D + Hs + U)
