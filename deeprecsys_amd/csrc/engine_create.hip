@@ -18,6 +18,7 @@ hipError_t device_init(int device, const float** zero_page) {
     if (e == hipSuccess) e = mlp_set_attrs();
     if (e == hipSuccess) e = gemm_set_attrs();
     if (e == hipSuccess) e = gemm_bf16_set_attrs();
+    if (e == hipSuccess) e = fused_bf16_set_attrs();
     if (e == hipSuccess && !zero[device]) {
       e = hipMalloc(reinterpret_cast<void**>(&zero[device]), 256);
       if (e == hipSuccess) e = hipMemset(zero[device], 0, 256);

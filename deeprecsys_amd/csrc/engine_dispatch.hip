@@ -20,7 +20,8 @@ bool is_wide(const drs_engine* e, const Mlp& m, int l) {
   return e->mlp_split && (int64_t)m.ln[l] * m.ln[l + 1] >= e->mlp_wide_kn;
 }
 
-// "mlp_dtype" 2: layer l of m runs on the bf16 matrix cores, always as a launch of its own (gemm_bf16.hip)
+// "mlp_dtype" 2: layer l of m runs on the bf16 matrix cores -- as a launch of its own (gemm_bf16.hip), or inside DLRM's
+// one-launch form ("mlp_bf16_fuse" 1, fused_bf16_plan)
 bool is_bf16(const drs_engine* e, const Mlp& m, int l) { return bf16_shape(e, m.ln[l], m.ln[l + 1]); }
 
 void fill_chain(ChainArgs& c, const Mlp& m, int l0, int cnt, const float* x, int64_t ldx, int64_t M,
@@ -122,6 +123,35 @@ bool fused_plan(const drs_engine* e, const Slot& s, int64_t Mv, float* out, cons
   fill_chain(b, e->top, 0, nt, s.R, e->ldR, Mv, out, e->n_out);
   const DotArgs dot = {s.T, e->ldT, e->T + 1, e->D, e->itself, s.R, e->ldR};
   return plan_chains(a, &b, e->tune, dp, xs, &dot, nullptr, p);
+}
+
+// "mlp_bf16_fuse" 1 with "mlp_dtype" 2: the same launch set under fused_plan's conditions (fusing on, enough rows, no wide
+// layer, chains of at most DRS_MAX_CHAIN layers, slabs that fit LDS), its bf16 layers included: fused_bf16_kernel.
+// false: the set runs as without the option.
+bool fused_bf16_plan(const drs_engine* e, const Slot& s, int64_t Mv, float* out, const Done* dp, const XSrc* xs, MlpPlan* p) {
+  if (!e->mlp_bf16_fuse || e->mlp_dtype != DRS_MLP_BF16) return false;
+  if (!e->mlp_fuse || Mv < e->mlp_fuse_rows || e->kind != DRS_MODEL_DLRM) return false;
+  const int nb = (int)e->bot.layers.size(), nt = (int)e->top.layers.size();
+  if (nb < 1 || nt < 1 || nb > DRS_MAX_CHAIN || nt > DRS_MAX_CHAIN) return false;
+  const uint16_t* wb_a[DRS_MAX_CHAIN] = {};
+  const uint16_t* wb_b[DRS_MAX_CHAIN] = {};
+  for (int l = 0; l < nb; ++l) {
+    if (is_wide(e, e->bot, l)) return false;
+    if (is_bf16(e, e->bot, l) && !(wb_a[l] = e->bot.layers[l].Wb)) return false;
+  }
+  for (int l = 0; l < nt; ++l) {
+    if (is_wide(e, e->top, l)) return false;
+    if (is_bf16(e, e->top, l) && !(wb_b[l] = e->top.layers[l].Wb)) return false;
+  }
+  ChainArgs a, b;
+  fill_chain(a, e->bot, 0, nb, nullptr, e->m_den, Mv, s.T, e->ldT);
+  if (e->interaction_op == DRS_INTERACT_CAT) {
+    fill_chain(b, e->top, 0, nt, s.T, e->ldT, Mv, out, e->n_out);
+    return plan_fused_bf16(a, b, wb_a, wb_b, nullptr, dp, xs, p);
+  }
+  fill_chain(b, e->top, 0, nt, s.R, e->ldR, Mv, out, e->n_out);
+  const DotArgs dot = {s.T, e->ldT, e->T + 1, e->D, e->itself, s.R, e->ldR};
+  return plan_fused_bf16(a, b, wb_a, wb_b, &dot, dp, xs, p);
 }
 
 // shared_stream: 1 = one stream for everything (launch sets strictly back to back);
@@ -474,7 +504,7 @@ static int32_t mlp_dense(SetCtx& x) {
       log_launch(e->tune.log, "early");
     }
 #endif
-    fused = fused || fused_plan(e, s, Mv, out, x.dp, &x.xs, &p);
+    fused = fused || fused_plan(e, s, Mv, out, x.dp, &x.xs, &p) || fused_bf16_plan(e, s, Mv, out, x.dp, &x.xs, &p);
     if (fused) {
       HIP_TRY(e, x.join());
       HIP_TRY(e, launch_plan(p, e->tune, s.stream));

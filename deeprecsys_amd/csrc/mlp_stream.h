@@ -94,6 +94,36 @@ struct NSplit {
 
 static_assert(sizeof(SArgs) + sizeof(Done) + sizeof(XSrc) <= 4096, "kernel arguments: 4 KB");
 
+// fused_bf16_kernel (mlp_fused_bf16.hip, "mlp_bf16_fuse" 1): DLRM's bottom chain, interaction and top chain of a 16-row
+// slab in one launch, the bf16 layers of "mlp_dtype" 2 on the bf16 matrix cores.  LDS offsets and leading dimensions in
+// floats; every slab is 16 rows.
+struct FLayer {
+  const float* W;          // [N, K] row-major (fp32 layer)
+  const uint16_t* Wb;      // the bf16 twin [N, bf16_kpad(K)]: a bf16 layer; nullptr: an fp32 layer
+  const float* b;          // [N] or nullptr
+  int32_t K, N, act;
+  int32_t in_off, in_ld;   // input slab
+  int32_t out_off, out_ld; // output slab (out_off < 0: none)
+  int32_t out_pad;         // columns [N, out_pad) of the output slab are zero filled
+  int32_t g_sc1;           // write-through stores (final outputs handed over by signal_done)
+  float* g_out;            // global output or nullptr
+  int64_t g_ld;
+};
+struct FArgs {
+  int32_t n_layers, n_bot, n_bf16;   // layers of both chains | of the bottom chain | bf16 layers among them
+  int32_t vec_x, vec_t;              // 16-byte loads of the dense rows | of the pooled rows
+  int32_t k0, x0_off, x0_ld;         // dense rows: width, slab X0
+  int64_t M, ldx;                    // virtual rows of the launch; floats between two dense rows of a query
+  const float* T;                    // the gather's output: pooled rows in columns [p_col0, p_col0 + p_cols), ld = ldt
+  int64_t ldt;
+  int32_t p_col0, p_cols, p_cols_pad, rs_off, rs_ld;   // ... staged into slab RS at the same columns, zeros up to p_cols_pad
+  int32_t dot, F, D, itself, ri_off, ri_ld;            // dot interaction: RS [F x D per row] -> slab RI [D + P per row] ...
+  float* R;                                            // ... and R (drs_fetch_interaction), ld = ldr
+  int64_t ldr;
+  FLayer L[DRS_MAX_STREAM_LAYERS];
+};
+static_assert(sizeof(FArgs) + sizeof(Done) + sizeof(XSrc) <= 4096, "kernel arguments: 4 KB");
+
 #define S3_LAST (1 << 16)
 #define S3_BARRIER (1 << 17)
 #define S3_INTERACT (1 << 18)
@@ -113,7 +143,8 @@ enum class MlpForm : int32_t {
   stream_packed, stream_packed_2cu, stream_lds,      // stream_kernel (mlp_stream8.hip)
   chain, fc,                                         // chain_kernel, fc_kernel (mlp.hip)
   gemm, gemm_2cu, gemm32, gemm32_sbase, gemm32_split,// gemm_kernel, gemm32_kernel (gemm.hip)
-  gemm_bf16                                          // gemm_bf16_kernel (gemm_bf16.hip): a bf16 layer ("mlp_dtype" 2)
+  gemm_bf16,                                         // gemm_bf16_kernel (gemm_bf16.hip): a bf16 layer ("mlp_dtype" 2)
+  fused_bf16                                         // fused_bf16_kernel (mlp_fused_bf16.hip): DLRM in one launch with its bf16 layers ("mlp_bf16_fuse" 1)
 };
 // One MLP launch, decided once (mlp.hip plan_chains / plan_layer) and run as it stands (launch_plan).
 struct MlpPlan {
@@ -128,6 +159,7 @@ struct MlpPlan {
   const uint16_t* wb;           // gemm_bf16: the layer's bf16 twin [N, bf16_kpad(K)]
   SArgs sa;                     // stream forms
   NSplit ns;
+  FArgs fa;                     // fused_bf16
 };
 // may the launch start before the gather is done (Done::wait_flag)?  Only the 16-row one-workgroup-per-CU stream4_kernel
 // has the late fetch of the second chain's input: the 2cu / 32-row builds have no registers to spare for it
@@ -146,6 +178,11 @@ bool gemm_plan(const Tune& tune, MlpPlan* p);   // gemm.hip: the GEMM form of th
 hipError_t launch_gemm(const MlpPlan& p, const float* zero, hipStream_t s);
 bool gemm_bf16_plan(const Tune& tune, MlpPlan* p);   // gemm_bf16.hip: the bf16 GEMM form of the layer p->a with the twin p->wb
 hipError_t launch_gemm_bf16(const MlpPlan& p, hipStream_t s);
+// mlp_fused_bf16.hip: bottom chain a, the interaction (dot, or null: cat) and top chain b in fused_bf16_kernel; wb_a / wb_b:
+// per layer its bf16 twin (a bf16 layer) or null (an fp32 layer).  false: the form does not take the launch.
+bool plan_fused_bf16(const ChainArgs& a, const ChainArgs& b, const uint16_t* const* wb_a, const uint16_t* const* wb_b,
+                     const DotArgs* dot, const Done* done, const XSrc* xs, MlpPlan* p);
+hipError_t launch_fused_bf16(const MlpPlan& p, hipStream_t s);
 
 hipError_t launch_stream8(const MlpPlan& p, size_t lds, hipStream_t s);
 hipError_t stream8_set_attrs();

@@ -57,6 +57,14 @@ def _mlp_dtype(args):
     return _MLP_DTYPES[name]
 
 
+def _mlp_bf16_fuse(args):
+    """--accel_mlp_bf16_fuse -> the engine's "mlp_bf16_fuse" value (0 when the flag is absent)."""
+    v = int(getattr(args, "accel_mlp_bf16_fuse", 0) or 0)
+    if v not in (0, 1):
+        raise ValueError("--accel_mlp_bf16_fuse %r: 0 or 1" % (v,))
+    return v
+
+
 def _init_table(n, m):
     # models/dlrm_s_caffe2.py:297-299
     return np.random.uniform(low=-np.sqrt(1 / n), high=np.sqrt(1 / n), size=(n, m)).astype(np.float32)
@@ -109,6 +117,7 @@ class _HipNet(object):
         max_batch = max(int(getattr(a, "max_mini_batch_size", 1)), int(getattr(a, "mini_batch_size", 1)), 1)
         dtype = _table_dtype(a)
         mlp_dtype = _mlp_dtype(a)
+        bf16_fuse = _mlp_bf16_fuse(a)
         def make(n_slots):
             eng = N.Engine(self.kind, self.ln_emb, self.m_spa, ln_bot_cfg, ln_top_cfg,
                            interaction_op=interaction_op, interaction_itself=itself,
@@ -125,6 +134,9 @@ class _HipNet(object):
             # engine is never told)
             if mlp_dtype != N.MLP_FP32:
                 eng.set_option("mlp_dtype", mlp_dtype)
+            # --accel_mlp_bf16_fuse: behind it, and only when asked for
+            if bf16_fuse:
+                eng.set_option("mlp_bf16_fuse", bf16_fuse)
             return eng
         eng = make(self._num_slots())
         if int(getattr(a, "accel_slots", 0) or 0) <= 0 and eng.get_option("preferred_slots") != eng.num_slots:
