@@ -95,7 +95,7 @@ hipError_t device_init(int device, const float** zero_page);
 hipError_t mlp_set_attrs();    // mlp.hip's kernels, on the current device
 hipError_t gemm_set_attrs();   // gemm.hip's kernels, on the current device
 hipError_t gemm_bf16_set_attrs();   // gemm_bf16.hip's kernels, on the current device
-hipError_t fused_bf16_set_attrs();  // mlp_fused_bf16.hip's kernel, on the current device
+hipError_t fused_bf16_set_attrs();  // mlp_fused_bf16.hip's kernels, on the current device
 
 // One gather launch, decided once by plan_sls and run by launch_sls (sls.hip).  Host-only.
 //   form: any (any row width) | ring (sls_kernel) | one (one lookup per bag) | flat | flatc (fixed-length bags)

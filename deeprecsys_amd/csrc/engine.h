@@ -181,7 +181,7 @@ struct drs_engine {
   std::vector<hipMemGenericAllocationHandle_t> spacers;   // "table_spacer": device memory taken (never mapped) between placement candidates
   size_t tables_bytes = 0;
   int mlp_dtype = DRS_MLP_FP32;     // "mlp_dtype": DRS_MLP_BF16 -- the FC layers with K >= 64 and N >= 64 on the bf16 matrix cores (bf16_layer)
-  int mlp_bf16_fuse = 0;            // "mlp_bf16_fuse": with "mlp_dtype" 2, DLRM's one-launch form keeps its bf16 layers (mlp_fused_bf16.hip)
+  int mlp_bf16_fuse = 0;            // "mlp_bf16_fuse": with "mlp_dtype" 2, DLRM's and NCF's one-launch forms keep their bf16 layers (mlp_fused_bf16.hip)
   int table_dtype = DRS_TABLE_FP32; // "table_dtype": element type of the arena (DRS_TABLE_*); sums and outputs stay fp32
   // how the NEXT arena is built (drs_create's first one, "table_placement" -1 candidates)
   int table_alloc = 0;              // 0 hipMalloc | 1 virtual-memory API

@@ -21,7 +21,7 @@ bool is_wide(const drs_engine* e, const Mlp& m, int l) {
 }
 
 // "mlp_dtype" 2: layer l of m runs on the bf16 matrix cores -- as a launch of its own (gemm_bf16.hip), or inside DLRM's
-// one-launch form ("mlp_bf16_fuse" 1, fused_bf16_plan)
+// or NCF's one-launch form ("mlp_bf16_fuse" 1: fused_bf16_plan, ncf_bf16_plan)
 bool is_bf16(const drs_engine* e, const Mlp& m, int l) { return bf16_shape(e, m.ln[l], m.ln[l + 1]); }
 
 void fill_chain(ChainArgs& c, const Mlp& m, int l0, int cnt, const float* x, int64_t ldx, int64_t M,
@@ -152,6 +152,24 @@ bool fused_bf16_plan(const drs_engine* e, const Slot& s, int64_t Mv, float* out,
   fill_chain(b, e->top, 0, nt, s.R, e->ldR, Mv, out, e->n_out);
   const DotArgs dot = {s.T, e->ldT, e->T + 1, e->D, e->itself, s.R, e->ldR};
   return plan_fused_bf16(a, b, wb_a, wb_b, &dot, dp, xs, p);
+}
+
+// "mlp_bf16_fuse" 1 with "mlp_dtype" 2, NCF: Sum, MLP branch (ca) and predictor (cb) stay ONE launch where only their bf16
+// layers keep them from the fp32 one-launch form (mlp_ncf): no wide layer, every bf16 layer with its twin, slabs that fit
+// LDS: fused_bf16_sum_kernel.  false: the set runs as without the option.
+bool ncf_bf16_plan(const drs_engine* e, const ChainArgs& ca, const ChainArgs& cb, const SumArgs& sum, const Done* dp, MlpPlan* p) {
+  if (!e->mlp_bf16_fuse || e->mlp_dtype != DRS_MLP_BF16) return false;
+  const int nt = (int)e->top.layers.size();
+  if (!e->mlp_fuse || nt < 1 || nt > DRS_MAX_CHAIN || e->fin.layers.size() != 1) return false;
+  const uint16_t* wb_a[DRS_MAX_CHAIN] = {};
+  const uint16_t* wb_b = nullptr;
+  for (int l = 0; l < nt; ++l) {
+    if (is_wide(e, e->top, l)) return false;
+    if (is_bf16(e, e->top, l) && !(wb_a[l] = e->top.layers[l].Wb)) return false;
+  }
+  if (is_wide(e, e->fin, 0)) return false;
+  if (is_bf16(e, e->fin, 0) && !(wb_b = e->fin.layers[0].Wb)) return false;
+  return plan_fused_bf16_sum(ca, cb, wb_a, wb_b, sum, dp, p);
 }
 
 // shared_stream: 1 = one stream for everything (launch sets strictly back to back);
@@ -456,7 +474,8 @@ static int32_t mlp_ncf(SetCtx& x) {
     bool wide = is_wide(e, e->fin, 0) || is_bf16(e, e->fin, 0);
     for (int l = 0; l < nt; ++l) wide = wide || is_wide(e, e->top, l) || is_bf16(e, e->top, l);
     MlpPlan p;
-    if (!wide && plan_chains(ca, &cb, e->tune, x.dp, nullptr, nullptr, &sum, &p)) {
+    // (... or, with "mlp_bf16_fuse" 1, in fused_bf16_sum_kernel when some of the layers are bf16 layers)
+    if ((!wide && plan_chains(ca, &cb, e->tune, x.dp, nullptr, nullptr, &sum, &p)) || ncf_bf16_plan(e, ca, cb, sum, x.dp, &p)) {
       HIP_TRY(e, launch_plan(p, e->tune, s.stream));
       return DRS_OK;
     }

@@ -204,7 +204,8 @@ const OptDesc kOptions[] = {
     OPT("mlp_gemm_tile", 0, 322, [](int64_t v) { return v == 0 || v == 22 || v == 12 || v == 21 || v == 11 || v == 214 || v == 322 || v == 321 || v == 312 || v == 311; }, 0, tune.gemm_tile),
     // DRS_MLP_BF16: the FC layers with K >= 64 and N >= 64 on the bf16 matrix cores (gemm_bf16.hip); "mlp_bf16_tile": force a tile shape
     {"mlp_dtype", 0, 2, [](int64_t v) { return v == DRS_MLP_FP32 || v == DRS_MLP_BF16; }, O_SYNC, [](drs_engine* e) -> int64_t { return e->mlp_dtype; }, nullptr, set_mlp_dtype},
-    // ... and DLRM's bottom MLP + interaction + top MLP stay ONE launch with their bf16 layers inside it (mlp_fused_bf16.hip)
+    // ... and DLRM's bottom MLP + interaction + top MLP, or NCF's Sum + MLP branch + predictor, stay ONE launch with their
+    // bf16 layers inside it (mlp_fused_bf16.hip)
     OPT("mlp_bf16_fuse", 0, 1, nullptr, 0, mlp_bf16_fuse),
     OPT("mlp_bf16_tile", 0, 44, [](int64_t v) { return v == 0 || v == 44 || v == 22 || v == 12; }, 0, tune.bf16_tile),
     // streams, host side

@@ -954,7 +954,7 @@ hipError_t launch_plan(const MlpPlan& p, const Tune& tune, hipStream_t s) {
       "stream4_kernel", "stream4_kernel<sum>", "stream4_kernel<2cu>", "stream4_kernel<rows32>", "stream4_kernel<nsplit2>",
       "stream4_kernel<nsplit4>", "stream4_kernel<rows32,nsplit2>", "stream4_kernel<rows32,nsplit4>", "stream_kernel<packed>",
       "stream_kernel<packed,2cu>", "stream_kernel<lds>", "chain_kernel", "fc_kernel", "gemm_kernel", "gemm_kernel",
-      "gemm32_kernel", "gemm32_kernel", "gemm32_kernel", "gemm_bf16_kernel", "fused_bf16_kernel"};
+      "gemm32_kernel", "gemm32_kernel", "gemm32_kernel", "gemm_bf16_kernel", "fused_bf16_kernel", "fused_bf16_kernel<sum>"};
   const char* name = names[(int)p.form];
   const size_t lds = launch_lds(p);
   const int K = p.a.width[0], N = p.a.width[1];
@@ -965,7 +965,7 @@ hipError_t launch_plan(const MlpPlan& p, const Tune& tune, hipStream_t s) {
     log_launch(tune.log, "%s<%s,%d>[%u wg, %d layers]", name, p.vec ? "vec" : "scalar", p.kc, p.grid_x, p.a.n_layers + p.b.n_layers);
   else if (p.form == MlpForm::fc)
     log_launch(tune.log, "%s<%s,%d>[%u x %u wg, %dx%d]", name, p.vec ? "vec" : "scalar", p.kc, p.grid_x, p.grid_y, K, N);
-  else if (p.form == MlpForm::fused_bf16)
+  else if (p.form == MlpForm::fused_bf16 || p.form == MlpForm::fused_bf16_sum)
     log_launch(tune.log, "%s[%u wg, %d layers, %d bf16%s, %zu B lds]", name, p.grid_x, p.fa.n_layers, p.fa.n_bf16, p.fa.dot ? ", dot" : "", lds);
   else if (p.form == MlpForm::gemm_bf16)
     log_launch(tune.log, "%s<%dx%d%s>[%u x %u wg, %dx%d]", name, 32 * p.tm, 32 * p.tn, p.vec ? "" : ",scalar", p.grid_x, p.grid_y, K, N);
@@ -1006,7 +1006,7 @@ hipError_t launch_plan(const MlpPlan& p, const Tune& tune, hipStream_t s) {
       return launch_gemm(p, tune.zero, s);
     case MlpForm::gemm_bf16:
       return launch_gemm_bf16(p, s);
-    case MlpForm::fused_bf16:
+    case MlpForm::fused_bf16: case MlpForm::fused_bf16_sum:
       return launch_fused_bf16(p, s);
     case MlpForm::stream_packed: case MlpForm::stream_packed_2cu: case MlpForm::stream_lds:
       return launch_stream8(p, lds, s);

@@ -22,6 +22,11 @@
 // once and 8 twice; MI355X LDS, 64 x 4 B banks): X0 (dense rows) | RS (dense_out | pooled rows: the cat top input or the
 // dot interaction's T slab) | RI (dot: the top input) | P | Q (ping-pong layer outputs).  A layer zero-fills its output
 // columns up to the next multiple of 64, so a bf16 layer's padded k reads zeros.
+//
+// NCF's one-launch form (Sum + MLP branch + predictor; stream_kernel<packed>'s SumArgs form in fp32) is a kernel of its
+// own, fused_bf16_sum_kernel, from the same passes: no dense rows and no XSrc -- X0 is Concat(emb2, emb3) out of T, RS is
+// the predictor's input [ mf = emb0 + emb1 | the branch's output ], i.e. the chain's output goes BEHIND the staged block
+// (column D), not in front of it; both halves are also left in the engine's buffer (drs_fetch_interaction).
 #include <string.h>
 
 #include "mlp_stream.h"
@@ -47,6 +52,14 @@ __device__ __forceinline__ bf16x8 to_bf16x8(const float4 lo, const float4 hi) {
 __device__ __forceinline__ void store_out(float* dst, float v, bool sc1) {
   if (sc1) __hip_atomic_store(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // write-through: signal_done reads it back
   else *dst = v;
+}
+
+// ... four consecutive outputs, dst 16-byte aligned.  (s_nop 1: two wait states between a store of more than 64 bits and
+// a VALU write of its data registers, which the compiler does not see inside the statement: signal_done, mlp_dev.h)
+__device__ __forceinline__ void store_out4(float* dst, const float (&v)[4], bool sc1) {
+  const f32x4 x = {v[0], v[1], v[2], v[3]};
+  if (sc1) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(x) : "memory");
+  else *reinterpret_cast<f32x4*>(dst) = x;
 }
 
 // 16 rows x cols of a global matrix -> an LDS slab, zeros in columns [cols, cols_pad).  Row i comes from row
@@ -85,6 +98,11 @@ __device__ __forceinline__ void stage_rows(const float* __restrict__ base, int64
 // A bf16 layer.  Wave w owns the 16-column tiles w, w + FW, ...; two of them at a time share the converted slab operand.
 // Lane (r, g): A operand = bf16 k = 32 s + 8 g .. + 7 of weight row 16 t + r, B operand = the same k of slab row r;
 // accumulator register q = output row r, column 16 t + 4 g + q (gemm_bf16_kernel's roles).
+// SUM (fused_bf16_sum_kernel's build): the output slab may start at any column (NCF's branch output behind D columns of
+// mf): 16-byte LDS stores only where they are aligned; and a lane's four outputs of a row go out as ONE 16-byte store
+// where the rows allow it (NCF's predictor hands 64 floats per row over, not one: as 4-byte write-through stores, four
+// lanes of a row apart, they were a quarter of a 64-byte line per instruction).
+template <bool SUM>
 __device__ __forceinline__ void bf16_pass(const FLayer& L, float* lds, int m0, int M, int wave, int lane) {
   const int r = lane & 15, g = lane >> 4;
   const int K = L.K, N = L.N;
@@ -95,6 +113,8 @@ __device__ __forceinline__ void bf16_pass(const FLayer& L, float* lds, int m0, i
   float* const o_lds = L.out_off >= 0 ? lds + L.out_off + r * L.out_ld : nullptr;
   float* const o_glb = L.g_out && m0 + r < M ? L.g_out + (int64_t)(m0 + r) * L.g_ld : nullptr;
   const bool sc1 = L.g_sc1 != 0;
+  const bool st4 = !SUM || !(L.out_off & 3);
+  const bool g4 = SUM && !(reinterpret_cast<uintptr_t>(L.g_out) & 15) && !(L.g_ld & 3);
 
   auto epilogue = [&](int t, const f32x4 acc) {
     const int col = 16 * t + 4 * g;
@@ -106,7 +126,7 @@ __device__ __forceinline__ void bf16_pass(const FLayer& L, float* lds, int m0, i
       v[q] = cq < N ? act_apply(acc[q] + bq, L.act) : 0.f;
     }
     if (o_lds) {
-      if (col + 3 < L.out_pad) {
+      if (st4 && col + 3 < L.out_pad) {
         *reinterpret_cast<float4*>(o_lds + col) = make_float4(v[0], v[1], v[2], v[3]);
       } else {
 #pragma unroll
@@ -114,8 +134,12 @@ __device__ __forceinline__ void bf16_pass(const FLayer& L, float* lds, int m0, i
       }
     }
     if (o_glb) {
+      if (g4 && col + 3 < N) {
+        store_out4(o_glb + col, v, sc1);
+      } else {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) if (col + q < N) store_out(o_glb + col + q, v[q], sc1);
+        for (int q = 0; q < 4; ++q) if (col + q < N) store_out(o_glb + col + q, v[q], sc1);
+      }
     }
   };
 
@@ -251,7 +275,7 @@ __global__ __launch_bounds__(kFThreads) void fused_bf16_kernel(FArgs a, Done don
 
   for (int l = 0; l < a.n_layers; ++l) {
     const FLayer& L = a.L[l];
-    if (L.Wb) bf16_pass(L, smem, m0, M, wave, lane);
+    if (L.Wb) bf16_pass<false>(L, smem, m0, M, wave, lane);
     else fp32_pass(L, smem, m0, M, wave, lane);
     __syncthreads();
     // (the loop counter through an opaque move: what the interaction needs is then worked out where it runs, once, and
@@ -282,13 +306,98 @@ __global__ __launch_bounds__(kFThreads) void fused_bf16_kernel(FArgs a, Done don
   signal_done(done, gridDim.x, smem);
 }
 
+// NCF's Sum: columns [0, D) of 16 rows of T + columns [col_b, col_b + D) -> slab columns [0, D) and R's.  One fp32 add
+// per element, operands in this order (add_rows_kernel, the stream kernels' SumArgs).  VEC: D % 4 == 0, T rows 16-byte
+// aligned; VEC_R: R's rows too.
+template <bool VEC>
+__device__ __forceinline__ void sum_rows(const float* __restrict__ T, int64_t ldt, int m0, int M, int col_b, int D,
+                                         float* dst, int dst_ld, float* __restrict__ R, int64_t ldr, bool vec_r) {
+  constexpr int V = VEC ? 4 : 1;
+  const int ppr = D / V, total = 16 * ppr;
+  for (int i = threadIdx.x; i < total; i += kFThreads) {
+    const int row = i / ppr, c = (i - row * ppr) * V;
+    const float* q = T + (int64_t)(m0 + row < M ? m0 + row : M - 1) * ldt + c;
+    float* d = dst + row * dst_ld + c;
+    float* g = m0 + row < M ? R + (int64_t)(m0 + row) * ldr + c : nullptr;
+    if (VEC) {
+      const float4 x = *reinterpret_cast<const float4*>(q), y = *reinterpret_cast<const float4*>(q + col_b);
+      const float4 v = make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w);
+      *reinterpret_cast<float4*>(d) = v;
+      if (g) {
+        if (vec_r) *reinterpret_cast<float4*>(g) = v;
+        else { g[0] = v.x; g[1] = v.y; g[2] = v.z; g[3] = v.w; }
+      }
+    } else {
+      const float v = q[0] + q[col_b];
+      *d = v;
+      if (g) *g = v;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kFThreads) void fused_bf16_sum_kernel(FArgs a, Done done) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int m0 = (int)blockIdx.x * 16, M = (int)a.M;
+
+  // L2 warm-up: fused_bf16_kernel's
+  float warm[2][4];
+  {
+    const int64_t part = ((blockIdx.x >> 3) & 15) + 16 * (int64_t)(blockIdx.x >> 7);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int l = wave + FW * h;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) warm[h][j] = 0.f;
+      if (l < a.n_layers) {                                        // wave-uniform
+        const FLayer& L = a.L[l];
+        const int64_t bytes = L.Wb ? (int64_t)L.N * ((L.K + 63) & ~63) * 2 : (int64_t)L.N * L.K * 4;
+        const int64_t lines = (bytes + 127) >> 7;
+        const char* p = L.Wb ? reinterpret_cast<const char*>(L.Wb) : reinterpret_cast<const char*>(L.W);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          warm[h][j] = *reinterpret_cast<const float*>(p + min(lines - 1, (part * 64 + lane) * 4 + j) * 128);
+      }
+    }
+  }
+
+  // inputs, all from the pooled rows the gather left in T: the branch's Concat and the Sum
+  {
+    const int k0_pad = (a.k0 + 63) & ~63;
+    if (a.vec_t) {
+      stage_rows<true>(a.T, a.ldt, m0, M, a.p_col0, a.k0, k0_pad, smem + a.x0_off, a.x0_ld, 0);
+      sum_rows<true>(a.T, a.ldt, m0, M, a.p_cols, a.D, smem + a.rs_off, a.rs_ld, a.R, a.ldr, a.vec_x != 0);
+    } else {
+      stage_rows<false>(a.T, a.ldt, m0, M, a.p_col0, a.k0, k0_pad, smem + a.x0_off, a.x0_ld, 0);
+      sum_rows<false>(a.T, a.ldt, m0, M, a.p_cols, a.D, smem + a.rs_off, a.rs_ld, a.R, a.ldr, false);
+    }
+  }
+  __syncthreads();
+
+  for (int l = 0; l < a.n_layers; ++l) {
+    const FLayer& L = a.L[l];
+    if (L.Wb) bf16_pass<true>(L, smem, m0, M, wave, lane);
+    else fp32_pass(L, smem, m0, M, wave, lane);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(warm[h][j]));
+  signal_done(done, gridDim.x, smem);
+}
+
 inline int pad64(int n) { return (n + 63) & ~63; }
 inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 }  // namespace
 
 // per device (device_init)
-hipError_t fused_bf16_set_attrs() { return set_max_lds(fused_bf16_kernel); }
+hipError_t fused_bf16_set_attrs() {
+  const hipError_t e = set_max_lds(fused_bf16_kernel);
+  return e != hipSuccess ? e : set_max_lds(fused_bf16_sum_kernel);
+}
 
 // Lay the bottom chain a, the interaction and the top chain b out for fused_bf16_kernel.  wb_a / wb_b: per layer its bf16
 // twin, or null for an fp32 layer.  false: the form does not take the launch (no bf16 layer, a launch that waits for the
@@ -373,8 +482,76 @@ bool plan_fused_bf16(const ChainArgs& a, const ChainArgs& b, const uint16_t* con
   return true;
 }
 
+// NCF: the MLP branch a (its input: columns of sum.src, the gather's output, behind the two summed blocks), the Sum and
+// the one-layer predictor b for fused_bf16_sum_kernel.  wb_a / wb_b as above.  false: the form does not take the launch
+// (no bf16 layer, a launch that waits for the gather by itself, buffers that are not laid out as NCF's, slabs beyond
+// LDS).  Any D, K and N otherwise.
+bool plan_fused_bf16_sum(const ChainArgs& a, const ChainArgs& b, const uint16_t* const* wb_a, const uint16_t* wb_b,
+                         const SumArgs& sum, const Done* done, MlpPlan* p) {
+  memset(p, 0, sizeof *p);
+  if (done) p->done = *done;
+  if (p->done.wait_flag) return false;
+  p->a = a; p->b = b;
+  const int na = a.n_layers, D = sum.cols;
+  if (na < 1 || na > DRS_MAX_CHAIN || b.n_layers != 1 || D < 1 || a.M < 1) return false;
+  const int wl = a.width[na];
+  const int64_t col_x = a.x - sum.src;
+  // T = [ emb0 | emb1 | ... branch input ... ], R = [ mf | branch output ] = the predictor's input
+  if (sum.col_a != 0 || sum.col_b < D || col_x < (int64_t)sum.col_b + D || col_x + a.width[0] > sum.ld || a.ldx != sum.ld ||
+      a.y != sum.dst + D || a.ldy != sum.ldd || b.x != sum.dst || b.ldx != sum.ldd || b.width[0] != D + wl || D + wl > sum.ldd)
+    return false;
+  FArgs& f = p->fa;
+  // LDS (floats): X0 | RS | P | Q
+  int off = 0;
+  f.k0 = a.width[0];
+  f.x0_ld = pad64(f.k0) + 4; f.x0_off = off; off += 16 * f.x0_ld;
+  f.rs_ld = pad64(D + wl) + 4; f.rs_off = off; off += 16 * f.rs_ld;
+  int wP = 0, wQ = 0;
+  for (int l = 0; l + 1 < na; ++l) { int& w = (l & 1) ? wQ : wP; w = pad64(a.width[l + 1]) > w ? pad64(a.width[l + 1]) : w; }
+  const int p_ld = wP + 4, q_ld = wQ + 4;
+  const int p_off = off; off += wP ? 16 * p_ld : 0;
+  const int q_off = off; off += wQ ? 16 * q_ld : 0;
+  if (sizeof(float) * (size_t)off > kFLdsBudget) return false;
+  p->lds = sizeof(float) * (size_t)off;
+
+  int n_bf16 = 0;
+  for (int l = 0; l <= na; ++l) {
+    const bool fin = l == na;
+    const ChainArgs& c = fin ? b : a;
+    const int cl = fin ? 0 : l;
+    FLayer& L = f.L[l];
+    L.W = c.W[cl]; L.Wb = fin ? wb_b : wb_a[l]; L.b = c.b[cl]; L.K = c.width[cl]; L.N = c.width[cl + 1]; L.act = c.act[cl];
+    n_bf16 += L.Wb ? 1 : 0;
+    L.in_off = fin ? f.rs_off : l == 0 ? f.x0_off : ((l - 1) & 1) ? q_off : p_off;
+    L.in_ld = fin ? f.rs_ld : l == 0 ? f.x0_ld : ((l - 1) & 1) ? q_ld : p_ld;
+    L.out_off = -1; L.out_ld = 0; L.out_pad = L.N;
+    if (fin) {
+      L.g_out = b.y; L.g_ld = b.ldy; L.g_sc1 = p->done.counter != nullptr;
+    } else if (l == na - 1) {    // behind mf; a bf16 predictor reads zeros up to its padded K
+      L.out_off = f.rs_off + D; L.out_ld = f.rs_ld; L.out_pad = wb_b ? pad64(D + wl) - D : wl;
+      L.g_out = a.y; L.g_ld = a.ldy;
+    } else {
+      L.out_off = (l & 1) ? q_off : p_off; L.out_ld = (l & 1) ? q_ld : p_ld; L.out_pad = pad64(L.N);
+    }
+  }
+  if (!n_bf16) return false;
+  f.n_layers = na + 1; f.n_bot = na; f.n_bf16 = n_bf16;
+  f.M = a.M;
+  f.T = sum.src; f.ldt = sum.ld; f.p_col0 = (int)col_x; f.p_cols = sum.col_b;
+  f.D = D; f.R = sum.dst; f.ldr = sum.ldd;
+  f.vec_t = al16(sum.src) && !(sum.ld & 3) && !(D & 3) && !(sum.col_b & 3) && !(col_x & 3) && !(f.k0 & 3);
+  f.vec_x = f.vec_t && al16(sum.dst) && !(sum.ldd & 3);
+  p->form = MlpForm::fused_bf16_sum;
+  p->grid_x = (unsigned)((a.M + 15) / 16);
+  p->grid_y = 1;
+  return true;
+}
+
 hipError_t launch_fused_bf16(const MlpPlan& p, hipStream_t s) {
-  hipLaunchKernelGGL(fused_bf16_kernel, dim3(p.grid_x), dim3(kFThreads), p.lds, s, p.fa, p.done, p.xs);
+  if (p.form == MlpForm::fused_bf16_sum)
+    hipLaunchKernelGGL(fused_bf16_sum_kernel, dim3(p.grid_x), dim3(kFThreads), p.lds, s, p.fa, p.done);
+  else
+    hipLaunchKernelGGL(fused_bf16_kernel, dim3(p.grid_x), dim3(kFThreads), p.lds, s, p.fa, p.done, p.xs);
   return hipGetLastError();
 }
 

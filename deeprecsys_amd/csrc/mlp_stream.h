@@ -97,6 +97,11 @@ static_assert(sizeof(SArgs) + sizeof(Done) + sizeof(XSrc) <= 4096, "kernel argum
 // fused_bf16_kernel (mlp_fused_bf16.hip, "mlp_bf16_fuse" 1): DLRM's bottom chain, interaction and top chain of a 16-row
 // slab in one launch, the bf16 layers of "mlp_dtype" 2 on the bf16 matrix cores.  LDS offsets and leading dimensions in
 // floats; every slab is 16 rows.
+// fused_bf16_sum_kernel, NCF's one-launch form (Sum + MLP branch + predictor), takes the same block and reads it as:
+//   k0, x0_*    the branch input: columns [p_col0, p_col0 + k0) of T -> slab X0 from column 0
+//   D, p_cols   mf = T[:, 0:D] + T[:, p_cols:p_cols + D] -> columns [0, D) of slab RS and of R (ld = ldr; vec_x: 16-byte stores)
+//   n_bot       the branch's layers; its last one writes behind mf (slab RS and R from column D), then the predictor reads RS
+//   dot, F, itself, ri_*, p_cols_pad, ldx: unused
 struct FLayer {
   const float* W;          // [N, K] row-major (fp32 layer)
   const uint16_t* Wb;      // the bf16 twin [N, bf16_kpad(K)]: a bf16 layer; nullptr: an fp32 layer
@@ -144,7 +149,8 @@ enum class MlpForm : int32_t {
   chain, fc,                                         // chain_kernel, fc_kernel (mlp.hip)
   gemm, gemm_2cu, gemm32, gemm32_sbase, gemm32_split,// gemm_kernel, gemm32_kernel (gemm.hip)
   gemm_bf16,                                         // gemm_bf16_kernel (gemm_bf16.hip): a bf16 layer ("mlp_dtype" 2)
-  fused_bf16                                         // fused_bf16_kernel (mlp_fused_bf16.hip): DLRM in one launch with its bf16 layers ("mlp_bf16_fuse" 1)
+  fused_bf16,                                        // fused_bf16_kernel (mlp_fused_bf16.hip): DLRM in one launch with its bf16 layers ("mlp_bf16_fuse" 1)
+  fused_bf16_sum                                     // fused_bf16_sum_kernel (mlp_fused_bf16.hip): NCF's Sum + MLP branch + predictor likewise
 };
 // One MLP launch, decided once (mlp.hip plan_chains / plan_layer) and run as it stands (launch_plan).
 struct MlpPlan {
@@ -159,7 +165,7 @@ struct MlpPlan {
   const uint16_t* wb;           // gemm_bf16: the layer's bf16 twin [N, bf16_kpad(K)]
   SArgs sa;                     // stream forms
   NSplit ns;
-  FArgs fa;                     // fused_bf16
+  FArgs fa;                     // fused_bf16, fused_bf16_sum
 };
 // may the launch start before the gather is done (Done::wait_flag)?  Only the 16-row one-workgroup-per-CU stream4_kernel
 // has the late fetch of the second chain's input: the 2cu / 32-row builds have no registers to spare for it
@@ -182,7 +188,10 @@ hipError_t launch_gemm_bf16(const MlpPlan& p, hipStream_t s);
 // per layer its bf16 twin (a bf16 layer) or null (an fp32 layer).  false: the form does not take the launch.
 bool plan_fused_bf16(const ChainArgs& a, const ChainArgs& b, const uint16_t* const* wb_a, const uint16_t* const* wb_b,
                      const DotArgs* dot, const Done* done, const XSrc* xs, MlpPlan* p);
-hipError_t launch_fused_bf16(const MlpPlan& p, hipStream_t s);
+// ... and NCF: the MLP branch a (reading T's columns behind the two summed blocks), sum, the one-layer predictor b
+bool plan_fused_bf16_sum(const ChainArgs& a, const ChainArgs& b, const uint16_t* const* wb_a, const uint16_t* wb_b,
+                         const SumArgs& sum, const Done* done, MlpPlan* p);
+hipError_t launch_fused_bf16(const MlpPlan& p, hipStream_t s);   // (either form)
 
 hipError_t launch_stream8(const MlpPlan& p, size_t lds, hipStream_t s);
 hipError_t stream8_set_attrs();

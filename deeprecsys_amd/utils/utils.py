@@ -71,7 +71,7 @@ EXTRA_FLAGS = [
     ("accel_table_init", _S, "numpy"),  # "numpy": reference RNG stream | "device": counter-based fill
     ("accel_table_dtype", _S, "fp32"),  # element type the accel engines store the tables in: fp32 | fp16 | bf16 | int8_rowwise (sums stay fp32)
     ("accel_mlp_dtype", _S, "fp32"),  # arithmetic of the wide FC layers (K, N >= 64) on the accel engines: fp32 | bf16 (bf16 operands, fp32 accumulation)
-    ("accel_mlp_bf16_fuse", _I, 0),   # 1 with --accel_mlp_dtype bf16: DLRM's bottom MLP + interaction + top MLP stay one launch, the bf16 layers inside it (engine option "mlp_bf16_fuse")
+    ("accel_mlp_bf16_fuse", _I, 0),   # 1 with --accel_mlp_dtype bf16: DLRM's bottom MLP + interaction + top MLP, and NCF's Sum + MLP branch + predictor, stay one launch, the bf16 layers inside it (engine option "mlp_bf16_fuse")
     ("accel_table_placements", _I, 12),  # places in HBM tried for the table arena at engine start (1 = wherever hipMalloc put it)
     ("accel_slots", _I, 0),           # launch sets in flight per accel engine; 0 = the engine's preference (3: gather | MLP | enqueue; MLP-bound models 6)
     ("accel_req_batch", _I, 16),      # requests per put on accelRequestQueue / responses per put back (1 = the reference's one packet per put)

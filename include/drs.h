@@ -295,7 +295,7 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  *                 "mlp_stream" 2|4   "mlp_stream_2cu" 0|1   "mlp_rows32" n
  *                 "mlp_nsplit" 0|2|4   "mlp_nsplit_rows" n   "mlp_gemm_tile" 0|22|12|21|11|214|322|321|312|311
  *                 "mlp_dtype" 0|2 (DRS_MLP_FP32 | DRS_MLP_BF16; DLRM, W&D, MT-WnD and NCF only)   "mlp_bf16_tile" 0|44|22|12
- *                 "mlp_bf16_fuse" 0|1 (1 with "mlp_dtype" 2: DLRM's one-launch form keeps its bf16 layers; same results)
+ *                 "mlp_bf16_fuse" 0|1 (1 with "mlp_dtype" 2: DLRM's and NCF's one-launch forms keep their bf16 layers; same results)
  *   streams, host "shared_stream" 0|1|2   "mlp_streams" 1..8   "host_threads" -1..64
  *                 "zero_copy_inputs" 1|2|3   "out_dma" bytes   "dispatch_log" 0|1
  *   table arena   "table_placement" -1|-2|k   "table_alloc" 0|1|2   "table_spacer" bytes
