@@ -221,12 +221,13 @@ void drs::eng::choose_launch_forms(drs_engine* e) {
   if (e->kind == DRS_MODEL_WND) { e->tune.gemm32_small = 12; e->tune.gemm32_small_blocks = 384; }
 }
 
-size_t drs::eng::table_layout(const drs_engine* e, int dtype, std::vector<int64_t>* off) {
+size_t drs::eng::table_layout(const drs_engine* e, int dtype, std::vector<int64_t>* off, int lines) {
   int64_t o = 0;
+  const int32_t n = dtype == DRS_TABLE_INT8_ROWWISE ? i8_lines(e->D, lines).n : 0;
   off->resize((size_t)e->T);
   for (int t = 0; t < e->T; ++t) {
     (*off)[(size_t)t] = o;
-    o += dtype == DRS_TABLE_INT8_ROWWISE ? round_up(e->rows[t] * table_row_stride(dtype, e->D), 256)   // bytes
+    o += dtype == DRS_TABLE_INT8_ROWWISE ? round_up(i8_table_bytes(e->rows[t], table_row_stride(dtype, e->D), n), 256)   // bytes
                                          : round_up(e->rows[t] * e->D, 64);                             // elements
   }
   return (size_t)o * (size_t)table_unit_bytes(dtype);
@@ -613,7 +614,8 @@ int32_t drs_set_table(drs_handle e, int32_t t, const float* h_W, int64_t rows) {
       const int64_t m = std::min(chunk, rows - i);
       r = hipMemcpy(stage, h_W + i * D, sizeof(float) * (size_t)(m * D), hipMemcpyHostToDevice);
       if (r == hipSuccess)
-        r = dt == DRS_TABLE_INT8_ROWWISE ? launch_convert_rows(stage, DRS_TABLE_FP32, dst + i * table_row_stride(dt, D), dt, m, (int)D, nullptr)
+        // (int8 rowwise: the kernel places rows i .. i + m - 1 of the table itself -- a chunk may start inside a line)
+        r = dt == DRS_TABLE_INT8_ROWWISE ? launch_convert_rows(stage, DRS_TABLE_FP32, dst, dt, m, (int)D, nullptr, 0, e->i8l.n, i, rows)
                                          : launch_convert_table(stage, DRS_TABLE_FP32, dst + i * table_row_stride(dt, D), dt, m * D, nullptr);
       if (r == hipSuccess) r = hipStreamSynchronize(nullptr);    // (before the next chunk overwrites the staging buffer)
     }
@@ -630,7 +632,7 @@ int32_t drs_fill_table_uniform(drs_handle e, int32_t t, float lo, float hi, uint
   if (t < 0 || t >= e->T) return fail(e, DRS_ERR_BAD_ARG, "bad table id");
   if (e->arenas.size() > 1) { if ((rc = drs_sync(e))) return rc; drop_other_placements(e); }
   HIP_TRY(e, launch_fill_uniform_dtype(reinterpret_cast<char*>(e->tables) + e->tab_off[t] * table_unit_bytes(e->table_dtype), e->table_dtype,
-                                       e->rows[t], e->D, t, lo, hi, seed, e->slots[0].stream));
+                                       e->rows[t], e->D, t, lo, hi, seed, e->slots[0].stream, e->i8l.n));
   HIP_TRY(e, hipStreamSynchronize(e->slots[0].stream));
   e->table_set[t] = true;
   return DRS_OK;

@@ -91,25 +91,25 @@ int32_t set_table_spacer(drs_engine* e, int64_t value) {
     return DRS_OK;
 }
 
-int32_t set_table_dtype(drs_engine* e, int64_t value) {
+// "table_dtype" and "table_int8_lines": the arena in use becomes one of element type dt, int8 rows laid out by `lines`
+int32_t convert_tables(drs_engine* e, int dt, int lines) {
   // The tables in use are converted on the device into a new arena of the new element type (round to nearest even;
-  // widening is exact; int8 rowwise: each row quantized, or each row's value written out), which then replaces the old
-  // arena and every other placement candidate.  Refused (DRS_ERR_OOM, nothing changes) when the new arena would not leave
-  // 3/4 of the device's memory free -- the rule of "table_placement" -1.  The launch forms that depend on the gathered
-  // bytes are chosen again (choose_launch_forms): set this one first.
-  if (value == e->table_dtype) return DRS_OK;
-  if (e->kind == DRS_MODEL_DIN || e->kind == DRS_MODEL_DIEN)
-    return fail(e, DRS_ERR_UNSUPPORTED, "table_dtype %lld: DIN and DIEN gather fp32 tables only", (long long)value);
-  const int dt = (int)value, from = e->table_dtype;
+  // widening is exact; int8 rowwise: each row quantized, each row's value written out, or its bytes moved to the other
+  // layout), which then replaces the old arena and every other placement candidate.  Refused (DRS_ERR_OOM, nothing changes)
+  // when the new arena would not leave 3/4 of the device's memory free -- the rule of "table_placement" -1.  The launch
+  // forms that depend on the gathered bytes are chosen again (choose_launch_forms): set these options first.
+  const int from = e->table_dtype;
+  const I8Lines to_l = dt == DRS_TABLE_INT8_ROWWISE ? i8_lines(e->D, lines) : I8Lines(), from_l = e->i8l;
   const bool rowwise = dt == DRS_TABLE_INT8_ROWWISE || from == DRS_TABLE_INT8_ROWWISE;
-  // the gather kernels address a row in 32-bit counts of 4-byte pieces: rows * S / 4 < 2^32 per int8 table
+  // the gather kernels address a row in 32-bit counts of 4-byte pieces: rows * S / 4 < 2^32 per int8 table, or
+  // ceil(rows / n) * 32 < 2^32 when n rows share a line
   if (dt == DRS_TABLE_INT8_ROWWISE)
     for (int t = 0; t < e->T; ++t)
-      if (e->rows[t] * (table_row_stride(dt, e->D) / 4) >= (1ll << 32))
-        return fail(e, DRS_ERR_UNSUPPORTED, "table_dtype 8: table %d (%lld rows of %lld bytes) is too large to address", t,
-                    (long long)e->rows[t], (long long)table_row_stride(dt, e->D));
+      if (i8_table_bytes(e->rows[t], table_row_stride(dt, e->D), to_l.n) / 4 >= (1ll << 32))
+        return fail(e, DRS_ERR_UNSUPPORTED, "table_dtype 8: table %d (%lld rows of %lld bytes%s) is too large to address", t,
+                    (long long)e->rows[t], (long long)table_row_stride(dt, e->D), to_l.n ? ", line-packed" : "");
   std::vector<int64_t> off;
-  const size_t bytes = table_layout(e, dt, &off);
+  const size_t bytes = table_layout(e, dt, &off, lines);
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 4)
     return fail(e, DRS_ERR_OOM, "table_dtype: no room for the converted tables (%zu bytes)", bytes);
@@ -122,7 +122,8 @@ int32_t set_table_dtype(drs_engine* e, int64_t value) {
   } else {
     for (int t = 0; t < e->T && r == hipSuccess; ++t)
       r = launch_convert_rows(reinterpret_cast<const char*>(e->tables) + e->tab_off[t] * table_unit_bytes(from), from,
-                              reinterpret_cast<char*>(fresh.p) + off[t] * table_unit_bytes(dt), dt, e->rows[t], e->D, nullptr);
+                              reinterpret_cast<char*>(fresh.p) + off[t] * table_unit_bytes(dt), dt, e->rows[t], e->D, nullptr,
+                              from_l.n, to_l.n);
   }
   if (r == hipSuccess) r = hipStreamSynchronize(nullptr);
   if (r == hipSuccess && rowwise) r = hipMemcpy(e->d_tab_off, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice);
@@ -139,8 +140,27 @@ int32_t set_table_dtype(drs_engine* e, int64_t value) {
   e->tables_bytes = bytes;
   e->tab_off = off;
   e->table_dtype = dt;
+  e->i8l = to_l;
   choose_launch_forms(e);
   apply_stream_mode(e);
+  return DRS_OK;
+}
+
+int32_t set_table_dtype(drs_engine* e, int64_t value) {
+  if (value == e->table_dtype) return DRS_OK;
+  if (e->kind == DRS_MODEL_DIN || e->kind == DRS_MODEL_DIEN)
+    return fail(e, DRS_ERR_UNSUPPORTED, "table_dtype %lld: DIN and DIEN gather fp32 tables only", (long long)value);
+  return convert_tables(e, (int)value, e->table_int8_lines);
+}
+
+int32_t set_table_int8_lines(drs_engine* e, int64_t value) {
+  // An int8 rowwise arena whose rows the option moves is laid out again (convert_tables: its refusals, and nothing changes
+  // when it fails); any other arena only remembers the value for a later "table_dtype" 8 -- either order, the same arena.
+  if (e->table_dtype == DRS_TABLE_INT8_ROWWISE && i8_lines(e->D, (int)value).n != e->i8l.n) {
+    const int32_t rc = convert_tables(e, e->table_dtype, (int)value);
+    if (rc) return rc;
+  }
+  e->table_int8_lines = (int)value;
   return DRS_OK;
 }
 
@@ -227,6 +247,8 @@ const OptDesc kOptions[] = {
     OPT("table_alloc", 0, 2, nullptr, 0, table_alloc),
 #endif
     {"table_dtype", 0, 8, [](int64_t v) { return v <= DRS_TABLE_BF16 || v == DRS_TABLE_INT8_ROWWISE; }, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_dtype; }, nullptr, set_table_dtype},
+    // an int8 rowwise arena keeps every row inside one 128-byte line: 128 / S rows to a line where S < 128 does not divide 128
+    {"table_int8_lines", 0, 1, nullptr, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_int8_lines; }, nullptr, set_table_int8_lines},
     {"table_spacer", 0, kBig, nullptr, 0, [](drs_engine* e) -> int64_t { return (int64_t)e->spacers.size() << 30; }, nullptr, set_table_spacer},
     // what the engine tells its feeder (read only)
     OPT_RO("preferred_coalesce", return e->mlp_streams > 1 ? DRS_MAX_COALESCE : (e->kind == DRS_MODEL_DLRM ? 12 : 8);),

@@ -82,13 +82,17 @@ __device__ __forceinline__ uint32_t ld_nt(const uint32_t* p) { return __builtin_
 // upcast table, in the same order: the same bits.  tag: the dispatch log's dtype token (none for fp32).
 //   sb: what a lane loads per row besides its piece (int8 rowwise: the row's fp32 scale and bias; nothing otherwise)
 //   pieces_per_row(D): the row stride in pieces; a.tab_off counts `elem`s
+//   row_piece(r, pr, ln): where row r starts in its table, in pieces (pr: the row stride) -- r * pr, but for I8L, whose
+//   launch constants `ln` a kernel reads with DRS_ROW_LINES (nothing for every other policy)
 //   add(acc, keep, piece, sb): acc += the row's values (keep == false: the row contributes +0)
 struct NoSb {};
 template <class Self>
 struct PlainRow {
-  static constexpr bool rowwise = false;
+  static constexpr bool rowwise = false, lines = false;
   using sb = NoSb;
+  using ln_t = NoSb;
   __host__ __device__ static constexpr uint32_t pieces_per_row(int D) { return (uint32_t)D >> 2; }
+  __device__ static __forceinline__ uint32_t row_piece(uint32_t r, uint32_t pr, NoSb) { return r * pr; }
   template <bool NT, class P>
   __device__ static __forceinline__ NoSb load_sb(const P*, int) { return NoSb{}; }
   template <class P>
@@ -127,13 +131,15 @@ struct BF16 : PlainRow<BF16> {
 // sequential form is bit-identical to embedding_bag_byte_rowwise_offsets.  A masked row adds with scale = bias = 0:
 // acc + 0 + 0 * q == acc (acc is never -0: every step is an fma onto a sum with +0).
 struct I8 {
-  static constexpr bool rowwise = true;
+  static constexpr bool rowwise = true, lines = false;
   using elem = uint8_t;
   using piece = uint32_t;
   using sb = float2;
+  using ln_t = NoSb;
   static constexpr const char* tag = "i8";
   __host__ __device__ static constexpr int padded(int D) { return (D + 7) & ~7; }
   __host__ __device__ static constexpr uint32_t pieces_per_row(int D) { return ((uint32_t)padded(D) >> 2) + 2u; }
+  __device__ static __forceinline__ uint32_t row_piece(uint32_t r, uint32_t pr, NoSb) { return r * pr; }
   // code: the lane's piece of the row; delta: bytes from it to the row's scale (round_up(D, 8) - the lane's column)
   template <bool NT>
   __device__ static __forceinline__ float2 load_sb(const uint32_t* code, int delta) {
@@ -149,6 +155,23 @@ struct I8 {
     acc.w = row1(s, b, (float)(p >> 24), acc.w);
   }
 };
+// The same rows in the line-packed layout ("table_int8_lines" 1, drs_internal.h I8Lines): n = 128 / S rows to a 128-byte
+// line, so that no row crosses one.  Only where a row starts differs -- r * PR + (r / n) * pad pieces into its table, the
+// quotient one v_mul_hi_u32 and a shift by the launch's constants -- so every form sums the same values in the same order
+// as I8.  The range check stays r < rows: the unused slots of a table's last line are out of range like any other index.
+struct LineMap { uint32_t mul, shift, pad; };   // SlsArgs::ln_mul, ln_shift, ln_pad
+struct I8L : I8 {
+  static constexpr bool lines = true;
+  using ln_t = LineMap;
+  static constexpr const char* tag = "i8l";
+  __device__ static __forceinline__ uint32_t row_piece(uint32_t r, uint32_t pr, LineMap ln) {
+    const uint32_t q = ln.mul ? __umulhi(r, ln.mul) >> ln.shift : r;
+    return r * pr + q * ln.pad;
+  }
+};
+#define DRS_ROW_LINES(E, a, ln) \
+  typename E::ln_t ln{};        \
+  if constexpr (E::lines) ln = LineMap{(a).ln_mul, (a).ln_shift, (a).ln_pad};
 template <class E>
 __device__ __forceinline__ const typename E::elem* table_base(const float* tables) {
   return reinterpret_cast<const typename E::elem*>(tables);
@@ -211,6 +234,7 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
   // rows * S / 4 < 2^32, enforced by the conversion)
   const uint32_t Dv = E::pieces_per_row(a.D);
   const int sbd = sb_delta<E>(a.D, col);
+  DRS_ROW_LINES(E, a, ln)
 
   int32_t* my_idx = s_idx[EXACT ? g : 0];
   const int me = EXACT ? gl : lane;           // my slot among the owners
@@ -254,7 +278,7 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
       for (int u = 0; u < U; ++u) {
         bad |= (pos + u * STEP < n) && (r[u] >= rows);
         r[u] = r[u] < rows ? r[u] : 0u;
-        const piece* rp_ = reinterpret_cast<const piece*>(W) + (uint64_t)(r[u] * Dv);
+        const piece* rp_ = reinterpret_cast<const piece*>(W) + (uint64_t)E::row_piece(r[u], Dv, ln);
         if constexpr (NT) ring[u] = ld_nt(rp_); else ring[u] = *rp_;
         rsb[u] = E::template load_sb<NT>(rp_, sbd);
       }
@@ -352,6 +376,7 @@ __global__ __launch_bounds__(64) void sls_one_kernel(SlsArgs a, int tiles) {
   const piece* __restrict__ W = reinterpret_cast<const piece*>(table_base<E>(a.tables) + a.tab_off[t]) + gl;
   float* __restrict__ out = a.out + a.col0 + (int64_t)t * (4 * G) + gl * 4;
   const int sbd = sb_delta<E>(4 * G, gl * 4);
+  DRS_ROW_LINES(E, a, ln)
 #pragma unroll
   for (int j0 = 0; j0 < PER; j0 += M) {
     piece v[M];
@@ -363,8 +388,9 @@ __global__ __launch_bounds__(64) void sls_one_kernel(SlsArgs a, int tiles) {
       const uint32_t rj = (uint32_t)__shfl((int)r, src);
       vr[j] = __shfl(dst, src);
       kp[j] = __shfl(keep, src);
-      v[j] = W[(uint64_t)(rj * PR)];                          // rows * D / 4 < 2^32 (enforced at table creation)
-      sb[j] = E::template load_sb<false>(W + (uint64_t)(rj * PR), sbd);
+      const uint32_t ro = E::row_piece(rj, PR, ln);            // rows * D / 4 < 2^32 (enforced at table creation)
+      v[j] = W[(uint64_t)ro];
+      sb[j] = E::template load_sb<false>(W + (uint64_t)ro, sbd);
     }
 #pragma unroll
     for (int j = 0; j < M; ++j)
@@ -421,6 +447,7 @@ __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_
   const int R = BPW * L;
   const uint32_t D4 = E::pieces_per_row(a.D);      // row stride in pieces: rows * D / 4 < 2^32 (enforced at table creation)
   const int sbd = sb_delta<E>(a.D, col);
+  DRS_ROW_LINES(E, a, ln)
   // table bases and row counts of the wave's BPW tables: scalar loads, issued now and waited
   // for only when the row addresses are formed, i.e. in the shadow of the index loads.  (Left
   // to the compiler they become vector loads -- it cannot prove the arrays are not written by
@@ -477,7 +504,7 @@ __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_
       rk = kj[u] == z ? (uint32_t)tab_rows_k[z] : rk;
     }
     bad |= g + NG * u < R && ridx[u] >= rk;
-    const uint32_t ro = (ridx[u] < rk ? ridx[u] : 0u) * D4 + ((uint32_t)col >> 2);
+    const uint32_t ro = E::row_piece(ridx[u] < rk ? ridx[u] : 0u, D4, ln) + ((uint32_t)col >> 2);
     rp[u] = W + ((uint64_t)ro << 2);
   }
   // ---- phase 3: all row loads, back to back, nothing else in between --------------------------
@@ -557,6 +584,7 @@ __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
   const int R = BPW * L;
   const uint32_t D4 = E::pieces_per_row(a.D);      // row stride in pieces: rows * D / 4 < 2^32 (enforced at table creation)
   const int sbd = sb_delta<E>(a.D, col);
+  DRS_ROW_LINES(E, a, ln)
   const elem* Wk[BPW];
   uint32_t rows_k[BPW];
 #pragma unroll
@@ -588,7 +616,7 @@ __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
     for (int z = 1; z < BPW; ++z) rk = k == z ? rows_k[z] : rk;
     bad |= i < R && r >= rk;
     r = r < rk ? r : 0u;
-    roff[q] = r * D4;
+    roff[q] = E::row_piece(r, D4, ln);
   }
 
   // every row load of the wave, back to back
@@ -676,6 +704,7 @@ __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
   const typename E::elem* __restrict__ W = table_base<E>(a.tables) + a.tab_off[t];
   const uint32_t rows = (uint32_t)a.tab_rows[t];
   const int D = a.D;
+  DRS_ROW_LINES(E, a, ln)
   float* o = a.out + (int64_t)vrow * a.ld_out + a.col0 + (int64_t)t * D;
   bool bad = false;
   for (int c0 = 0; c0 < D; c0 += 64 * 4) {          // four columns per lane and pass
@@ -686,7 +715,9 @@ __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
       r = r < rows ? r : 0u;
       if constexpr (E::rowwise) {
         // byte loads of the codes; every lane of the wave reads the row's scale and bias
-        const uint8_t* row = W + (int64_t)r * (int64_t)E::pieces_per_row(D) * 4;
+        const uint8_t* row;
+        if constexpr (E::lines) row = W + (int64_t)E::row_piece(r, E::pieces_per_row(D), ln) * 4;
+        else row = W + (int64_t)r * (int64_t)E::pieces_per_row(D) * 4;
         const float2 sb = *reinterpret_cast<const float2*>(row + E::padded(D));
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -717,7 +748,7 @@ __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
 
 int lanes_per_row(int D) { return D <= 8 ? 2 : D <= 16 ? 4 : D <= 32 ? 8 : D <= 64 ? 16 : D <= 128 ? 32 : 64; }
 
-// the launch for tables of element type E (F32 / F16 / BF16 / I8): the plan's dispatch-log line, then its instance
+// the launch for tables of element type E (F32 / F16 / BF16 / I8 / I8L): the plan's dispatch-log line, then its instance
 template <class E>
 hipError_t launch_sls_e(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hipStream_t s, hipEvent_t stop) {
   const char* dt = E::tag;                // dispatch log: "" for fp32, else the dtype token
@@ -847,7 +878,7 @@ hipError_t launch_sls(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hipS
   switch (p.dtype) {
     case DRS_TABLE_FP16: return launch_sls_e<F16>(a, p, tune, s, stop);
     case DRS_TABLE_BF16: return launch_sls_e<BF16>(a, p, tune, s, stop);
-    case DRS_TABLE_INT8_ROWWISE: return launch_sls_e<I8>(a, p, tune, s, stop);
+    case DRS_TABLE_INT8_ROWWISE: return a.ln_pad ? launch_sls_e<I8L>(a, p, tune, s, stop) : launch_sls_e<I8>(a, p, tune, s, stop);
     default: return launch_sls_e<F32>(a, p, tune, s, stop);
   }
 }
@@ -914,8 +945,23 @@ struct SrcFill {       // fill_uniform_kernel's values of table t
   uint64_t seed;
   __device__ __forceinline__ float operator()(int64_t r, int D, int c) const { return fill_value(r * D + c, t, lo, span, seed); }
 };
+// Where the int8 rows of a launch go, or come from: `base` is the TABLE's first byte, the launch's row r is the table's row
+// first + r (drs_set_table stages a table in chunks) of `total`, n = I8Lines::n of the layout (0: plain).
+struct I8Rows {
+  uint8_t* base;
+  int64_t first, total;
+  int32_t n;
+  __device__ __forceinline__ uint8_t* row(int64_t r, int64_t S) const { return base + i8_row_offset(first + r, S, n); }
+  // line-packed layout: the bytes of its line behind row r that belong to no row -- the line's last 128 - n S bytes after
+  // its last slot, and the unused slots too after the table's last row
+  __device__ __forceinline__ int tail(int64_t r, int64_t S) const {
+    if (!n) return 0;
+    const int slot = (int)((first + r) % n);
+    return slot == n - 1 || first + r == total - 1 ? 128 - (slot + 1) * (int)S : 0;
+  }
+};
 template <class Src>
-__global__ __launch_bounds__(256) void quantize_rows_kernel(Src src, uint8_t* dst, int64_t rows, int D) {
+__global__ __launch_bounds__(256) void quantize_rows_kernel(Src src, I8Rows dst, int64_t rows, int D) {
   const int lane = threadIdx.x & 63;
   const int D8 = I8::padded(D);
   const int64_t S = D8 + 8;
@@ -933,22 +979,34 @@ __global__ __launch_bounds__(256) void quantize_rows_kernel(Src src, uint8_t* ds
     }
     const float range = __fsub_rn(mx, mn);
     const float inv = __fdiv_rn(255.0f, __fadd_rn(range, 1e-8f));
-    uint8_t* row = dst + r * S;
+    uint8_t* row = dst.row(r, S);
     for (int c = lane; c < D8; c += 64) {
       const float q = c < D ? rintf(__fmul_rn(__fsub_rn(src(r, D, c), mn), inv)) : 0.f;
       row[c] = (uint8_t)fminf(fmaxf(q, 0.f), 255.f);
     }
     if (lane == 0) *reinterpret_cast<float2*>(row + D8) = make_float2(__fdiv_rn(range, 255.0f), mn);
+    for (int c = lane * 8, z = dst.tail(r, S); c < z; c += 64 * 8) *reinterpret_cast<uint2*>(row + S + c) = make_uint2(0u, 0u);
   }
 }
 // int8 rows -> elements of type dt: each row's value fmaf(scale, q, 0.0f + bias) (the one-row bag), rounded to dt
-__global__ __launch_bounds__(256) void dequantize_rows_kernel(const uint8_t* src, void* dst, int dt, int64_t rows, int D) {
+__global__ __launch_bounds__(256) void dequantize_rows_kernel(I8Rows src, void* dst, int dt, int64_t rows, int D) {
   const int lane = threadIdx.x & 63;
   const int D8 = I8::padded(D);
   for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
-    const uint8_t* row = src + r * (D8 + 8);
+    const uint8_t* row = src.row(r, D8 + 8);
     const float2 sb = *reinterpret_cast<const float2*>(row + D8);
     for (int c = lane; c < D; c += 64) store_elem(dst, dt, r * D + c, I8::row1(sb.x, sb.y, (float)row[c], 0.0f));
+  }
+}
+// int8 rows from one layout to the other ("table_int8_lines" set on an int8 arena): the rows' bytes as they are
+__global__ __launch_bounds__(256) void relayout_rows_kernel(I8Rows src, I8Rows dst, int64_t rows, int D) {
+  const int lane = threadIdx.x & 63;
+  const int64_t S = I8::padded(D) + 8;
+  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
+    const uint8_t* from = src.row(r, S);
+    uint8_t* to = dst.row(r, S);
+    for (int c = lane * 8; c < S; c += 64 * 8) *reinterpret_cast<uint2*>(to + c) = *reinterpret_cast<const uint2*>(from + c);
+    for (int c = lane * 8, z = dst.tail(r, S); c < z; c += 64 * 8) *reinterpret_cast<uint2*>(to + S + c) = make_uint2(0u, 0u);
   }
 }
 static unsigned row_grid(int64_t rows) {
@@ -1087,13 +1145,13 @@ hipError_t launch_fill_uniform(float* W, int64_t n, int32_t t, float lo, float h
 }
 
 hipError_t launch_fill_uniform_dtype(void* W, int dtype, int64_t rows, int D, int32_t t, float lo, float hi, uint64_t seed,
-                                     hipStream_t s) {
+                                     hipStream_t s, int32_t n_lines) {
   const int64_t n = rows * D;
   if (dtype == DRS_TABLE_FP32) return launch_fill_uniform(static_cast<float*>(W), n, t, lo, hi, seed, s);
   if (n <= 0) return hipSuccess;
   if (dtype == DRS_TABLE_INT8_ROWWISE) {
     hipLaunchKernelGGL(quantize_rows_kernel<SrcFill>, dim3(row_grid(rows)), dim3(256), 0, s, SrcFill{t, lo, hi - lo, seed},
-                       static_cast<uint8_t*>(W), rows, D);
+                       I8Rows{static_cast<uint8_t*>(W), 0, rows, n_lines}, rows, D);
     return hipGetLastError();
   }
   const int64_t want = (n + 255) / 256;
@@ -1102,14 +1160,18 @@ hipError_t launch_fill_uniform_dtype(void* W, int dtype, int64_t rows, int D, in
   return hipGetLastError();
 }
 
-hipError_t launch_convert_rows(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t rows, int D, hipStream_t s) {
+hipError_t launch_convert_rows(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t rows, int D, hipStream_t s,
+                               int32_t n_src, int32_t n_dst, int64_t first, int64_t total) {
   if (rows <= 0) return hipSuccess;
-  if (dst_dtype == DRS_TABLE_INT8_ROWWISE && src_dtype != DRS_TABLE_INT8_ROWWISE)
-    hipLaunchKernelGGL(quantize_rows_kernel<SrcElems>, dim3(row_grid(rows)), dim3(256), 0, s, SrcElems{src, src_dtype},
-                       static_cast<uint8_t*>(dst), rows, D);
-  else if (src_dtype == DRS_TABLE_INT8_ROWWISE && dst_dtype != DRS_TABLE_INT8_ROWWISE)
-    hipLaunchKernelGGL(dequantize_rows_kernel, dim3(row_grid(rows)), dim3(256), 0, s, static_cast<const uint8_t*>(src), dst,
-                       dst_dtype, rows, D);
+  if (total < 0) total = first + rows;
+  const I8Rows from{static_cast<uint8_t*>(const_cast<void*>(src)), first, total, n_src}, to{static_cast<uint8_t*>(dst), first, total, n_dst};
+  const bool si8 = src_dtype == DRS_TABLE_INT8_ROWWISE, di8 = dst_dtype == DRS_TABLE_INT8_ROWWISE;
+  if (di8 && !si8)
+    hipLaunchKernelGGL(quantize_rows_kernel<SrcElems>, dim3(row_grid(rows)), dim3(256), 0, s, SrcElems{src, src_dtype}, to, rows, D);
+  else if (si8 && !di8)
+    hipLaunchKernelGGL(dequantize_rows_kernel, dim3(row_grid(rows)), dim3(256), 0, s, from, dst, dst_dtype, rows, D);
+  else if (si8 && di8)
+    hipLaunchKernelGGL(relayout_rows_kernel, dim3(row_grid(rows)), dim3(256), 0, s, from, to, rows, D);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();

@@ -65,6 +65,14 @@ def _mlp_bf16_fuse(args):
     return v
 
 
+def _table_int8_lines(args):
+    """--accel_table_int8_lines -> the engine's "table_int8_lines" value (0 when the flag is absent)."""
+    v = int(getattr(args, "accel_table_int8_lines", 0) or 0)
+    if v not in (0, 1):
+        raise ValueError("--accel_table_int8_lines %r: 0 or 1" % (v,))
+    return v
+
+
 def _init_table(n, m):
     # models/dlrm_s_caffe2.py:297-299
     return np.random.uniform(low=-np.sqrt(1 / n), high=np.sqrt(1 / n), size=(n, m)).astype(np.float32)
@@ -118,6 +126,7 @@ class _HipNet(object):
         dtype = _table_dtype(a)
         mlp_dtype = _mlp_dtype(a)
         bf16_fuse = _mlp_bf16_fuse(a)
+        int8_lines = _table_int8_lines(a)
         def make(n_slots):
             eng = N.Engine(self.kind, self.ln_emb, self.m_spa, ln_bot_cfg, ln_top_cfg,
                            interaction_op=interaction_op, interaction_itself=itself,
@@ -126,6 +135,9 @@ class _HipNet(object):
                            num_staged_batches=n_stage,
                            num_slots=n_slots, device=self._device,
                            ln_task=ln_task, num_tasks=num_tasks)
+            # --accel_table_int8_lines: ahead of table_dtype, so that the int8 arena is laid out once; only when asked for
+            if int8_lines:
+                eng.set_option("table_int8_lines", int8_lines)
             # --accel_table_dtype: first, while the arena is empty -- the engine then re-derives its by-model launch
             # forms (and "preferred_slots") for the element size, and every table write below is rounded on the device
             if dtype != N.TABLE_FP32:

@@ -302,6 +302,9 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  *                 "table_dtype" 0|1|2|8 (DRS_TABLE_FP32 | DRS_TABLE_FP16 | DRS_TABLE_BF16 | DRS_TABLE_INT8_ROWWISE:
  *                 converts the arena in use; DLRM, W&D, MT-WnD and NCF only.  8: FBGEMM's embedding_bag_byte_prepack
  *                 quantization, and with sls_exact 1 the pooled sums of embedding_bag_byte_rowwise_offsets, bit for bit)
+ *                 "table_int8_lines" 0|1 (1 with "table_dtype" 8: no int8 row crosses a 128-byte line -- 128 / S rows of
+ *                 S = round_up(D, 8) + 8 bytes share a line where S < 128 does not divide 128; set before or after
+ *                 "table_dtype", the same arena; same results)
  *   read only     "preferred_coalesce"  "preferred_slots"  "gather_bound"  "device"
  *                 "table_placements"  "table_bytes"  "table_address"
  * Options belong to the handle: two engines in one process (the mixed-model accelerator engine) keep their own.
