@@ -21,7 +21,7 @@ bool is_wide(const drs_engine* e, const Mlp& m, int l) {
 }
 
 // "mlp_dtype" 2: layer l of m runs on the bf16 matrix cores -- as a launch of its own (gemm_bf16.hip), or inside DLRM's
-// or NCF's one-launch form ("mlp_bf16_fuse" 1: fused_bf16_plan, ncf_bf16_plan)
+// or NCF's one-launch form ("mlp_bf16_fuse" 1: dlrm_one_launch, mlp_ncf)
 bool is_bf16(const drs_engine* e, const Mlp& m, int l) { return bf16_shape(e, m.ln[l], m.ln[l + 1]); }
 
 void fill_chain(ChainArgs& c, const Mlp& m, int l0, int cnt, const float* x, int64_t ldx, int64_t M,
@@ -105,71 +105,42 @@ int32_t run_mlp(drs_engine* e, Slot& s, const Mlp& m, const float* x, int64_t ld
   return DRS_OK;
 }
 
-// DLRM: bottom MLP, interaction and top MLP of a 16-row slab in ONE launch (the slab's
-// dense_out never waits for a kernel boundary).  "cat": the top chain reads the buffer the
-// bottom chain wrote; "dot": the stream kernel computes T.T^T in LDS between the chains.
-bool fused_plan(const drs_engine* e, const Slot& s, int64_t Mv, float* out, const Done* dp, const XSrc* xs, MlpPlan* p) {
+// What a one-launch form asks of an MLP's layers: none wide; under "mlp_dtype" 2 which are bf16 layers, each with its twin.
+struct LayerScan {
+  bool wide = false, bf16 = false, twins = true;
+  const uint16_t* wb[DRS_MAX_CHAIN] = {};   // per layer its bf16 twin (a bf16 layer) or null
+};
+LayerScan scan_layers(const drs_engine* e, const Mlp& m) {
+  LayerScan r;
+  for (int l = 0; l < (int)m.layers.size() && l < DRS_MAX_CHAIN; ++l) {
+    r.wide = r.wide || is_wide(e, m, l);
+    if (!is_bf16(e, m, l)) continue;
+    r.bf16 = true;
+    r.twins = r.twins && (r.wb[l] = m.layers[l].Wb);
+  }
+  return r;
+}
+bool bf16_fuse_on(const drs_engine* e) { return e->mlp_bf16_fuse && e->mlp_dtype == DRS_MLP_BF16; }
+
+// DLRM: bottom MLP, interaction and top MLP of a 16-row slab in ONE launch (the slab's dense_out never waits for a kernel
+// boundary): fusing on, enough rows, no wide layer, chains of at most DRS_MAX_CHAIN layers, slabs that fit LDS.  "cat":
+// the top chain reads the buffer the bottom chain wrote; "dot": the kernel computes T.T^T in LDS between the chains.
+// All layers fp32: a stream kernel or chain_kernel (plan_chains).  Some of them bf16 layers: fused_bf16_kernel, under
+// "mlp_bf16_fuse" 1 with "mlp_dtype" 2 and every bf16 layer with its twin.  false: the set runs launch by launch.
+bool dlrm_one_launch(const drs_engine* e, const Slot& s, int64_t Mv, float* out, const Done* dp, const XSrc* xs, MlpPlan* p) {
   if (!e->mlp_fuse || Mv < e->mlp_fuse_rows || e->kind != DRS_MODEL_DLRM) return false;
   const int nb = (int)e->bot.layers.size(), nt = (int)e->top.layers.size();
   if (nb < 1 || nt < 1 || nb > DRS_MAX_CHAIN || nt > DRS_MAX_CHAIN) return false;
-  for (int l = 0; l < nb; ++l) if (is_wide(e, e->bot, l) || is_bf16(e, e->bot, l)) return false;
-  for (int l = 0; l < nt; ++l) if (is_wide(e, e->top, l) || is_bf16(e, e->top, l)) return false;
+  const LayerScan sa = scan_layers(e, e->bot), sb = scan_layers(e, e->top);
+  if (sa.wide || sb.wide) return false;
+  const bool cat = e->interaction_op == DRS_INTERACT_CAT;
   ChainArgs a, b;
   fill_chain(a, e->bot, 0, nb, nullptr, e->m_den, Mv, s.T, e->ldT);
-  if (e->interaction_op == DRS_INTERACT_CAT) {
-    fill_chain(b, e->top, 0, nt, s.T, e->ldT, Mv, out, e->n_out);
-    return plan_chains(a, &b, e->tune, dp, xs, nullptr, nullptr, p);
-  }
-  fill_chain(b, e->top, 0, nt, s.R, e->ldR, Mv, out, e->n_out);
+  fill_chain(b, e->top, 0, nt, cat ? s.T : s.R, cat ? e->ldT : e->ldR, Mv, out, e->n_out);
   const DotArgs dot = {s.T, e->ldT, e->T + 1, e->D, e->itself, s.R, e->ldR};
-  return plan_chains(a, &b, e->tune, dp, xs, &dot, nullptr, p);
-}
-
-// "mlp_bf16_fuse" 1 with "mlp_dtype" 2: the same launch set under fused_plan's conditions (fusing on, enough rows, no wide
-// layer, chains of at most DRS_MAX_CHAIN layers, slabs that fit LDS), its bf16 layers included: fused_bf16_kernel.
-// false: the set runs as without the option.
-bool fused_bf16_plan(const drs_engine* e, const Slot& s, int64_t Mv, float* out, const Done* dp, const XSrc* xs, MlpPlan* p) {
-  if (!e->mlp_bf16_fuse || e->mlp_dtype != DRS_MLP_BF16) return false;
-  if (!e->mlp_fuse || Mv < e->mlp_fuse_rows || e->kind != DRS_MODEL_DLRM) return false;
-  const int nb = (int)e->bot.layers.size(), nt = (int)e->top.layers.size();
-  if (nb < 1 || nt < 1 || nb > DRS_MAX_CHAIN || nt > DRS_MAX_CHAIN) return false;
-  const uint16_t* wb_a[DRS_MAX_CHAIN] = {};
-  const uint16_t* wb_b[DRS_MAX_CHAIN] = {};
-  for (int l = 0; l < nb; ++l) {
-    if (is_wide(e, e->bot, l)) return false;
-    if (is_bf16(e, e->bot, l) && !(wb_a[l] = e->bot.layers[l].Wb)) return false;
-  }
-  for (int l = 0; l < nt; ++l) {
-    if (is_wide(e, e->top, l)) return false;
-    if (is_bf16(e, e->top, l) && !(wb_b[l] = e->top.layers[l].Wb)) return false;
-  }
-  ChainArgs a, b;
-  fill_chain(a, e->bot, 0, nb, nullptr, e->m_den, Mv, s.T, e->ldT);
-  if (e->interaction_op == DRS_INTERACT_CAT) {
-    fill_chain(b, e->top, 0, nt, s.T, e->ldT, Mv, out, e->n_out);
-    return plan_fused_bf16(a, b, wb_a, wb_b, nullptr, dp, xs, p);
-  }
-  fill_chain(b, e->top, 0, nt, s.R, e->ldR, Mv, out, e->n_out);
-  const DotArgs dot = {s.T, e->ldT, e->T + 1, e->D, e->itself, s.R, e->ldR};
-  return plan_fused_bf16(a, b, wb_a, wb_b, &dot, dp, xs, p);
-}
-
-// "mlp_bf16_fuse" 1 with "mlp_dtype" 2, NCF: Sum, MLP branch (ca) and predictor (cb) stay ONE launch where only their bf16
-// layers keep them from the fp32 one-launch form (mlp_ncf): no wide layer, every bf16 layer with its twin, slabs that fit
-// LDS: fused_bf16_sum_kernel.  false: the set runs as without the option.
-bool ncf_bf16_plan(const drs_engine* e, const ChainArgs& ca, const ChainArgs& cb, const SumArgs& sum, const Done* dp, MlpPlan* p) {
-  if (!e->mlp_bf16_fuse || e->mlp_dtype != DRS_MLP_BF16) return false;
-  const int nt = (int)e->top.layers.size();
-  if (!e->mlp_fuse || nt < 1 || nt > DRS_MAX_CHAIN || e->fin.layers.size() != 1) return false;
-  const uint16_t* wb_a[DRS_MAX_CHAIN] = {};
-  const uint16_t* wb_b = nullptr;
-  for (int l = 0; l < nt; ++l) {
-    if (is_wide(e, e->top, l)) return false;
-    if (is_bf16(e, e->top, l) && !(wb_a[l] = e->top.layers[l].Wb)) return false;
-  }
-  if (is_wide(e, e->fin, 0)) return false;
-  if (is_bf16(e, e->fin, 0) && !(wb_b = e->fin.layers[0].Wb)) return false;
-  return plan_fused_bf16_sum(ca, cb, wb_a, wb_b, sum, dp, p);
+  if (!sa.bf16 && !sb.bf16) return plan_chains(a, &b, e->tune, dp, xs, cat ? nullptr : &dot, nullptr, p);
+  if (!bf16_fuse_on(e) || !sa.twins || !sb.twins) return false;
+  return plan_fused_bf16(a, b, sa.wb, sb.wb, cat ? nullptr : &dot, dp, xs, p);
 }
 
 // shared_stream: 1 = one stream for everything (launch sets strictly back to back);
@@ -472,11 +443,13 @@ static int32_t mlp_ncf(SetCtx& x) {
     fill_chain(ca, e->top, 0, nt, s.T + 2 * D, e->ldT, Mv, s.H2 + D, ldc);
     fill_chain(cb, e->fin, 0, 1, s.H2, ldc, Mv, x.out, e->n_out);
     const SumArgs sum = {s.T, e->ldT, 0, D, D, s.H2, ldc};
-    bool wide = is_wide(e, e->fin, 0) || is_bf16(e, e->fin, 0);
-    for (int l = 0; l < nt; ++l) wide = wide || is_wide(e, e->top, l) || is_bf16(e, e->top, l);
+    const LayerScan st = scan_layers(e, e->top), sf = scan_layers(e, e->fin);
     MlpPlan p;
-    // (... or, with "mlp_bf16_fuse" 1, in fused_bf16_sum_kernel when some of the layers are bf16 layers)
-    if ((!wide && plan_chains(ca, &cb, e->tune, x.dp, nullptr, nullptr, &sum, &p)) || ncf_bf16_plan(e, ca, cb, sum, x.dp, &p)) {
+    // (... or, with "mlp_bf16_fuse" 1, in fused_bf16_sum_kernel when some of the layers are bf16 layers, each with its twin)
+    const bool one = st.wide || sf.wide ? false
+                     : !st.bf16 && !sf.bf16 ? plan_chains(ca, &cb, e->tune, x.dp, nullptr, nullptr, &sum, &p)
+                     : bf16_fuse_on(e) && st.twins && sf.twins && plan_fused_bf16_sum(ca, cb, st.wb, sf.wb[0], sum, x.dp, &p);
+    if (one) {
       HIP_TRY(e, launch_plan(p, e->tune, s.stream));
       return DRS_OK;
     }
@@ -515,7 +488,8 @@ static int32_t mlp_dense(SetCtx& x) {
         staged = staged && x.qb[i] >= e->batches.data() && x.qb[i] < e->batches.data() + e->batches.size();
       x.done.wait_flag = staged ? s.d_gflag : nullptr;
       x.done.wait_val = staged ? s.seq : 0;
-      fused = staged && fused_plan(e, s, Mv, out, x.dp, &x.xs, &p);   // (a waiting launch is planned only where it can wait)
+      // (a waiting launch is planned only where it can wait: plan_fused_bf16 takes none, this is the fp32 attempt alone)
+      fused = staged && dlrm_one_launch(e, s, Mv, out, x.dp, &x.xs, &p);
       if (!fused) { x.done.wait_flag = nullptr; x.done.wait_val = 0; }
     }
     if (fused) {
@@ -524,7 +498,7 @@ static int32_t mlp_dense(SetCtx& x) {
       log_launch(e->tune.log, "early");
     }
 #endif
-    fused = fused || fused_plan(e, s, Mv, out, x.dp, &x.xs, &p) || fused_bf16_plan(e, s, Mv, out, x.dp, &x.xs, &p);
+    fused = fused || dlrm_one_launch(e, s, Mv, out, x.dp, &x.xs, &p);
     if (fused) {
       HIP_TRY(e, x.join());
       HIP_TRY(e, launch_plan(p, e->tune, s.stream));

@@ -21,8 +21,6 @@
 //   chain_kernel   per-layer passes (fallback: widths not a multiple of 4, inputs too
 //                  wide for an LDS slab)
 //   fc_kernel      one layer on a 2-D grid (fallback of gemm.hip's gemm_kernel)
-#include <string.h>
-
 #include "mlp_stream.h"
 
 namespace drs {
@@ -62,7 +60,7 @@ struct LayerIo {
 // sA: [nbuf][16][KC+4] (used only when A comes from global), sB: [nbuf][128][KC+4];
 // nbuf = 2 (double buffered) when the layer needs more than one K chunk, else 1.
 constexpr int kThreads = 512;
-constexpr int PN = 128;                  // columns per pass (8 waves x 16)
+constexpr int PN = kFcPassCols;          // columns per pass (8 waves x 16)
 
 template <bool A_LDS, bool O_LDS, bool VEC, int KC>
 __device__ __forceinline__ void layer_pass(const LayerIo io, int64_t m0, int64_t M, int K,
@@ -496,34 +494,6 @@ hipError_t launch_pack_stream_weights(const float* W, int32_t K, int32_t N, floa
   return hipGetLastError();
 }
 
-static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
-constexpr size_t kLdsBudget = 156 * 1024;
-
-static size_t stage_bytes(int kc, int nbuf, int) {
-  return sizeof(float) * (size_t)nbuf * (16 + PN) * (kc + 4);
-}
-
-// Fewest K rounds that fit the LDS budget next to `extra` bytes of slabs.
-// force_kc: drs_set_option "mlp_kc" (0 = fewest rounds that fit)
-static bool pick_kc(int maxK, size_t extra, int nt, int force_kc, int* kc_out, int* nbuf_out) {
-  const int cands[4] = {256, 192, 128, 64};
-  int best_kc = 0, best_nbuf = 0, best_rounds = 1 << 30;
-  for (int kc : cands) {
-    if (force_kc && kc != force_kc) continue;
-    const int rounds = (maxK + kc - 1) / kc;
-    const int nbuf = rounds > 1 ? 2 : 1;
-    if (stage_bytes(kc, nbuf, nt) + extra > kLdsBudget) continue;
-    if (rounds < best_rounds || (rounds == best_rounds && kc < best_kc)) {
-      best_rounds = rounds; best_kc = kc; best_nbuf = nbuf;
-    }
-  }
-  if (!best_kc) return false;
-  *kc_out = best_kc; *nbuf_out = best_nbuf;
-  return true;
-}
-
-
 #define DRS_FOR_EACH_KC(X) X(64) X(128) X(192) X(256)
 
 // HIP function attributes are per device: device_init() (engine.hip) calls this once for
@@ -541,404 +511,6 @@ hipError_t mlp_set_attrs() {
   if (e == hipSuccess) e = stream4_set_attrs();
   if (e == hipSuccess) e = set_max_lds(interact_dot_kernel);
   return e;
-}
-
-// One layer: a GEMM form (gemm.hip) when the layer has one, else fc_kernel.  A split input row (XSrc::ksplit) is for
-// the GEMM forms only.  Wb: a bf16 layer ("mlp_dtype" 2) -- the bf16 GEMM form (gemm_bf16.hip) and no other.
-bool plan_layer(const float* x, int64_t ldx, int64_t M, int32_t K, const float* W, const float* b, int32_t N, int32_t act,
-                float* y, int64_t ldy, const Tune& tune, const Done* done, const XSrc* xs, MlpPlan* p, const uint16_t* Wb) {
-  memset(p, 0, sizeof *p);
-  if (done) p->done = *done;
-  if (xs) p->xs = *xs;
-  ChainArgs& L = p->a;
-  L.x = x; L.ldx = ldx; L.M = M; L.n_layers = 1; L.width[0] = K; L.width[1] = N;
-  L.W[0] = W; L.b[0] = b; L.act[0] = act; L.y = y; L.ldy = ldy;
-  if (Wb) { p->wb = Wb; return gemm_bf16_plan(tune, p); }
-  if (N >= 64 && K >= 64 && gemm_plan(tune, p)) return true;
-  if (p->xs.ksplit > 0 || !pick_kc(K, 0, 2, tune.mlp_kc, &p->kc, &p->nbuf)) return false;
-  p->form = MlpForm::fc;
-  p->lds = stage_bytes(p->kc, p->nbuf, 2);
-  p->grid_x = (unsigned)((M + 15) / 16);
-  p->grid_y = (unsigned)((N + PN - 1) / PN);
-  bool vec = aligned16(x) && aligned16(W) && (ldx & 3) == 0 && (K & 3) == 0;
-  for (int i = 0; i < p->xs.q.n_q; ++i) vec = vec && aligned16(p->xs.x[i]);
-  p->vec = vec;
-  return true;
-}
-
-static int chain_slab_ld2(const ChainArgs& a, const ChainArgs* b) {
-  int w = 4;
-  for (int l = 1; l < a.n_layers; ++l) w = a.width[l] > w ? a.width[l] : w;  // slabs hold layer outputs
-  if (b) for (int l = 1; l < b->n_layers; ++l) w = b->width[l] > w ? b->width[l] : w;
-  return (w + 3) / 4 * 4 + 4;
-}
-
-// ldA > 0: the chains' input slab (16 x K0) is preloaded into LDS (see run_chain)
-static bool chain_plan(const ChainArgs& a, const ChainArgs* b, const Tune& tune, int* kc, int* nbuf,
-                       size_t* lds, int* ldA) {
-  int maxK = 1, k0 = a.width[0];
-  for (int l = 0; l < a.n_layers; ++l) maxK = a.width[l] > maxK ? a.width[l] : maxK;
-  if (b) {
-    for (int l = 0; l < b->n_layers; ++l) maxK = b->width[l] > maxK ? b->width[l] : maxK;
-    k0 = b->width[0] > k0 ? b->width[0] : k0;
-  }
-  const size_t slabs = sizeof(float) * (size_t)2 * 16 * chain_slab_ld2(a, b);
-  const int lda = (k0 + 3) / 4 * 4 + 4;
-  const size_t pre = (tune.mlp_preload && k0 <= 640) ? sizeof(float) * (size_t)16 * lda : 0;
-  if (pre && pick_kc(maxK, slabs + pre, 2, tune.mlp_kc, kc, nbuf)) {
-    *lds = stage_bytes(*kc, *nbuf, 2) + slabs + pre;
-    *ldA = lda;
-    return true;
-  }
-  if (!pick_kc(maxK, slabs, 2, tune.mlp_kc, kc, nbuf)) return false;
-  *lds = stage_bytes(*kc, *nbuf, 2) + slabs;
-  *ldA = 0;
-  return true;
-}
-
-static inline int pad64(int n) { return (n + 63) & ~63; }
-
-// Lay the chain(s) out for a stream kernel (pl: its Done and XSrc set).  false = not applicable.
-static bool stream_plan(const ChainArgs& a, const ChainArgs* b, const Tune& tune, const DotArgs* dot, const SumArgs* sum,
-                        MlpPlan* pl) {
-  SArgs& p = pl->sa;
-  NSplit* nsp = &pl->ns;
-  const XSrc& xs = pl->xs;
-  const bool publish = pl->done.counter != nullptr, d_wait = pl->done.wait_flag != nullptr;   // (d_wait: the launch polls Done::wait_flag)
-  memset(nsp, 0, sizeof *nsp);
-  memset(&p, 0, sizeof p);
-  const int na = a.n_layers, nb = b ? b->n_layers : 0;
-  if (na + nb > DRS_MAX_STREAM_LAYERS) return false;
-  // second chain must read the buffer the first one writes (dense_out slot in front)
-  const int d_out = a.width[na];
-  int dotP = 0;
-  if (dot) {
-    // bottom -> T (dense_out slot) -> interaction -> R -> top
-    dotP = dot->F * (dot->F - 1) / 2 + (dot->itself ? dot->F : 0);
-    if (!b || dot->T != a.y || dot->ldt != a.ldy || dot->R != b->x || dot->ldr != b->ldx ||
-        dot->D != d_out || (d_out & 3) || b->width[0] != d_out + dotP || dot->F < 2)
-      return false;
-  } else if (sum) {
-    // [ sum of two column blocks | first chain's output ] -> second chain
-    if (!b || dot || sum->cols <= 0 || (sum->cols & 3) || (sum->col_a & 3) || (sum->col_b & 3) || (sum->ld & 3) ||
-        (sum->ldd & 3) || !aligned16(sum->src) || !aligned16(sum->dst) || b->x != sum->dst ||
-        b->ldx != sum->ldd || a.y != sum->dst + sum->cols || a.ldy != sum->ldd ||
-        b->width[0] != sum->cols + d_out || (d_out & 3))
-      return false;
-  } else if (b && (b->x != a.y || b->ldx != a.ldy || d_out > b->width[0] || (d_out & 3))) {
-    return false;
-  }
-  auto ok_ptr = [](const void* q) { return aligned16(q); };
-  // every weight matrix must live inside the engine's arena (tile addresses are 32-bit byte
-  // offsets from its base)
-  auto in_arena = [&](const float* w, int64_t n) {
-    return tune.w_arena && w >= tune.w_arena && w + n <= tune.w_arena + tune.w_arena_floats &&
-           tune.w_arena_floats < (1ull << 30);
-  };
-  for (int l = 0; l < na; ++l) if (!in_arena(a.W[l], (int64_t)a.width[l] * a.width[l + 1])) return false;
-  for (int l = 0; l < nb; ++l) if (!in_arena(b->W[l], (int64_t)b->width[l] * b->width[l + 1])) return false;
-  if (!ok_ptr(a.x) || (a.ldx & 3)) return false;
-  for (int i = 0; i < xs.q.n_q; ++i) if (!ok_ptr(xs.x[i])) return false;
-  for (int l = 0; l < na; ++l) if (!ok_ptr(a.W[l]) || (a.width[l] & 3)) return false;
-  if (b) {
-    if (!ok_ptr(b->x) || (b->ldx & 3)) return false;
-    for (int l = 0; l < nb; ++l) if (!ok_ptr(b->W[l]) || (b->width[l] & 3)) return false;
-  }
-  // biases back to back, each padded to 4 floats (how the engine's arena lays them out)
-  {
-    const float* expect = a.b[0];
-    if (!expect) return false;
-    for (int l = 0; l < na; ++l) { if (a.b[l] != expect) return false; expect += (a.width[l + 1] + 3) & ~3; }
-    for (int l = 0; l < nb; ++l) { if (b->b[l] != expect) return false; expect += (b->width[l + 1] + 3) & ~3; }
-  }
-  // the packed form ("mlp_stream" 2): every layer must carry its packed twin (engine layers of the
-  // bottom / top / final / task MLPs do: drs_set_fc)
-  bool pk = tune.mlp_stream >= 2 && tune.w_packed_hi > tune.w_packed_lo;
-  {
-    auto has_twin = [&](const float* w) {
-      const uint64_t o = (uint64_t)(w - tune.w_arena);
-      return o >= tune.w_packed_lo && o < tune.w_packed_hi;
-    };
-    for (int l = 0; l < na; ++l) pk = pk && has_twin(a.W[l]);
-    for (int l = 0; l < nb; ++l) pk = pk && has_twin(b->W[l]);
-  }
-  // "mlp_stream" 4: stream4_kernel -- four waves x up to four tiles, b128 activation operands, the step table below
-  // run segment by segment; its steps must fit the descriptor table
-  const bool f4 = tune.mlp_stream == 4;
-  const int nt3 = 4, nw3 = 16 / nt3;   // tiles per wave at most; waves
-  auto tpw3 = [&](int N, int out_pad) {       // tiles per wave of a layer: 1 / 2 (/ 4): a pass covers nw3 * tpw tiles
-    const int etl = ((out_pad > N ? out_pad : N) + 15) / 16;
-    int t = 1;
-    while (t < nt3 && etl > nw3 * t) t *= 2;
-    return t;
-  };
-  auto steps3 = [&](int K, int N, int out_pad) {
-    const int etl = ((out_pad > N ? out_pad : N) + 15) / 16, tpp = nw3 * tpw3(N, out_pad);
-    return ((etl + tpp - 1) / tpp) * ((K + 63) / 64);
-  };
-  bool f3 = pk && f4;
-  // Column-split form ("mlp_nsplit"; SArgs::ns): the first layer of the second chain over ns workgroups per slab of rows.
-  // A slice is ONE pass of the four waves: N / ns in {64, 128, 256} columns (1 / 2 / 4 tiles per wave), N a multiple of
-  // 64 (no zero pad in the slab), and the layer must hand its outputs on through LDS (not the chain's last).
-  int ns = 0;
-  if (f3 && b && !sum && nb >= 2 && tune.mlp_nsplit >= 2 && tune.xbuf && tune.xcnt && !d_wait &&
-      a.M <= tune.mlp_nsplit_rows && a.M <= tune.xbuf_rows && b->width[1] <= tune.xbuf_cols && !(b->width[1] & 63)) {
-    for (int S = tune.mlp_nsplit >= 4 ? 4 : 2; S >= 2 && !ns; S >>= 1) {
-      const int cw = b->width[1] / S;
-      if (b->width[1] % S == 0 && (cw == 64 || cw == 128 || cw == 256)) ns = S;
-    }
-  }
-  if (f3) {
-    int st = 0;
-    for (int l = 0; l < na; ++l) {
-      int op = l == na - 1 ? a.width[l + 1] : pad64(a.width[l + 1]);
-      if (l == na - 1 && b && sum) op = pad64(b->width[0]) - sum->cols;
-      st += steps3(a.width[l], a.width[l + 1], op);
-    }
-    for (int l = 0; l < nb; ++l)
-      st += l == 0 && ns ? (b->width[0] + 63) / 64
-                         : steps3(b->width[l], b->width[l + 1], l == nb - 1 ? b->width[l + 1] : pad64(b->width[l + 1]));
-    for (int l = 0; l < na; ++l) f3 = f3 && a.width[l + 1] <= 4080 && a.width[l] <= 4096;
-    for (int l = 0; l < nb; ++l) f3 = f3 && b->width[l + 1] <= 4080 && b->width[l] <= 4096;
-    f3 = f3 && st <= DRS_MAX_STREAM_TILES;
-  }
-  if (sum && !f3 && pad64(b->width[0]) - sum->cols > ((d_out + 127) / 128) * 128) return false;   // zero pad must fall in an existing pass
-  const int nwv = 8;
-  const int passw = 16 * nwv;
-  const int lpad = f3 ? 8 : 4;      // slab rows: 64 m + 8 floats apart in the b128 form, 64 m + 4 else
-  // rows per workgroup: 16, or 32 for stream4_kernel's two-halves form ("mlp_rows32": launches of at
-  // least that many rows, no summed input, slabs that still fit LDS)
-  int SR = 16;
-  if (f3 && f4 && !sum && tune.mlp_rows32 > 0 && a.M >= tune.mlp_rows32) {
-    size_t fl = 32 * (size_t)(pad64(a.width[0]) + lpad);
-    if (b) {
-      const int rc = dot ? dot->F * dot->D : b->width[0];
-      fl += 32 * (size_t)(pad64(rc) + lpad);
-      if (dot) fl += 32 * (size_t)(pad64(b->width[0]) + lpad);
-    }
-    int w0 = 0, w1 = 0, wh = 0;
-    auto note = [&](int n) { int& w = wh ? w1 : w0; w = pad64(n) > w ? pad64(n) : w; wh ^= 1; };
-    for (int l = 0; l < na; ++l) if (!(l == na - 1)) note(a.width[l + 1]);
-    for (int l = 0; l < nb; ++l) if (!(l == nb - 1)) note(b->width[l + 1]);
-    const bool q_in_x0 = !b && w1 && w1 <= pad64(a.width[0]);     // (see the Q slab below)
-    fl += (w0 ? 32 * (size_t)(w0 + lpad) : 0) + (w1 && !q_in_x0 ? 32 * (size_t)(w1 + lpad) : 0);
-    for (int l = 0; l < na; ++l) fl += (a.width[l + 1] + 3) & ~3;
-    for (int l = 0; l < nb; ++l) fl += (b->width[l + 1] + 3) & ~3;
-    fl += 4 + 4 * DRS_MAX_STREAM_TILES + (sizeof(SLayer) / 4) * DRS_MAX_STREAM_LAYERS;
-    if (sizeof(float) * fl <= kLdsBudget) SR = 32;
-  }
-  // LDS layout (floats): [sB 2x128x68 (LDS-staged form only)][X0][RS][P][Q][biases]
-  int off = 0;
-  p.sB_off = off; off += pk ? 0 : 2 * 128 * 68;
-  const int x0_ld = pad64(a.width[0]) + lpad;
-  const int x0_off = off; off += SR * x0_ld;
-  // RS: what the first chain's last layer writes its dense_out slot into and the pooled rows
-  // are pulled beside: the second chain's input (cat) or the interaction's T slab (dot)
-  int rs_off = -1, rs_ld = 0, rs_cols = 0, ri_off = -1, ri_ld = 0;
-  if (b) {
-    rs_cols = dot ? dot->F * dot->D : b->width[0];
-    rs_ld = pad64(rs_cols) + lpad; rs_off = off; off += SR * rs_ld;
-    if (dot) { ri_ld = pad64(b->width[0]) + lpad; ri_off = off; off += SR * ri_ld; }
-  }
-  // ping-pong widths
-  int wP = 0, wQ = 0;
-  {
-    int which = 0;   // next ping-pong slab to write: 0 = P, 1 = Q
-    auto note = [&](int n) { int& w = which ? wQ : wP; w = pad64(n) > w ? pad64(n) : w; which ^= 1; };
-    for (int l = 0; l < na; ++l) if (!(l == na - 1)) note(a.width[l + 1]);
-    for (int l = 0; l < nb; ++l) if (!(l == nb - 1)) note(b->width[l + 1]);
-  }
-  const int p_ld = wP + lpad, q_ld = wQ + lpad;
-  const int p_off = off; off += wP ? SR * p_ld : 0;
-  // 32-row form, single chain: the input slab is dead once layer 0 has run (the barrier behind it), and Q
-  // is first written by layer 1 -- Q lives in X0's space when it fits there (RM3's 416-512-256-1 top
-  // chain: 164 KB -> 130 KB)
-  const bool q_in_x0 = SR == 32 && !b && wQ && q_ld <= x0_ld;
-  const int q_off = q_in_x0 ? x0_off : off; off += wQ && !q_in_x0 ? SR * q_ld : 0;
-  const int bias_off = off;
-  for (int l = 0; l < na; ++l) off += (a.width[l + 1] + 3) & ~3;
-  for (int l = 0; l < nb; ++l) off += (b->width[l + 1] + 3) & ~3;
-  off = (off + 3) & ~3;
-  p.tab_off = off; off += pk ? 4 * DRS_MAX_STREAM_TILES : 0;
-  p.lay_off = off; off += pk ? (int)(sizeof(SLayer) / 4) * DRS_MAX_STREAM_LAYERS : 0;
-  if (sizeof(float) * (size_t)off > kLdsBudget) return false;
-  pl->lds = sizeof(float) * (size_t)off;
-  p.lds_floats = off;
-
-  int which = 0, cur_off = x0_off, cur_ld = x0_ld, n = 0, tiles = 0, boff = bias_off;
-  auto add = [&](const ChainArgs& c, int l, bool last_of_chain, bool last_of_all) {
-    SLayer& L = p.L[n++];
-    L.W = c.W[l]; L.w_off = (uint32_t)(c.W[l] - tune.w_arena);
-    L.wp_off = L.w_off + (uint32_t)(((uint64_t)c.width[l] * c.width[l + 1] + 63) / 64 * 64);   // twin right behind W
-    L.b = c.b[l]; L.K = c.width[l]; L.N = c.width[l + 1]; L.act = c.act[l];
-    L.in_off = cur_off; L.in_ld = cur_ld;
-    L.out_off = -1; L.out_ld = 0; L.out_pad = L.N; L.out_col0 = 0;
-    L.g_out = nullptr; L.g_ld = 0; L.g_sc1 = 0;
-    L.b_off = boff; boff += (L.N + 3) & ~3;
-    if (last_of_chain) {
-      L.g_out = c.y; L.g_ld = c.ldy;
-      L.g_sc1 = last_of_all && publish;
-      if (!last_of_all) {           // dense_out slot of the second chain's input slab
-        L.out_off = rs_off; L.out_ld = rs_ld; L.out_pad = L.N;
-        if (sum) { L.out_col0 = sum->cols; L.out_pad = pad64(b->width[0]) - sum->cols; }   // behind the summed block, zero tail
-        cur_off = dot ? ri_off : rs_off; cur_ld = dot ? ri_ld : rs_ld;
-      }
-    } else {
-      L.out_off = which ? q_off : p_off; L.out_ld = which ? q_ld : p_ld; L.out_pad = pad64(L.N);
-      cur_off = L.out_off; cur_ld = L.out_ld;
-      which ^= 1;
-    }
-    tiles += ((L.N + passw - 1) / passw) * ((L.K + 63) / 64);
-  };
-  for (int l = 0; l < na; ++l) add(a, l, l == na - 1, l == na - 1 && !b);
-  for (int l = 0; l < nb; ++l) add(*b, l, l == nb - 1, l == nb - 1);
-  p.n_layers = n;
-  p.n_tiles = tiles;
-  p.n_table = 0;
-  p.wait_tile = -1; p.ns = 0;
-  if (f3) {
-    // one descriptor per STEP of stream3_kernel: (layer, pass of nw3 x TPW tiles, 64-k chunk).
-    // wp_off: chunk c of the twin's first 128-column pass; in_ld: floats between two such passes;
-    // a_off: low half = LDS offset of (row 0, k = 64 c) of the input slab, high half = its leading dimension
-    int ti = 0, inter_at = -1;
-    if (dot) inter_at = 0;
-    for (int l = 0; l < n; ++l) {
-      const SLayer& L = p.L[l];
-      const int nch = (L.K + 63) / 64, ntl = (L.N + 15) / 16;
-      const int opad = L.out_off >= 0 && L.out_pad > L.N ? L.out_pad : L.N;
-      const bool split = ns && l == na;      // this launch's split layer: the table names slice 0's tiles (one pass)
-      const int etl = (opad + 15) / 16, tpw = split ? L.N / ns / 64 : tpw3(L.N, opad);
-      const int tpp = nw3 * tpw, npass = split ? 1 : (etl + tpp - 1) / tpp;
-      if (dot && l < na) inter_at += npass * nch;
-      if (b && !sum && l == na) p.wait_tile = ti;
-      if (split) {
-        p.ns = ns;
-        nsp->t0 = ti; nsp->t1 = ti + nch; nsp->tps = tpp; nsp->n = L.N; nsp->off = L.out_off; nsp->ld = L.out_ld;
-        nsp->xbuf = tune.xbuf; nsp->xcnt = tune.xcnt;
-      }
-      for (int ps = 0; ps < npass; ++ps)
-        for (int c = 0; c < nch; ++c) {
-          STile& t = p.tiles[ti];
-          t.wp_off = L.wp_off + (uint32_t)c * 8192u;
-          t.a_off = (L.in_off + c * 64) | (L.in_ld << 16);
-          t.in_ld = nch * 8192;
-          const bool last_of_layer = c == nch - 1 && ps == npass - 1;
-          t.info = (ps * tpp) | (ntl << 8) | (c == nch - 1 ? S3_LAST : 0) | (last_of_layer ? S3_BARRIER : 0) |
-                   (last_of_layer ? 0 : S3_ANEXT) | (tpw << S3_TPW_SHIFT) | (c == 0 ? S3_FIRST : 0) | (l << 24);
-          ++ti;
-        }
-    }
-    if (inter_at >= 0 && inter_at < ti) p.tiles[inter_at].info |= S3_INTERACT;
-    p.n_table = ti;
-    p.n_tiles = ti;
-    // the arena range that holds the packed twins of this launch's layers (L2 warm-up)
-    uint64_t lo = ~0ull, hi = 0;
-    for (int l = 0; l < n; ++l) {
-      const uint64_t b = p.L[l].wp_off, e = b + (uint64_t)stream_packed_floats(p.L[l].K, p.L[l].N);
-      lo = b < lo ? b : lo; hi = e > hi ? e : hi;
-    }
-    lo &= ~1023ull;                                          // 4-KB granules
-    hi = (hi + 1023) & ~1023ull;
-    if (hi > tune.w_arena_floats) hi = tune.w_arena_floats & ~1023ull;
-    if (hi < lo + 1024) { lo = 0; hi = 1024; }
-    p.warm_off = (uint32_t)lo;
-    p.warm_bytes = (int32_t)((hi - lo) * 4);
-  } else if (pk && nwv == 8 && tiles <= DRS_MAX_STREAM_TILES) {
-    int ti = 0, inter_at = -1;
-    if (dot) {
-      inter_at = 0;
-      for (int l = 0; l < na; ++l) inter_at += ((a.width[l + 1] + 127) / 128) * ((a.width[l] + 63) / 64);
-    }
-    for (int l = 0; l < n; ++l) {
-      const SLayer& L = p.L[l];
-      const int nch = (L.K + 63) / 64, npass = (L.N + 127) / 128;
-      for (int ps = 0; ps < npass; ++ps)
-        for (int c = 0; c < nch; ++c) {
-          STile& t = p.tiles[ti];
-          t.wp_off = L.wp_off + (uint32_t)(ps * nch + c) * 8192u;
-          t.a_off = L.in_off + c * 64;
-          t.in_ld = L.in_ld;
-          const int ncols = L.N - ps * 128;
-          t.info = (ncols > 0xffff ? 0xffff : ncols) | (c == nch - 1 ? 1 << 16 : 0) |
-                   (c == nch - 1 && ps == npass - 1 ? 1 << 17 : 0) | (ti == inter_at ? 1 << 18 : 0) | (l << 24);
-          ++ti;
-        }
-    }
-    p.n_table = ti;
-  }
-  p.n_bias = boff - bias_off;
-  p.bias_off = bias_off;
-  p.bias = a.b[0];
-  p.M = a.M;
-  p.zero = tune.zero;
-  p.wbase = tune.w_arena;
-  p.zero_off = tune.w_zero_off;
-  p.dbg = tune.mlp_debug;
-  SInput& i0 = p.in[0];
-  i0.src = a.x; i0.ld = a.ldx; i0.col0 = 0; i0.cols = a.width[0]; i0.cols_pad = pad64(a.width[0]);
-  i0.lds_off = x0_off; i0.lds_ld = x0_ld; i0.lds_col0 = 0; i0.use_xs = xs.q.n_q > 0;
-  p.in[0].col2 = p.in[1].col2 = -1;
-  p.n_inputs = 1;
-  if (b) {
-    SInput& i1 = p.in[1];
-    i1.src = dot ? dot->T : b->x; i1.ld = dot ? dot->ldt : b->ldx; i1.col0 = d_out; i1.cols = rs_cols - d_out;
-    i1.cols_pad = pad64(rs_cols) - d_out;
-    i1.lds_off = rs_off; i1.lds_ld = rs_ld; i1.lds_col0 = d_out; i1.use_xs = 0;
-    if (sum) {
-      i1.src = sum->src; i1.ld = sum->ld; i1.col0 = sum->col_a; i1.col2 = sum->col_b;
-      i1.cols = i1.cols_pad = sum->cols; i1.lds_col0 = 0;
-      i1.g_dst = sum->dst; i1.g_ldd = sum->ldd;
-    }
-    p.n_inputs = 2;
-  }
-  if (dot) {
-    p.inter_on = 1; p.F = dot->F; p.D = dot->D; p.itself = dot->itself ? 1 : 0; p.P = dotP;
-    p.t_off = rs_off; p.t_ld = rs_ld; p.r_off = ri_off; p.r_ld = ri_ld; p.r_pad = pad64(b->width[0]);
-    p.g_R = dot->R; p.g_ldr = dot->ldr;
-    p.inter_tile = 0;
-    for (int l = 0; l < na; ++l) p.inter_tile += ((a.width[l + 1] + passw - 1) / passw) * ((a.width[l] + 63) / 64);
-  }
-  // the kernel instance: stream4_kernel (the packed step table), else stream_kernel (packed twins | weights staged in LDS)
-  const bool two = tune.mlp_stream_2cu;
-  if (p.ns) pl->form = SR == 32 ? (p.ns == 4 ? MlpForm::stream4_rows32_nsplit4 : MlpForm::stream4_rows32_nsplit2)
-                                : (p.ns == 4 ? MlpForm::stream4_nsplit4 : MlpForm::stream4_nsplit2);
-  else if (f3) pl->form = SR == 32 ? MlpForm::stream4_rows32 : sum ? MlpForm::stream4_sum : two ? MlpForm::stream4_2cu : MlpForm::stream4;
-  else pl->form = !pk ? MlpForm::stream_lds : (two && p.n_table > 0) ? MlpForm::stream_packed_2cu : MlpForm::stream_packed;
-  pl->grid_x = (unsigned)((a.M + SR - 1) / SR) * (p.ns ? (unsigned)p.ns : 1u);
-  pl->grid_y = 1;
-  return true;
-}
-
-// One or two chains in one launch: the stream kernel when it takes them, else chain_kernel -- which has neither the
-// interaction nor the summed input nor the late start.  A single chain is planned only where chain_kernel holds it
-// (run_mlp cuts a run of layers shorter until it does).
-bool plan_chains(const ChainArgs& a, const ChainArgs* b, const Tune& tune, const Done* done, const XSrc* xs,
-                 const DotArgs* dot, const SumArgs* sum, MlpPlan* p) {
-  memset(p, 0, sizeof *p);
-  if (done) p->done = *done;
-  if (xs) p->xs = *xs;
-  if (a.n_layers < 1 || a.n_layers > DRS_MAX_CHAIN || (b && (b->n_layers < 1 || b->n_layers > DRS_MAX_CHAIN)))
-    return false;
-  p->a = a;
-  if (b) p->b = *b;
-  const bool chain_ok = !dot && !sum && !p->done.wait_flag && chain_plan(a, b, tune, &p->kc, &p->nbuf, &p->lds, &p->lda);
-  if (!b && !chain_ok) return false;
-  if (tune.mlp_stream && tune.zero && stream_plan(a, b, tune, dot, sum, p))
-    return !p->done.wait_flag || can_defer(*p);
-  if (!chain_ok) return false;
-  bool vec = aligned16(a.x) && (a.ldx & 3) == 0;
-  for (int l = 0; l < a.n_layers; ++l) vec = vec && aligned16(a.W[l]) && (a.width[l] & 3) == 0;
-  if (b) {
-    vec = vec && aligned16(b->x) && (b->ldx & 3) == 0;
-    for (int l = 0; l < b->n_layers; ++l) vec = vec && aligned16(b->W[l]) && (b->width[l] & 3) == 0;
-  }
-  for (int i = 0; i < p->xs.q.n_q; ++i) vec = vec && aligned16(p->xs.x[i]);
-  p->form = MlpForm::chain;
-  p->vec = vec;
-  p->sld = chain_slab_ld2(a, b);
-  p->grid_x = (unsigned)((a.M + 15) / 16);
-  p->grid_y = 1;
-  return true;
 }
 
 // DRS_TIMELINE builds: the mlp.hip / stream kernels stamp into 8 KB behind the LDS they use

@@ -27,8 +27,6 @@
 // own, fused_bf16_sum_kernel, from the same passes: no dense rows and no XSrc -- X0 is Concat(emb2, emb3) out of T, RS is
 // the predictor's input [ mf = emb0 + emb1 | the branch's output ], i.e. the chain's output goes BEHIND the staged block
 // (column D), not in front of it; both halves are also left in the engine's buffer (drs_fetch_interaction).
-#include <string.h>
-
 #include "mlp_stream.h"
 
 namespace drs {
@@ -40,7 +38,6 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr int FW = 8;                 // waves per workgroup: two per SIMD, each covers the other's L2 and LDS latencies
 constexpr int kFThreads = 64 * FW;
 constexpr int PD = 4;                 // 64-k chunks of weights in flight per tile ahead of the MFMAs
-constexpr size_t kFLdsBudget = 156 * 1024;
 
 __device__ __forceinline__ bf16x8 to_bf16x8(const float4 lo, const float4 hi) {
   bf16x8 r;
@@ -388,163 +385,12 @@ __global__ __launch_bounds__(kFThreads) void fused_bf16_sum_kernel(FArgs a, Done
   signal_done(done, gridDim.x, smem);
 }
 
-inline int pad64(int n) { return (n + 63) & ~63; }
-inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 }  // namespace
 
 // per device (device_init)
 hipError_t fused_bf16_set_attrs() {
   const hipError_t e = set_max_lds(fused_bf16_kernel);
   return e != hipSuccess ? e : set_max_lds(fused_bf16_sum_kernel);
-}
-
-// Lay the bottom chain a, the interaction and the top chain b out for fused_bf16_kernel.  wb_a / wb_b: per layer its bf16
-// twin, or null for an fp32 layer.  false: the form does not take the launch (no bf16 layer, a launch that waits for the
-// gather by itself, D not a multiple of 4 under the dot interaction, slabs beyond LDS).  Any K and N otherwise.
-bool plan_fused_bf16(const ChainArgs& a, const ChainArgs& b, const uint16_t* const* wb_a, const uint16_t* const* wb_b,
-                     const DotArgs* dot, const Done* done, const XSrc* xs, MlpPlan* p) {
-  memset(p, 0, sizeof *p);
-  if (done) p->done = *done;
-  if (!xs || xs->q.n_q < 1 || p->done.wait_flag) return false;
-  p->xs = *xs;
-  p->a = a; p->b = b;
-  const int na = a.n_layers, nb = b.n_layers;
-  if (na < 1 || nb < 1 || na > DRS_MAX_CHAIN || nb > DRS_MAX_CHAIN) return false;
-  const int d_out = a.width[na];
-  FArgs& f = p->fa;
-  int dotP = 0, rs_cols;
-  const float* T;
-  int64_t ldt;
-  if (dot) {
-    dotP = dot->F * (dot->F - 1) / 2 + (dot->itself ? dot->F : 0);
-    if (dot->T != a.y || dot->ldt != a.ldy || dot->R != b.x || dot->ldr != b.ldx || dot->D != d_out || (d_out & 3) ||
-        b.width[0] != d_out + dotP || dot->F < 2)
-      return false;
-    rs_cols = dot->F * dot->D; T = dot->T; ldt = dot->ldt;
-  } else {
-    if (b.x != a.y || b.ldx != a.ldy || d_out >= b.width[0]) return false;
-    rs_cols = b.width[0]; T = b.x; ldt = b.ldx;
-  }
-  // LDS (floats): X0 | RS | RI (dot) | P | Q
-  int off = 0;
-  f.k0 = a.width[0];
-  f.x0_ld = pad64(f.k0) + 4; f.x0_off = off; off += 16 * f.x0_ld;
-  f.rs_ld = pad64(rs_cols) + 4; f.rs_off = off; off += 16 * f.rs_ld;
-  if (dot) { f.ri_ld = pad64(b.width[0]) + 4; f.ri_off = off; off += 16 * f.ri_ld; }
-  int wP = 0, wQ = 0;
-  {
-    int which = 0;
-    auto note = [&](int n) { int& w = which ? wQ : wP; w = pad64(n) > w ? pad64(n) : w; which ^= 1; };
-    for (int l = 0; l + 1 < na; ++l) note(a.width[l + 1]);
-    for (int l = 0; l + 1 < nb; ++l) note(b.width[l + 1]);
-  }
-  const int p_ld = wP + 4, q_ld = wQ + 4;
-  const int p_off = off; off += wP ? 16 * p_ld : 0;
-  const int q_off = off; off += wQ ? 16 * q_ld : 0;
-  if (sizeof(float) * (size_t)off > kFLdsBudget) return false;
-  p->lds = sizeof(float) * (size_t)off;
-
-  int which = 0, cur_off = f.x0_off, cur_ld = f.x0_ld, n = 0, n_bf16 = 0;
-  auto add = [&](const ChainArgs& c, const uint16_t* wb, int l, bool last_of_chain, bool last_of_all) {
-    FLayer& L = f.L[n++];
-    L.W = c.W[l]; L.Wb = wb; L.b = c.b[l]; L.K = c.width[l]; L.N = c.width[l + 1]; L.act = c.act[l];
-    L.in_off = cur_off; L.in_ld = cur_ld;
-    L.out_off = -1; L.out_ld = 0; L.out_pad = L.N;
-    n_bf16 += wb ? 1 : 0;
-    if (last_of_chain) {
-      L.g_out = c.y; L.g_ld = c.ldy; L.g_sc1 = last_of_all && p->done.counter;
-      if (!last_of_all) {        // the dense_out slot in front of the pooled rows: exactly N columns
-        L.out_off = f.rs_off; L.out_ld = f.rs_ld;
-        cur_off = dot ? f.ri_off : f.rs_off; cur_ld = dot ? f.ri_ld : f.rs_ld;
-      }
-    } else {
-      L.out_off = which ? q_off : p_off; L.out_ld = which ? q_ld : p_ld; L.out_pad = pad64(L.N);
-      cur_off = L.out_off; cur_ld = L.out_ld;
-      which ^= 1;
-    }
-  };
-  for (int l = 0; l < na; ++l) add(a, wb_a[l], l, l == na - 1, false);
-  for (int l = 0; l < nb; ++l) add(b, wb_b[l], l, l == nb - 1, l == nb - 1);
-  if (!n_bf16) return false;
-  f.n_layers = n; f.n_bot = na; f.n_bf16 = n_bf16;
-  f.M = a.M; f.ldx = a.ldx;
-  f.T = T; f.ldt = ldt; f.p_col0 = d_out; f.p_cols = rs_cols - d_out;
-  f.p_cols_pad = dot ? f.p_cols : pad64(rs_cols) - d_out;
-  bool vx = !(f.k0 & 3) && !(a.ldx & 3);
-  for (int i = 0; i < xs->q.n_q; ++i) vx = vx && al16(xs->x[i]);
-  f.vec_x = vx;
-  f.vec_t = al16(T) && !(ldt & 3) && !(d_out & 3) && !(f.p_cols & 3);
-  if (dot) { f.dot = 1; f.F = dot->F; f.D = dot->D; f.itself = dot->itself ? 1 : 0; f.R = dot->R; f.ldr = dot->ldr; }
-  p->form = MlpForm::fused_bf16;
-  p->grid_x = (unsigned)((a.M + 15) / 16);
-  p->grid_y = 1;
-  return true;
-}
-
-// NCF: the MLP branch a (its input: columns of sum.src, the gather's output, behind the two summed blocks), the Sum and
-// the one-layer predictor b for fused_bf16_sum_kernel.  wb_a / wb_b as above.  false: the form does not take the launch
-// (no bf16 layer, a launch that waits for the gather by itself, buffers that are not laid out as NCF's, slabs beyond
-// LDS).  Any D, K and N otherwise.
-bool plan_fused_bf16_sum(const ChainArgs& a, const ChainArgs& b, const uint16_t* const* wb_a, const uint16_t* wb_b,
-                         const SumArgs& sum, const Done* done, MlpPlan* p) {
-  memset(p, 0, sizeof *p);
-  if (done) p->done = *done;
-  if (p->done.wait_flag) return false;
-  p->a = a; p->b = b;
-  const int na = a.n_layers, D = sum.cols;
-  if (na < 1 || na > DRS_MAX_CHAIN || b.n_layers != 1 || D < 1 || a.M < 1) return false;
-  const int wl = a.width[na];
-  const int64_t col_x = a.x - sum.src;
-  // T = [ emb0 | emb1 | ... branch input ... ], R = [ mf | branch output ] = the predictor's input
-  if (sum.col_a != 0 || sum.col_b < D || col_x < (int64_t)sum.col_b + D || col_x + a.width[0] > sum.ld || a.ldx != sum.ld ||
-      a.y != sum.dst + D || a.ldy != sum.ldd || b.x != sum.dst || b.ldx != sum.ldd || b.width[0] != D + wl || D + wl > sum.ldd)
-    return false;
-  FArgs& f = p->fa;
-  // LDS (floats): X0 | RS | P | Q
-  int off = 0;
-  f.k0 = a.width[0];
-  f.x0_ld = pad64(f.k0) + 4; f.x0_off = off; off += 16 * f.x0_ld;
-  f.rs_ld = pad64(D + wl) + 4; f.rs_off = off; off += 16 * f.rs_ld;
-  int wP = 0, wQ = 0;
-  for (int l = 0; l + 1 < na; ++l) { int& w = (l & 1) ? wQ : wP; w = pad64(a.width[l + 1]) > w ? pad64(a.width[l + 1]) : w; }
-  const int p_ld = wP + 4, q_ld = wQ + 4;
-  const int p_off = off; off += wP ? 16 * p_ld : 0;
-  const int q_off = off; off += wQ ? 16 * q_ld : 0;
-  if (sizeof(float) * (size_t)off > kFLdsBudget) return false;
-  p->lds = sizeof(float) * (size_t)off;
-
-  int n_bf16 = 0;
-  for (int l = 0; l <= na; ++l) {
-    const bool fin = l == na;
-    const ChainArgs& c = fin ? b : a;
-    const int cl = fin ? 0 : l;
-    FLayer& L = f.L[l];
-    L.W = c.W[cl]; L.Wb = fin ? wb_b : wb_a[l]; L.b = c.b[cl]; L.K = c.width[cl]; L.N = c.width[cl + 1]; L.act = c.act[cl];
-    n_bf16 += L.Wb ? 1 : 0;
-    L.in_off = fin ? f.rs_off : l == 0 ? f.x0_off : ((l - 1) & 1) ? q_off : p_off;
-    L.in_ld = fin ? f.rs_ld : l == 0 ? f.x0_ld : ((l - 1) & 1) ? q_ld : p_ld;
-    L.out_off = -1; L.out_ld = 0; L.out_pad = L.N;
-    if (fin) {
-      L.g_out = b.y; L.g_ld = b.ldy; L.g_sc1 = p->done.counter != nullptr;
-    } else if (l == na - 1) {    // behind mf; a bf16 predictor reads zeros up to its padded K
-      L.out_off = f.rs_off + D; L.out_ld = f.rs_ld; L.out_pad = wb_b ? pad64(D + wl) - D : wl;
-      L.g_out = a.y; L.g_ld = a.ldy;
-    } else {
-      L.out_off = (l & 1) ? q_off : p_off; L.out_ld = (l & 1) ? q_ld : p_ld; L.out_pad = pad64(L.N);
-    }
-  }
-  if (!n_bf16) return false;
-  f.n_layers = na + 1; f.n_bot = na; f.n_bf16 = n_bf16;
-  f.M = a.M;
-  f.T = sum.src; f.ldt = sum.ld; f.p_col0 = (int)col_x; f.p_cols = sum.col_b;
-  f.D = D; f.R = sum.dst; f.ldr = sum.ldd;
-  f.vec_t = al16(sum.src) && !(sum.ld & 3) && !(D & 3) && !(sum.col_b & 3) && !(col_x & 3) && !(f.k0 & 3);
-  f.vec_x = f.vec_t && al16(sum.dst) && !(sum.ldd & 3);
-  p->form = MlpForm::fused_bf16_sum;
-  p->grid_x = (unsigned)((a.M + 15) / 16);
-  p->grid_y = 1;
-  return true;
 }
 
 hipError_t launch_fused_bf16(const MlpPlan& p, hipStream_t s) {

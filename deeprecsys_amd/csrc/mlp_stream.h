@@ -1,6 +1,7 @@
-// Shared by the MLP translation units (mlp.hip: planning, chain / fc kernels; mlp_stream8.hip: stream_kernel;
-// mlp_stream4.hip: stream4_kernel; gemm.hip) and the engine: the launch description a stream kernel receives, the plan of
-// one MLP launch, the step-table flags, device helpers, and the launch functions each kernel translation unit exports.
+// Shared by the MLP translation units (mlp_plan.hip: planning; mlp.hip: chain / fc kernels, launch_plan; mlp_stream8.hip:
+// stream_kernel; mlp_stream4.hip: stream4_kernel; mlp_fused_bf16.hip; gemm.hip, gemm_bf16.hip) and the engine: the launch
+// description a stream kernel receives, the plan of one MLP launch, the step-table flags, device helpers, the planners
+// and the launch functions each kernel translation unit exports.
 #pragma once
 #include "drs_internal.h"
 #include "mlp_dev.h"
@@ -152,7 +153,7 @@ enum class MlpForm : int32_t {
   fused_bf16,                                        // fused_bf16_kernel (mlp_fused_bf16.hip): DLRM in one launch with its bf16 layers ("mlp_bf16_fuse" 1)
   fused_bf16_sum                                     // fused_bf16_sum_kernel (mlp_fused_bf16.hip): NCF's Sum + MLP branch + predictor likewise
 };
-// One MLP launch, decided once (mlp.hip plan_chains / plan_layer) and run as it stands (launch_plan).
+// One MLP launch, decided once (mlp_plan.hip) and run as it stands (mlp.hip launch_plan).
 struct MlpPlan {
   MlpForm form;
   unsigned grid_x, grid_y;
@@ -170,7 +171,9 @@ struct MlpPlan {
 // may the launch start before the gather is done (Done::wait_flag)?  Only the 16-row one-workgroup-per-CU stream4_kernel
 // has the late fetch of the second chain's input: the 2cu / 32-row builds have no registers to spare for it
 inline bool can_defer(const MlpPlan& p) { return p.form == MlpForm::stream4 && p.sa.wait_tile > 0; }
-// Planners (false: no form takes the launch), given the launch's Done and XSrc (null: none).  plan_chains: chain a, then
+constexpr int kFcPassCols = 128;   // columns per pass of chain_kernel / fc_kernel (8 waves x 16): fc_kernel's grid, the staged chunks
+inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// Planners (mlp_plan.hip; false: no form takes the launch), given the launch's Done and XSrc (null: none).  plan_chains: chain a, then
 // b (may be null) on the same rows, with the dot interaction or the summed input between them.  plan_layer: one layer.
 bool plan_chains(const ChainArgs& a, const ChainArgs* b, const Tune& tune, const Done* done, const XSrc* xs,
                  const DotArgs* dot, const SumArgs* sum, MlpPlan* p);
@@ -184,7 +187,7 @@ bool gemm_plan(const Tune& tune, MlpPlan* p);   // gemm.hip: the GEMM form of th
 hipError_t launch_gemm(const MlpPlan& p, const float* zero, hipStream_t s);
 bool gemm_bf16_plan(const Tune& tune, MlpPlan* p);   // gemm_bf16.hip: the bf16 GEMM form of the layer p->a with the twin p->wb
 hipError_t launch_gemm_bf16(const MlpPlan& p, hipStream_t s);
-// mlp_fused_bf16.hip: bottom chain a, the interaction (dot, or null: cat) and top chain b in fused_bf16_kernel; wb_a / wb_b:
+// fused_bf16_kernel (mlp_fused_bf16.hip): bottom chain a, the interaction (dot, or null: cat) and top chain b; wb_a / wb_b:
 // per layer its bf16 twin (a bf16 layer) or null (an fp32 layer).  false: the form does not take the launch.
 bool plan_fused_bf16(const ChainArgs& a, const ChainArgs& b, const uint16_t* const* wb_a, const uint16_t* const* wb_b,
                      const DotArgs* dot, const Done* done, const XSrc* xs, MlpPlan* p);

@@ -1,7 +1,7 @@
 """The MLP launch planner's boundary catalogue (a plain module: no tests in it).
 
-csrc/mlp.hip (plan_chains / plan_layer / stream_plan / chain_plan / pick_kc), csrc/gemm.hip (gemm_plan) and
-csrc/engine_dispatch.hip (run_mlp / fused_plan / mlp_ncf / mlp_dense) pick the kernel form of every MLP launch from about a
+csrc/mlp_plan.hip (plan_chains / plan_layer / stream_plan / chain_plan / pick_kc), csrc/gemm.hip (gemm_plan) and
+csrc/engine_dispatch.hip (run_mlp / dlrm_one_launch / mlp_ncf / mlp_dense) pick the kernel form of every MLP launch from about a
 dozen thresholds.  CASES holds one small model on each side of every one of them (DESIGN.md 3.1 lists the thresholds and
 names the cases).  The rule numbers:
 
@@ -71,7 +71,7 @@ _case("depth_6_6_fused", "dlrm_cat", 16, 2, "16-32-32-32-32-32-16", "48-32-32-32
 # ... with the dot interaction between the chains (F = 8: 16 + 28 = 44 columns)
 _case("depth_6_6_fused_dot", "dlrm_dot", 16, 7, "16-32-32-32-32-32-16", "44-32-32-32-32-32-1", 1, "at",
       [S4 + " .. , 12 layers, dot"], ["chain_kernel", "interact_dot_kernel"], launches=1)
-# 6 + 7: fused_plan refuses (nt > 6); bottom chain of 6, top as a run of 6 and the 7th layer alone
+# 6 + 7: dlrm_one_launch refuses (nt > 6); bottom chain of 6, top as a run of 6 and the 7th layer alone
 _case("depth_6_7_unfused", "dlrm_cat", 16, 2, "16-32-32-32-32-32-16", "48-32-32-32-32-32-32-1", 1, "beyond",
       [S4 + " .. , 6 layers", S4 + " .. , 1 layers"], ["12 layers", "13 layers", ", 7 layers"], launches=3, rows=ROWS_ALL)
 # 7-layer bottom MLP: runs of 6 and 1 (through s.H), then the 2-layer top chain
