@@ -43,6 +43,7 @@ struct SlsArgs {
   int32_t* err;               // device error word: bit0 = index out of range
   uint64_t* ts;               // optional [2 * gridDim.x] start/end wall_clock64() per workgroup
   int32_t nt;                 // fused DIN launch: table rows by non-temporal loads ("sls_nt"; set by launch_din_fused)
+  int32_t pool;               // "sls_pool": 0 a bag's sum | 1 its mean, the finished sum / (float)length (sls.hip pool_finish)
   // int8 rowwise tables in the line-packed layout ("table_int8_lines", I8Lines below): row r starts r * PR + (r / n) * ln_pad
   // pieces into its table, r / n == ln_mul ? umulhi(r, ln_mul) >> ln_shift : r.  ln_pad == 0: every other layout.
   uint32_t ln_mul, ln_shift, ln_pad;

@@ -183,6 +183,7 @@ struct drs_engine {
   size_t tables_bytes = 0;
   int mlp_dtype = DRS_MLP_FP32;     // "mlp_dtype": DRS_MLP_BF16 -- the FC layers with K >= 64 and N >= 64 on the bf16 matrix cores (bf16_layer)
   int mlp_bf16_fuse = 0;            // "mlp_bf16_fuse": with "mlp_dtype" 2, DLRM's and NCF's one-launch forms keep their bf16 layers (mlp_fused_bf16.hip)
+  int sls_pool = 0;                 // "sls_pool": 1 -- every bag's pooled vector is its mean, the gather's fp32 sum / (float)length (SlsArgs::pool)
   int table_dtype = DRS_TABLE_FP32; // "table_dtype": element type of the arena (DRS_TABLE_*); sums and outputs stay fp32
   int table_int8_lines = 0;         // "table_int8_lines": an int8 rowwise arena keeps every row inside one 128-byte line (drs_internal.h I8Lines)
   I8Lines i8l;                      // ... the layout of the arena in use: i8_lines(D, table_int8_lines) while it is int8 rowwise, else plain

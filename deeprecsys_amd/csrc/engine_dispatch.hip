@@ -315,6 +315,7 @@ static int32_t launch_gather(SetCtx& x) {
   a.T = e->T; a.D = e->D; a.err = reinterpret_cast<int32_t*>(s.d_err);
   a.ts = prof ? s.d_ts : nullptr;
   a.ln_mul = e->i8l.mul; a.ln_shift = e->i8l.shift; a.ln_pad = e->i8l.pad;   // ("table_int8_lines": zeros for every other layout)
+  a.pool = e->sls_pool;      // ("sls_pool": DIN and DIEN refuse 1, so the fused DIN launch never sees it)
   // short bags (W&D / NCF: one lookup per table) take the sequential lane-group-per-bag form (plan_sls); the queries'
   // own bag lengths count here, also when "sls_uniform" 0 keeps them from the kernels
   bool short_bags = true;
@@ -851,6 +852,7 @@ int32_t drs_sls(drs_handle e, const float* d_W, int64_t rows, int32_t D, const i
     a.q.n_q = 1; a.q.vstart[1] = (int32_t)n_bags; a.q.cum[1] = (int32_t)n_bags; a.q.bs[0] = (int32_t)n_bags;
     a.idx[0] = d_idx; a.off[0] = d_off; a.uniform_len[0] = -1;
     a.out = d_out; a.ld_out = D; a.col0 = 0; a.T = 1; a.D = D; a.err = d_err; a.ts = nullptr;
+    a.pool = e->sls_pool;    // the operator follows the handle: SparseLengthsMean under "sls_pool" 1
     r = launch_sls(a, plan_sls(a, exact_order != 0, false, e->tune, DRS_TABLE_FP32), e->tune, s.stream);
   }
   if (r == hipSuccess) r = hipStreamSynchronize(s.stream);

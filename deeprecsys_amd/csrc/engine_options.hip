@@ -190,6 +190,17 @@ int32_t set_mlp_dtype(drs_engine* e, int64_t value) {
   return DRS_OK;
 }
 
+int32_t set_sls_pool(drs_engine* e, int64_t value) {
+  // Mean pooling: the gather kernels divide every bag's finished sum by its length (sls.hip pool_finish).  One field that
+  // every later launch copies into its SlsArgs: nothing is converted, allocated or chosen again.  DIN and DIEN
+  // pool by sum only (the fused DIN launch has a gather of its own, din.hip): refused, like their other result-changing options.
+  if (value == e->sls_pool) return DRS_OK;
+  if (e->kind == DRS_MODEL_DIN || e->kind == DRS_MODEL_DIEN)
+    return fail(e, DRS_ERR_UNSUPPORTED, "sls_pool %lld: DIN and DIEN pool their bags by sum only", (long long)value);
+  e->sls_pool = (int)value;
+  return DRS_OK;
+}
+
 int64_t arena_in_use(drs_engine* e) {
   return (int64_t)(std::find_if(e->arenas.begin(), e->arenas.end(), [&](const Arena& a) { return a.p == e->tables; }) - e->arenas.begin());
 }
@@ -201,6 +212,8 @@ const OptDesc kOptions[] = {
     OPT("sls_bpw", 0, 4, [](int64_t v) { return v != 3; }, 0, tune.sls_bpw),
     OPT("sls_nt", 0, 1, nullptr, O_BOOL, tune.sls_nt),
     OPT("sls_one", 0, 64, [](int64_t v) { return v == 0 || v == 1 || v == 16 || v == 64; }, 0, tune.sls_one),
+    // 1: SparseLengthsMean / EmbeddingBag(mode="mean") -- the same gather form's fp32 sum, divided by the bag's length
+    {"sls_pool", 0, 1, nullptr, O_SYNC, [](drs_engine* e) -> int64_t { return e->sls_pool; }, nullptr, set_sls_pool},
     OPT("din_fused", 0, 1, nullptr, O_BOOL, din_fused),
     OPT("din_pipe", 0, 1, nullptr, O_BOOL, tune.din_pipe),
     OPT("din_s", 0, 4, [](int64_t v) { return v != 3; }, 0, tune.din_s),

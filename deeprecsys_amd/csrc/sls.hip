@@ -54,6 +54,22 @@ __device__ __forceinline__ float4 vsel(bool keep, const float4& v) {
   return make_float4(keep ? v.x : 0.f, keep ? v.y : 0.f, keep ? v.z : 0.f, keep ? v.w : 0.f);
 }
 
+// "sls_pool" 1 (SlsArgs::pool, mean pooling): a bag's FINISHED fp32 sum -- after every cross-lane combine, never a partial
+// one -- is divided by its length just before the store: one IEEE fp32 division per element (v_div_scale / v_div_fmas /
+// v_div_fixup, correctly rounded, subnormal quotients included), never a multiplication by a reciprocal, which differs
+// from torch's EmbeddingBag(mode="mean") on the CPU in about a quarter of the elements.  An empty bag divides its +0.0
+// by 1: it stays +0.0.  pool is a kernel argument, i.e. wave-uniform: a scalar branch around the epilogue, and with 0
+// the sum is stored as it is.
+__device__ __forceinline__ float pool_finish(float sum, int pool, int len) {
+  return pool ? __fdiv_rn(sum, len > 0 ? (float)len : 1.0f) : sum;
+}
+__device__ __forceinline__ void pool_finish(float4& acc, int pool, int len) {
+  if (pool) {
+    const float d = len > 0 ? (float)len : 1.0f;
+    acc = make_float4(__fdiv_rn(acc.x, d), __fdiv_rn(acc.y, d), __fdiv_rn(acc.z, d), __fdiv_rn(acc.w, d));
+  }
+}
+
 constexpr int kChunk = 128;  // indices staged in LDS per bag per round
 
 // table rows are read once per launch (~1 % reuse inside a batch): "sls_nt" reads them with the
@@ -330,6 +346,7 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
     for (int m = G; m < 64; m <<= 1) vadd(acc, vshfl_xor(acc, m));
   }
   if (bad) atomicOr(a.err, 1);
+  pool_finish(acc, a.pool, len);   // (behind the loops and the butterfly: the pipeline arms above keep their waitcnt counts)
   if (bag_ok && col_ok && (EXACT || g == 0)) {
     float* o = a.out + (int64_t)vrow * a.ld_out + a.col0 + (int64_t)t * D + col;
     *reinterpret_cast<float4*>(o) = acc;
@@ -397,6 +414,7 @@ __global__ __launch_bounds__(64) void sls_one_kernel(SlsArgs a, int tiles) {
       if (vr[j] >= 0) {
         float4 o = vzero4();                                  // 0.0f + row: the one-row bag's value
         E::add(o, kp[j] != 0, v[j], sb[j]);
+        pool_finish(o, a.pool, 1);                            // a one-row bag's mean: x / 1.0f == x, the same bits
         *reinterpret_cast<float4*>(out + (int64_t)vr[j] * a.ld_out) = o;
       }
   }
@@ -539,6 +557,8 @@ __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_
     for (int m = G; m < 64; m <<= 1) vadd(acc[k], vshfl_xor(acc[k], m));
 
   if (bad) atomicOr(a.err, 1);
+#pragma unroll
+  for (int k = 0; k < BPW; ++k) pool_finish(acc[k], a.pool, L);
   // every group holds every sum after the butterfly; group 0 stores them, one 128..512-B row per
   // bag.  (Letting group k store bag k needs acc[g]: the optimiser turns that select chain into a
   // dynamically indexed array, i.e. SCRATCH memory -- which capped the BPW > 1 variants at half
@@ -664,6 +684,8 @@ __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
     for (int m = G; m < 64; m <<= 1) vadd(acc[k], vshfl_xor(acc[k], m));
 
   if (bad) atomicOr(a.err, 1);
+#pragma unroll
+  for (int k = 0; k < BPW; ++k) pool_finish(acc[k], a.pool, L);
   // lane group k stores bag k (every group holds every sum after the butterfly)
   if (col_ok && g < BPW) {
     float4 o4 = acc[0];
@@ -736,7 +758,7 @@ __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int c = c0 + lane + 64 * k;
-      if (c < D) o[c] = acc[k];
+      if (c < D) o[c] = pool_finish(acc[k], a.pool, end - beg);
     }
   }
   if (bad) atomicOr(a.err, 1);
@@ -751,7 +773,10 @@ int lanes_per_row(int D) { return D <= 8 ? 2 : D <= 16 ? 4 : D <= 32 ? 8 : D <= 
 // the launch for tables of element type E (F32 / F16 / BF16 / I8 / I8L): the plan's dispatch-log line, then its instance
 template <class E>
 hipError_t launch_sls_e(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hipStream_t s, hipEvent_t stop) {
-  const char* dt = E::tag;                // dispatch log: "" for fp32, else the dtype token
+  // dispatch log: the dtype token ("" for fp32), then "mean" under "sls_pool" 1 (nothing for sum)
+  char tags[16];
+  snprintf(tags, sizeof tags, "%s%s%s", E::tag, *E::tag && a.pool ? "," : "", a.pool ? "mean" : "");
+  const char* dt = tags;
   const char* sep = *dt ? "," : "";
   const long long wg = (long long)p.grid;
   if (!wg && (p.form == SlsForm::any || p.form == SlsForm::one)) return hipSuccess;   // (an empty launch of these is not logged)

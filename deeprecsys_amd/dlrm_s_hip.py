@@ -73,6 +73,17 @@ def _table_int8_lines(args):
     return v
 
 
+_SLS_POOLS = {"sum": N.POOL_SUM, "mean": N.POOL_MEAN}
+
+
+def _sls_pool(args):
+    """--accel_sls_pool -> the engine's "sls_pool" value (sum when the flag is absent)."""
+    name = str(getattr(args, "accel_sls_pool", "sum") or "sum")
+    if name not in _SLS_POOLS:
+        raise ValueError("--accel_sls_pool %r: one of %s" % (name, ", ".join(_SLS_POOLS)))
+    return _SLS_POOLS[name]
+
+
 def _init_table(n, m):
     # models/dlrm_s_caffe2.py:297-299
     return np.random.uniform(low=-np.sqrt(1 / n), high=np.sqrt(1 / n), size=(n, m)).astype(np.float32)
@@ -127,6 +138,7 @@ class _HipNet(object):
         mlp_dtype = _mlp_dtype(a)
         bf16_fuse = _mlp_bf16_fuse(a)
         int8_lines = _table_int8_lines(a)
+        pool = _sls_pool(a)
         def make(n_slots):
             eng = N.Engine(self.kind, self.ln_emb, self.m_spa, ln_bot_cfg, ln_top_cfg,
                            interaction_op=interaction_op, interaction_itself=itself,
@@ -149,6 +161,9 @@ class _HipNet(object):
             # --accel_mlp_bf16_fuse: behind it, and only when asked for
             if bf16_fuse:
                 eng.set_option("mlp_bf16_fuse", bf16_fuse)
+            # --accel_sls_pool mean: every bag's pooled vector is its mean (only when asked for: a sum engine is never told)
+            if pool != N.POOL_SUM:
+                eng.set_option("sls_pool", pool)
             return eng
         eng = make(self._num_slots())
         if int(getattr(a, "accel_slots", 0) or 0) <= 0 and eng.get_option("preferred_slots") != eng.num_slots:

@@ -265,7 +265,8 @@ int32_t drs_interaction_width(drs_handle h, int32_t* num_int);
  * drs_sls  == SparseLengthsSum([tbl, idx, len]) (models/dlrm_s_caffe2.py:317-325)
  *   out[b,:] = sum over the bag's indices of W[idx,:], fp32, sequential in
  *   index order when exact_order != 0 (bit-identical to the Caffe2 CPU
- *   perfkernel); empty bag -> zeros.                                           */
+ *   perfkernel); empty bag -> zeros.  Under the handle's "sls_pool" 1 it is
+ *   SparseLengthsMean: that sum divided by (float)len, an empty bag -> zeros.   */
 int32_t drs_sls(drs_handle h, const float* d_W, int64_t rows, int32_t D,
                 const int32_t* d_idx, const int32_t* d_len, int64_t n_bags,
                 int64_t n_idx, float* d_out /*[n_bags, D]*/, int32_t exact_order);
@@ -285,9 +286,13 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  * Results never depend on an option except where noted (sls_exact: the gather's fp32 summation order; table_dtype:
  * the tables are stored in fp16 / bf16, rounded to nearest even, or quantized to 8 bits per value with a per-row scale
  * and bias, and still summed in fp32 into fp32 outputs; mlp_dtype: the FC layers with K >= 64 and N >= 64 take bf16
- * operands on the matrix cores, accumulated in fp32 -- the operator-level FC call follows the handle's setting).
+ * operands on the matrix cores, accumulated in fp32 -- the operator-level FC call follows the handle's setting;
+ * sls_pool: a bag's pooled vector is its mean, the gather's fp32 sum / (float)length -- drs_sls follows the handle too).
  * The product library takes the keys below; unknown key or value -> DRS_ERR_BAD_ARG.
  *   gather        "sls_exact" 0|1 (1: sequential order, bit-identical to Caffe2's SparseLengthsSum)
+ *                 "sls_pool" 0|1 (1: mean pooling, SparseLengthsMean / EmbeddingBag(mode="mean") -- the same form's fp32 sum
+ *                 divided by (float)len, one correctly rounded division per element, an empty bag stays +0.0; DLRM, W&D,
+ *                 MT-WnD and NCF only; set before or after the table options; same launch forms, same drs_gather_bytes)
  *                 "sls_flat" 0|1|2   "sls_bpw" 0|1|2|4   "sls_nt" 0|1   "sls_one" 0|1|16|64
  *                 "din_fused" 0|1   "din_pipe" 0|1   "din_s" 0|1|2|4   "din_nt" 0|1
  *                 "dien_mfma" 0|1|2|3   "dien_fuse_top" 0|1
