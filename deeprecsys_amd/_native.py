@@ -19,6 +19,7 @@ MODEL_DLRM, MODEL_WND, MODEL_NCF, MODEL_MTWND, MODEL_DIN, MODEL_DIEN = 0, 1, 2, 
 INTERACT_DOT, INTERACT_CAT = 0, 1
 TABLE_FP32, TABLE_FP16, TABLE_BF16 = 0, 1, 2   # option "table_dtype": element type of the stored tables
 TABLE_INT8_ROWWISE = 8                          # ... 8-bit codes with an fp32 scale and bias per row (Caffe2's Fused8BitRowwise)
+TABLE_INT4_ROWWISE = 9                          # ... 4-bit codes with an fp16 scale and bias per row (torch's embedding_bag_4bit_prepack; even D)
 POOL_SUM, POOL_MEAN = 0, 1                      # option "sls_pool": a bag's pooled vector is its sum | its mean (the fp32 sum / length)
 MLP_FP32, MLP_BF16 = 0, 2                       # option "mlp_dtype": arithmetic of the FC layers with K, N >= 64 (bf16 operands, fp32 accumulation)
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2

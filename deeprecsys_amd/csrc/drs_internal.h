@@ -124,16 +124,21 @@ SlsPlan plan_sls(const SlsArgs& a, bool exact, bool short_bags, const Tune& tune
 hipError_t launch_sls(const SlsArgs& a, const SlsPlan& plan, const Tune& tune, hipStream_t stream,
                       hipEvent_t stop_event = nullptr);
 // "table_dtype" layouts.  Stored bytes of one row: D elements of 4 (fp32) or 2 (fp16 / bf16) bytes; int8 rowwise: D codes,
-// zero padding to round_up(D, 8), fp32 scale, fp32 bias (every row 8-byte aligned)
+// zero padding to round_up(D, 8), fp32 scale, fp32 bias (every row 8-byte aligned); int4 rowwise: D / 2 code bytes, zero
+// padding to round_up(D / 2, 4), fp16 scale, fp16 bias (every row 4-byte aligned; D even)
+inline bool table_rowwise(int dtype) { return dtype == DRS_TABLE_INT8_ROWWISE || dtype == DRS_TABLE_INT4_ROWWISE; }
 inline int64_t table_row_stride(int dtype, int64_t D) {
+  if (dtype == DRS_TABLE_INT4_ROWWISE) return (D / 2 + 3) / 4 * 4 + 4;
   return dtype == DRS_TABLE_INT8_ROWWISE ? (D + 7) / 8 * 8 + 8 : D * (dtype == DRS_TABLE_FP32 ? 4 : 2);
 }
-// bytes a gathered row moves (the algorithmic count of drs_gather_bytes and of the launch-form choice): int8 rowwise D + 8
+// bytes a gathered row moves (the algorithmic count of drs_gather_bytes and of the launch-form choice): int8 rowwise D + 8,
+// int4 rowwise D / 2 + 4
 inline int64_t table_row_bytes(int dtype, int64_t D) {
+  if (dtype == DRS_TABLE_INT4_ROWWISE) return D / 2 + 4;
   return dtype == DRS_TABLE_INT8_ROWWISE ? D + 8 : table_row_stride(dtype, D);
 }
-// what a table offset (SlsArgs::tab_off, drs_engine::tab_off) counts: elements (4 / 2 bytes), or bytes for int8 rowwise
-inline int64_t table_unit_bytes(int dtype) { return dtype == DRS_TABLE_FP32 ? 4 : dtype == DRS_TABLE_INT8_ROWWISE ? 1 : 2; }
+// what a table offset (SlsArgs::tab_off, drs_engine::tab_off) counts: elements (4 / 2 bytes), or bytes for the rowwise types
+inline int64_t table_unit_bytes(int dtype) { return dtype == DRS_TABLE_FP32 ? 4 : table_rowwise(dtype) ? 1 : 2; }
 
 // "table_int8_lines": int8 rowwise rows that never cross a 128-byte line.  When S = table_row_stride(8, D) < 128 does not
 // divide 128, n = 128 / S rows share a line: row r starts at byte (r / n) * 128 + (r % n) * S of its table and the last
@@ -329,15 +334,16 @@ hipError_t probe_latency(const void* base, size_t chunk_bytes, int n_chunks, int
 hipError_t launch_fill_uniform(float* W, int64_t n, int32_t t, float lo, float hi, uint64_t seed,
                                hipStream_t stream);
 // the same values of a table of rows x D, stored as `dtype` (DRS_TABLE_*; fp32: launch_fill_uniform; fp16 / bf16: rounded;
-// int8 rowwise: each row quantized, n = I8Lines::n of the table's layout)
+// int8 / int4 rowwise: each row quantized, n = I8Lines::n of an int8 table's layout)
 hipError_t launch_fill_uniform_dtype(void* W, int dtype, int64_t rows, int D, int32_t t, float lo, float hi, uint64_t seed,
                                      hipStream_t stream, int32_t n = 0);
 // n table elements of type src_dtype -> dst_dtype (rounded to nearest even; widening is exact); fp32 / fp16 / bf16 only
 hipError_t launch_convert_table(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, hipStream_t stream);
-// rows x D of one table, into or out of int8 rowwise: quantized per row, each row's value fmaf(scale, q, 0.0f + bias)
-// rounded to dst_dtype, or (int8 on both sides) the rows' bytes moved from one layout to the other.  An int8 side is the
-// TABLE's base, in the layout n_src / n_dst (I8Lines::n), and the rows are its rows first .. first + rows - 1 of `total`
-// (the last row of a table clears the rest of its line); the other side is the rows themselves, D elements each.
+// rows x D of one table, into or out of int8 / int4 rowwise: quantized per row, each row's value fmaf(scale, q, 0.0f + bias)
+// rounded to dst_dtype (or quantized again, between the two rowwise types), or (int8 on both sides) the rows' bytes moved
+// from one layout to the other.  A rowwise side is the TABLE's base -- int8: in the layout n_src / n_dst (I8Lines::n); int4:
+// always plain -- and the rows are its rows first .. first + rows - 1 of `total` (the last row of an int8 table clears the
+// rest of its line); the other side is the rows themselves, D elements each.
 hipError_t launch_convert_rows(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t rows, int D, hipStream_t stream,
                                int32_t n_src = 0, int32_t n_dst = 0, int64_t first = 0, int64_t total = -1);
 

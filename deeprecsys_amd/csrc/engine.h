@@ -5,7 +5,8 @@
 // HBM layout (all hipMalloc'ed once in drs_create / first use):
 //   tables   one arena, rows row-major ("table_dtype": rows*D fp32, fp16 or bf16, table t at a 64-element aligned offset;
 //            int8 rowwise: rows of round_up(D, 8) + 8 bytes, table t at a 256-byte aligned offset; "table_int8_lines" 1:
-//            128 / S rows to a 128-byte line where S does not divide 128 -- table_layout)
+//            128 / S rows to a 128-byte line where S does not divide 128; int4 rowwise: rows of round_up(D / 2, 4) + 4
+//            bytes, table t at a 256-byte aligned offset -- table_layout)
 //   weights  one arena: all biases back to back (layer order, padded to 4 floats), then per
 //            layer W [N, K] dense row-major (as fed by the reference)
 //   batches  per staged batch: dense [max_batch, m_den] f32 | idx [T, cap] i32 |

@@ -227,8 +227,8 @@ size_t drs::eng::table_layout(const drs_engine* e, int dtype, std::vector<int64_
   off->resize((size_t)e->T);
   for (int t = 0; t < e->T; ++t) {
     (*off)[(size_t)t] = o;
-    o += dtype == DRS_TABLE_INT8_ROWWISE ? round_up(i8_table_bytes(e->rows[t], table_row_stride(dtype, e->D), n), 256)   // bytes
-                                         : round_up(e->rows[t] * e->D, 64);                             // elements
+    o += table_rowwise(dtype) ? round_up(i8_table_bytes(e->rows[t], table_row_stride(dtype, e->D), n), 256)   // bytes (int4: n == 0, rows * S)
+                              : round_up(e->rows[t] * e->D, 64);                                    // elements
   }
   return (size_t)o * (size_t)table_unit_bytes(dtype);
 }
@@ -602,7 +602,7 @@ int32_t drs_set_table(drs_handle e, int32_t t, const float* h_W, int64_t rows) {
   if (e->table_dtype == DRS_TABLE_FP32) {
     HIP_TRY(e, hipMemcpy(e->tables + e->tab_off[t], h_W, sizeof(float) * (size_t)rows * e->D, hipMemcpyHostToDevice));
   } else {
-    // half / int8 tables: the fp32 rows cross the bus through a staging buffer, chunk by chunk (whole rows of up to 16 M
+    // half / int8 / int4 tables: the fp32 rows cross the bus through a staging buffer, chunk by chunk (whole rows of up to 16 M
     // elements), and are rounded or quantized on the device
     const int dt = e->table_dtype;
     const int64_t D = e->D, chunk = std::min<int64_t>(rows, std::max<int64_t>(((int64_t)16 << 20) / D, 1));
@@ -614,9 +614,9 @@ int32_t drs_set_table(drs_handle e, int32_t t, const float* h_W, int64_t rows) {
       const int64_t m = std::min(chunk, rows - i);
       r = hipMemcpy(stage, h_W + i * D, sizeof(float) * (size_t)(m * D), hipMemcpyHostToDevice);
       if (r == hipSuccess)
-        // (int8 rowwise: the kernel places rows i .. i + m - 1 of the table itself -- a chunk may start inside a line)
-        r = dt == DRS_TABLE_INT8_ROWWISE ? launch_convert_rows(stage, DRS_TABLE_FP32, dst, dt, m, (int)D, nullptr, 0, e->i8l.n, i, rows)
-                                         : launch_convert_table(stage, DRS_TABLE_FP32, dst + i * table_row_stride(dt, D), dt, m * D, nullptr);
+        // (rowwise: the kernel places rows i .. i + m - 1 of the table itself -- an int8 chunk may start inside a line)
+        r = table_rowwise(dt) ? launch_convert_rows(stage, DRS_TABLE_FP32, dst, dt, m, (int)D, nullptr, 0, e->i8l.n, i, rows)
+                              : launch_convert_table(stage, DRS_TABLE_FP32, dst + i * table_row_stride(dt, D), dt, m * D, nullptr);
       if (r == hipSuccess) r = hipStreamSynchronize(nullptr);    // (before the next chunk overwrites the staging buffer)
     }
     (void)hipFree(stage);

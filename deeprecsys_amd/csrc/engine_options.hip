@@ -94,13 +94,13 @@ int32_t set_table_spacer(drs_engine* e, int64_t value) {
 // "table_dtype" and "table_int8_lines": the arena in use becomes one of element type dt, int8 rows laid out by `lines`
 int32_t convert_tables(drs_engine* e, int dt, int lines) {
   // The tables in use are converted on the device into a new arena of the new element type (round to nearest even;
-  // widening is exact; int8 rowwise: each row quantized, each row's value written out, or its bytes moved to the other
+  // widening is exact; int8 / int4 rowwise: each row quantized, each row's value written out, or its bytes moved to the other
   // layout), which then replaces the old arena and every other placement candidate.  Refused (DRS_ERR_OOM, nothing changes)
   // when the new arena would not leave 3/4 of the device's memory free -- the rule of "table_placement" -1.  The launch
   // forms that depend on the gathered bytes are chosen again (choose_launch_forms): set these options first.
   const int from = e->table_dtype;
   const I8Lines to_l = dt == DRS_TABLE_INT8_ROWWISE ? i8_lines(e->D, lines) : I8Lines(), from_l = e->i8l;
-  const bool rowwise = dt == DRS_TABLE_INT8_ROWWISE || from == DRS_TABLE_INT8_ROWWISE;
+  const bool rowwise = table_rowwise(dt) || table_rowwise(from);
   // the gather kernels address a row in 32-bit counts of 4-byte pieces: rows * S / 4 < 2^32 per int8 table, or
   // ceil(rows / n) * 32 < 2^32 when n rows share a line
   if (dt == DRS_TABLE_INT8_ROWWISE)
@@ -108,6 +108,14 @@ int32_t convert_tables(drs_engine* e, int dt, int lines) {
       if (i8_table_bytes(e->rows[t], table_row_stride(dt, e->D), to_l.n) / 4 >= (1ll << 32))
         return fail(e, DRS_ERR_UNSUPPORTED, "table_dtype 8: table %d (%lld rows of %lld bytes%s) is too large to address", t,
                     (long long)e->rows[t], (long long)table_row_stride(dt, e->D), to_l.n ? ", line-packed" : "");
+  // int4 rowwise: two codes to a byte, so even D only; rows * S / 2 < 2^32 per table (2-byte pieces)
+  if (dt == DRS_TABLE_INT4_ROWWISE) {
+    if (e->D & 1) return fail(e, DRS_ERR_UNSUPPORTED, "table_dtype 9: D = %d is odd (two 4-bit codes share a byte)", e->D);
+    for (int t = 0; t < e->T; ++t)
+      if (e->rows[t] * table_row_stride(dt, e->D) / 2 >= (1ll << 32))
+        return fail(e, DRS_ERR_UNSUPPORTED, "table_dtype 9: table %d (%lld rows of %lld bytes) is too large to address", t,
+                    (long long)e->rows[t], (long long)table_row_stride(dt, e->D));
+  }
   std::vector<int64_t> off;
   const size_t bytes = table_layout(e, dt, &off, lines);
   size_t free_b = 0, total_b = 0;
@@ -259,7 +267,7 @@ const OptDesc kOptions[] = {
 #else
     OPT("table_alloc", 0, 2, nullptr, 0, table_alloc),
 #endif
-    {"table_dtype", 0, 8, [](int64_t v) { return v <= DRS_TABLE_BF16 || v == DRS_TABLE_INT8_ROWWISE; }, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_dtype; }, nullptr, set_table_dtype},
+    {"table_dtype", 0, 9, [](int64_t v) { return v <= DRS_TABLE_BF16 || v == DRS_TABLE_INT8_ROWWISE || v == DRS_TABLE_INT4_ROWWISE; }, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_dtype; }, nullptr, set_table_dtype},
     // an int8 rowwise arena keeps every row inside one 128-byte line: 128 / S rows to a line where S < 128 does not divide 128
     {"table_int8_lines", 0, 1, nullptr, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_int8_lines; }, nullptr, set_table_int8_lines},
     {"table_spacer", 0, kBig, nullptr, 0, [](drs_engine* e) -> int64_t { return (int64_t)e->spacers.size() << 30; }, nullptr, set_table_spacer},

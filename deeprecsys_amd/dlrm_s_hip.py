@@ -35,7 +35,8 @@ def _ints(s):
     return np.array([int(x) for x in str(s).split("-")], dtype=int)
 
 
-_TABLE_DTYPES = {"fp32": N.TABLE_FP32, "fp16": N.TABLE_FP16, "bf16": N.TABLE_BF16, "int8_rowwise": N.TABLE_INT8_ROWWISE}
+_TABLE_DTYPES = {"fp32": N.TABLE_FP32, "fp16": N.TABLE_FP16, "bf16": N.TABLE_BF16, "int8_rowwise": N.TABLE_INT8_ROWWISE,
+                 "int4_rowwise": N.TABLE_INT4_ROWWISE}
 
 
 def _table_dtype(args):

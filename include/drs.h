@@ -79,8 +79,11 @@ enum { DRS_INTERACT_DOT = 0, DRS_INTERACT_CAT = 1 };
 
 /* element type of the stored embedding tables (option "table_dtype"); sums and outputs are fp32 in every case.
  * DRS_TABLE_INT8_ROWWISE: Caffe2's Fused8BitRowwise -- a row is D uint8 codes, zero padding to a multiple of 8 bytes, an
- * fp32 scale and an fp32 bias; a row's value is fmaf(scale, q, 0.0f + bias) */
-enum { DRS_TABLE_FP32 = 0, DRS_TABLE_FP16 = 1, DRS_TABLE_BF16 = 2, DRS_TABLE_INT8_ROWWISE = 8 };
+ * fp32 scale and an fp32 bias; a row's value is fmaf(scale, q, 0.0f + bias).
+ * DRS_TABLE_INT4_ROWWISE: FBGEMM's Fused4BitRowwise, torch's embedding_bag_4bit_prepack -- a row is D / 2 bytes of 4-bit
+ * codes (column 2j the low nibble of byte j), zero padding to a multiple of 4 bytes, an fp16 scale and an fp16 bias; the
+ * same value formula; D must be even */
+enum { DRS_TABLE_FP32 = 0, DRS_TABLE_FP16 = 1, DRS_TABLE_BF16 = 2, DRS_TABLE_INT8_ROWWISE = 8, DRS_TABLE_INT4_ROWWISE = 9 };
 
 /* arithmetic of the wide FC layers (option "mlp_dtype").  DRS_MLP_BF16: a layer of the bottom, top, final or task MLP
  * with K >= 64 and N >= 64 rounds its input and its weights to bf16 (nearest even, NaN stays NaN) and accumulates the
@@ -304,9 +307,11 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  *   streams, host "shared_stream" 0|1|2   "mlp_streams" 1..8   "host_threads" -1..64
  *                 "zero_copy_inputs" 1|2|3   "out_dma" bytes   "dispatch_log" 0|1
  *   table arena   "table_placement" -1|-2|k   "table_alloc" 0|1|2   "table_spacer" bytes
- *                 "table_dtype" 0|1|2|8 (DRS_TABLE_FP32 | DRS_TABLE_FP16 | DRS_TABLE_BF16 | DRS_TABLE_INT8_ROWWISE:
- *                 converts the arena in use; DLRM, W&D, MT-WnD and NCF only.  8: FBGEMM's embedding_bag_byte_prepack
- *                 quantization, and with sls_exact 1 the pooled sums of embedding_bag_byte_rowwise_offsets, bit for bit)
+ *                 "table_dtype" 0|1|2|8|9 (DRS_TABLE_FP32 | DRS_TABLE_FP16 | DRS_TABLE_BF16 | DRS_TABLE_INT8_ROWWISE |
+ *                 DRS_TABLE_INT4_ROWWISE: converts the arena in use; DLRM, W&D, MT-WnD and NCF only.  8: FBGEMM's
+ *                 embedding_bag_byte_prepack quantization, and with sls_exact 1 the pooled sums of
+ *                 embedding_bag_byte_rowwise_offsets, bit for bit.  9: embedding_bag_4bit_prepack's quantization and
+ *                 embedding_bag_4bit_rowwise_offsets' sums likewise; even D only, DRS_ERR_UNSUPPORTED otherwise)
  *                 "table_int8_lines" 0|1 (1 with "table_dtype" 8: no int8 row crosses a 128-byte line -- 128 / S rows of
  *                 S = round_up(D, 8) + 8 bytes share a line where S < 128 does not divide 128; set before or after
  *                 "table_dtype", the same arena; same results)
