@@ -44,8 +44,8 @@ struct SlsArgs {
   uint64_t* ts;               // optional [2 * gridDim.x] start/end wall_clock64() per workgroup
   int32_t nt;                 // fused DIN launch: table rows by non-temporal loads ("sls_nt"; set by launch_din_fused)
   int32_t pool;               // "sls_pool": 0 a bag's sum | 1 its mean, the finished sum / (float)length (sls.hip pool_finish)
-  // int8 rowwise tables in the line-packed layout ("table_int8_lines", I8Lines below): row r starts r * PR + (r / n) * ln_pad
-  // pieces into its table, r / n == ln_mul ? umulhi(r, ln_mul) >> ln_shift : r.  ln_pad == 0: every other layout.
+  // int8 / int4 rowwise tables in the line-packed layout ("table_int8_lines" / "table_int4_lines", I8Lines below): row r
+  // starts r * PR + (r / n) * ln_pad pieces into its table, r / n == ln_mul ? umulhi(r, ln_mul) >> ln_shift : r.  ln_pad == 0: every other layout.
   uint32_t ln_mul, ln_shift, ln_pad;
 };
 
@@ -140,22 +140,22 @@ inline int64_t table_row_bytes(int dtype, int64_t D) {
 // what a table offset (SlsArgs::tab_off, drs_engine::tab_off) counts: elements (4 / 2 bytes), or bytes for the rowwise types
 inline int64_t table_unit_bytes(int dtype) { return dtype == DRS_TABLE_FP32 ? 4 : table_rowwise(dtype) ? 1 : 2; }
 
-// "table_int8_lines": int8 rowwise rows that never cross a 128-byte line.  When S = table_row_stride(8, D) < 128 does not
-// divide 128, n = 128 / S rows share a line: row r starts at byte (r / n) * 128 + (r % n) * S of its table and the last
-// 128 - n * S bytes of every line are zero.  Any other S keeps the plain layout (n == 0 here).  The kernels count in
-// 4-byte pieces: r * (S / 4) + (r / n) * pad, with r / n == umulhi(r, mul) >> shift for every 32-bit r (n == 1: mul == 0
-// and the quotient is r itself; n == 2: 2^31, 0; n == 3: 0xAAAAAAAB, 1; n == 5: 0xCCCCCCCD, 2 -- the 64-bit product shifted
-// by 32 + shift).
+// "table_int8_lines" / "table_int4_lines": rowwise rows that never cross a 128-byte line.  When the row stride S =
+// table_row_stride(dtype, D) < 128 does not divide 128, n = 128 / S rows share a line: row r starts at byte
+// (r / n) * 128 + (r % n) * S of its table and the last 128 - n * S bytes of every line are zero.  Any other S keeps the
+// plain layout (n == 0 here).  The kernels count in pieces of `piece` bytes (int8: 4, int4: 2): r * (S / piece) +
+// (r / n) * pad, with r / n == umulhi(r, mul) >> shift for every 32-bit r (n == 1: mul == 0 and the quotient is r itself;
+// n == 2: 2^31, 0; n == 3: 0xAAAAAAAB, 1; n == 4: 2^31, 1; n == 5: 0xCCCCCCCD, 2; n == 6: 0xAAAAAAAB, 2; n == 10:
+// 0xCCCCCCCD, 3 -- the 64-bit product shifted by 32 + shift).
 struct I8Lines {
   int32_t n = 0;                   // rows per line; 0: the plain layout
   uint32_t mul = 0, shift = 0, pad = 0;
 };
-inline I8Lines i8_lines(int64_t D, int lines) {
+inline I8Lines row_lines(int64_t S, int64_t piece, int lines) {
   I8Lines l;
-  const int64_t S = (D + 7) / 8 * 8 + 8;
   if (!lines || S >= 128 || 128 % S == 0) return l;
   l.n = (int32_t)(128 / S);
-  l.pad = (uint32_t)(32 - l.n * (S / 4));
+  l.pad = (uint32_t)(128 / piece - l.n * (S / piece));
   if (l.n > 1) {
     int lg = 0;                    // ceil(log2(n))
     while ((1 << lg) < l.n) ++lg;
@@ -164,7 +164,13 @@ inline I8Lines i8_lines(int64_t D, int lines) {
   }
   return l;
 }
-// byte offset of row r inside its int8 rowwise table, and the bytes `rows` rows occupy (before the 256-byte rounding)
+inline I8Lines i8_lines(int64_t D, int lines) { return row_lines(table_row_stride(DRS_TABLE_INT8_ROWWISE, D), 4, lines); }
+inline I8Lines i4_lines(int64_t D, int lines) { return row_lines(table_row_stride(DRS_TABLE_INT4_ROWWISE, D), 2, lines); }
+// the layout of an arena of type dtype under its own option's value (fp32 / fp16 / bf16: plain)
+inline I8Lines table_lines(int dtype, int64_t D, int lines) {
+  return dtype == DRS_TABLE_INT8_ROWWISE ? i8_lines(D, lines) : dtype == DRS_TABLE_INT4_ROWWISE ? i4_lines(D, lines) : I8Lines();
+}
+// byte offset of row r inside its int8 / int4 rowwise table, and the bytes `rows` rows occupy (before the 256-byte rounding)
 __host__ __device__ inline int64_t i8_row_offset(int64_t r, int64_t S, int32_t n) { return n ? r / n * 128 + r % n * S : r * S; }
 inline int64_t i8_table_bytes(int64_t rows, int64_t S, int32_t n) { return n ? (rows + n - 1) / n * 128 : rows * S; }
 
@@ -334,16 +340,16 @@ hipError_t probe_latency(const void* base, size_t chunk_bytes, int n_chunks, int
 hipError_t launch_fill_uniform(float* W, int64_t n, int32_t t, float lo, float hi, uint64_t seed,
                                hipStream_t stream);
 // the same values of a table of rows x D, stored as `dtype` (DRS_TABLE_*; fp32: launch_fill_uniform; fp16 / bf16: rounded;
-// int8 / int4 rowwise: each row quantized, n = I8Lines::n of an int8 table's layout)
+// int8 / int4 rowwise: each row quantized, n = I8Lines::n of the table's layout)
 hipError_t launch_fill_uniform_dtype(void* W, int dtype, int64_t rows, int D, int32_t t, float lo, float hi, uint64_t seed,
                                      hipStream_t stream, int32_t n = 0);
 // n table elements of type src_dtype -> dst_dtype (rounded to nearest even; widening is exact); fp32 / fp16 / bf16 only
 hipError_t launch_convert_table(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, hipStream_t stream);
 // rows x D of one table, into or out of int8 / int4 rowwise: quantized per row, each row's value fmaf(scale, q, 0.0f + bias)
-// rounded to dst_dtype (or quantized again, between the two rowwise types), or (int8 on both sides) the rows' bytes moved
-// from one layout to the other.  A rowwise side is the TABLE's base -- int8: in the layout n_src / n_dst (I8Lines::n); int4:
-// always plain -- and the rows are its rows first .. first + rows - 1 of `total` (the last row of an int8 table clears the
-// rest of its line); the other side is the rows themselves, D elements each.
+// rounded to dst_dtype (or quantized again, between the two rowwise types), or (the same rowwise type on both sides) the
+// rows' bytes moved from one layout to the other.  A rowwise side is the TABLE's base, in the layout n_src / n_dst
+// (I8Lines::n of its own type), and the rows are its rows first .. first + rows - 1 of `total` (the last row of a table
+// clears the rest of its line); the other side is the rows themselves, D elements each.
 hipError_t launch_convert_rows(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t rows, int D, hipStream_t stream,
                                int32_t n_src = 0, int32_t n_dst = 0, int64_t first = 0, int64_t total = -1);
 

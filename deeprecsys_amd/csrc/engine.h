@@ -6,7 +6,7 @@
 //   tables   one arena, rows row-major ("table_dtype": rows*D fp32, fp16 or bf16, table t at a 64-element aligned offset;
 //            int8 rowwise: rows of round_up(D, 8) + 8 bytes, table t at a 256-byte aligned offset; "table_int8_lines" 1:
 //            128 / S rows to a 128-byte line where S does not divide 128; int4 rowwise: rows of round_up(D / 2, 4) + 4
-//            bytes, table t at a 256-byte aligned offset -- table_layout)
+//            bytes, table t at a 256-byte aligned offset, "table_int4_lines" 1: the same line packing -- table_layout)
 //   weights  one arena: all biases back to back (layer order, padded to 4 floats), then per
 //            layer W [N, K] dense row-major (as fed by the reference)
 //   batches  per staged batch: dense [max_batch, m_den] f32 | idx [T, cap] i32 |
@@ -187,7 +187,8 @@ struct drs_engine {
   int sls_pool = 0;                 // "sls_pool": 1 -- every bag's pooled vector is its mean, the gather's fp32 sum / (float)length (SlsArgs::pool)
   int table_dtype = DRS_TABLE_FP32; // "table_dtype": element type of the arena (DRS_TABLE_*); sums and outputs stay fp32
   int table_int8_lines = 0;         // "table_int8_lines": an int8 rowwise arena keeps every row inside one 128-byte line (drs_internal.h I8Lines)
-  I8Lines i8l;                      // ... the layout of the arena in use: i8_lines(D, table_int8_lines) while it is int8 rowwise, else plain
+  int table_int4_lines = 0;         // "table_int4_lines": the same for an int4 rowwise arena (2-byte pieces)
+  I8Lines i8l;                      // ... the layout of the arena in use: table_lines(table_dtype, D, its option) while it is int8 / int4 rowwise, else plain
   // how the NEXT arena is built (drs_create's first one, "table_placement" -1 candidates)
   int table_alloc = 0;              // 0 hipMalloc | 1 virtual-memory API
   int64_t vmm_chunk = -1;           // bytes of physical memory per handle (0: one handle | -1: 1 GiB handles from 1 GiB on, else one); rounded up to whole 2 MiB pages
@@ -310,7 +311,7 @@ inline bool bf16_shape(const drs_engine* e, int64_t K, int64_t N) { return e->ml
 std::vector<Mlp*> served_mlps(drs_engine* e);
 // ... and the bf16 twin of one of their layers, built from its weights on the device (hipErrorOutOfMemory: nothing changed)
 hipError_t build_bf16_twin(Layer& L);
-// where the tables of an arena of type `dtype` start (*off, units of table_unit_bytes) and its bytes; lines: "table_int8_lines"
+// where the tables of an arena of type `dtype` start (*off, units of table_unit_bytes) and its bytes; lines: "table_int8_lines" / "table_int4_lines", the option of that type
 size_t table_layout(const drs_engine* e, int dtype, std::vector<int64_t>* off, int lines = 0);
 int32_t fail(drs_engine* e, int32_t code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
 int32_t set_device(drs_engine* e);

@@ -223,11 +223,11 @@ void drs::eng::choose_launch_forms(drs_engine* e) {
 
 size_t drs::eng::table_layout(const drs_engine* e, int dtype, std::vector<int64_t>* off, int lines) {
   int64_t o = 0;
-  const int32_t n = dtype == DRS_TABLE_INT8_ROWWISE ? i8_lines(e->D, lines).n : 0;
+  const int32_t n = table_lines(dtype, e->D, lines).n;
   off->resize((size_t)e->T);
   for (int t = 0; t < e->T; ++t) {
     (*off)[(size_t)t] = o;
-    o += table_rowwise(dtype) ? round_up(i8_table_bytes(e->rows[t], table_row_stride(dtype, e->D), n), 256)   // bytes (int4: n == 0, rows * S)
+    o += table_rowwise(dtype) ? round_up(i8_table_bytes(e->rows[t], table_row_stride(dtype, e->D), n), 256)   // bytes
                               : round_up(e->rows[t] * e->D, 64);                                    // elements
   }
   return (size_t)o * (size_t)table_unit_bytes(dtype);

@@ -314,7 +314,7 @@ static int32_t launch_gather(SetCtx& x) {
   a.out = s.T; a.ld_out = e->ldT; a.col0 = e->kind == DRS_MODEL_NCF ? 0 : e->w0;
   a.T = e->T; a.D = e->D; a.err = reinterpret_cast<int32_t*>(s.d_err);
   a.ts = prof ? s.d_ts : nullptr;
-  a.ln_mul = e->i8l.mul; a.ln_shift = e->i8l.shift; a.ln_pad = e->i8l.pad;   // ("table_int8_lines": zeros for every other layout)
+  a.ln_mul = e->i8l.mul; a.ln_shift = e->i8l.shift; a.ln_pad = e->i8l.pad;   // ("table_int8_lines" / "table_int4_lines": zeros for every other layout)
   a.pool = e->sls_pool;      // ("sls_pool": DIN and DIEN refuse 1, so the fused DIN launch never sees it)
   // short bags (W&D / NCF: one lookup per table) take the sequential lane-group-per-bag form (plan_sls); the queries'
   // own bag lengths count here, also when "sls_uniform" 0 keeps them from the kernels

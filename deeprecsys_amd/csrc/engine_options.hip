@@ -91,7 +91,8 @@ int32_t set_table_spacer(drs_engine* e, int64_t value) {
     return DRS_OK;
 }
 
-// "table_dtype" and "table_int8_lines": the arena in use becomes one of element type dt, int8 rows laid out by `lines`
+// "table_dtype", "table_int8_lines" and "table_int4_lines": the arena in use becomes one of element type dt, int8 / int4
+// rows laid out by `lines` (the option of dt's type)
 int32_t convert_tables(drs_engine* e, int dt, int lines) {
   // The tables in use are converted on the device into a new arena of the new element type (round to nearest even;
   // widening is exact; int8 / int4 rowwise: each row quantized, each row's value written out, or its bytes moved to the other
@@ -99,7 +100,7 @@ int32_t convert_tables(drs_engine* e, int dt, int lines) {
   // when the new arena would not leave 3/4 of the device's memory free -- the rule of "table_placement" -1.  The launch
   // forms that depend on the gathered bytes are chosen again (choose_launch_forms): set these options first.
   const int from = e->table_dtype;
-  const I8Lines to_l = dt == DRS_TABLE_INT8_ROWWISE ? i8_lines(e->D, lines) : I8Lines(), from_l = e->i8l;
+  const I8Lines to_l = table_lines(dt, e->D, lines), from_l = e->i8l;
   const bool rowwise = table_rowwise(dt) || table_rowwise(from);
   // the gather kernels address a row in 32-bit counts of 4-byte pieces: rows * S / 4 < 2^32 per int8 table, or
   // ceil(rows / n) * 32 < 2^32 when n rows share a line
@@ -108,13 +109,14 @@ int32_t convert_tables(drs_engine* e, int dt, int lines) {
       if (i8_table_bytes(e->rows[t], table_row_stride(dt, e->D), to_l.n) / 4 >= (1ll << 32))
         return fail(e, DRS_ERR_UNSUPPORTED, "table_dtype 8: table %d (%lld rows of %lld bytes%s) is too large to address", t,
                     (long long)e->rows[t], (long long)table_row_stride(dt, e->D), to_l.n ? ", line-packed" : "");
-  // int4 rowwise: two codes to a byte, so even D only; rows * S / 2 < 2^32 per table (2-byte pieces)
+  // int4 rowwise: two codes to a byte, so even D only; rows * S / 2 < 2^32 per table (2-byte pieces), or
+  // ceil(rows / n) * 64 < 2^32 when n rows share a line
   if (dt == DRS_TABLE_INT4_ROWWISE) {
     if (e->D & 1) return fail(e, DRS_ERR_UNSUPPORTED, "table_dtype 9: D = %d is odd (two 4-bit codes share a byte)", e->D);
     for (int t = 0; t < e->T; ++t)
-      if (e->rows[t] * table_row_stride(dt, e->D) / 2 >= (1ll << 32))
-        return fail(e, DRS_ERR_UNSUPPORTED, "table_dtype 9: table %d (%lld rows of %lld bytes) is too large to address", t,
-                    (long long)e->rows[t], (long long)table_row_stride(dt, e->D));
+      if (i8_table_bytes(e->rows[t], table_row_stride(dt, e->D), to_l.n) / 2 >= (1ll << 32))
+        return fail(e, DRS_ERR_UNSUPPORTED, "table_dtype 9: table %d (%lld rows of %lld bytes%s) is too large to address", t,
+                    (long long)e->rows[t], (long long)table_row_stride(dt, e->D), to_l.n ? ", line-packed" : "");
   }
   std::vector<int64_t> off;
   const size_t bytes = table_layout(e, dt, &off, lines);
@@ -158,7 +160,7 @@ int32_t set_table_dtype(drs_engine* e, int64_t value) {
   if (value == e->table_dtype) return DRS_OK;
   if (e->kind == DRS_MODEL_DIN || e->kind == DRS_MODEL_DIEN)
     return fail(e, DRS_ERR_UNSUPPORTED, "table_dtype %lld: DIN and DIEN gather fp32 tables only", (long long)value);
-  return convert_tables(e, (int)value, e->table_int8_lines);
+  return convert_tables(e, (int)value, value == DRS_TABLE_INT4_ROWWISE ? e->table_int4_lines : e->table_int8_lines);
 }
 
 int32_t set_table_int8_lines(drs_engine* e, int64_t value) {
@@ -169,6 +171,16 @@ int32_t set_table_int8_lines(drs_engine* e, int64_t value) {
     if (rc) return rc;
   }
   e->table_int8_lines = (int)value;
+  return DRS_OK;
+}
+
+int32_t set_table_int4_lines(drs_engine* e, int64_t value) {
+  // "table_int8_lines"' twin for an int4 rowwise arena; the two options are independent, each acts on its own arena type
+  if (e->table_dtype == DRS_TABLE_INT4_ROWWISE && i4_lines(e->D, (int)value).n != e->i8l.n) {
+    const int32_t rc = convert_tables(e, e->table_dtype, (int)value);
+    if (rc) return rc;
+  }
+  e->table_int4_lines = (int)value;
   return DRS_OK;
 }
 
@@ -270,6 +282,8 @@ const OptDesc kOptions[] = {
     {"table_dtype", 0, 9, [](int64_t v) { return v <= DRS_TABLE_BF16 || v == DRS_TABLE_INT8_ROWWISE || v == DRS_TABLE_INT4_ROWWISE; }, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_dtype; }, nullptr, set_table_dtype},
     // an int8 rowwise arena keeps every row inside one 128-byte line: 128 / S rows to a line where S < 128 does not divide 128
     {"table_int8_lines", 0, 1, nullptr, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_int8_lines; }, nullptr, set_table_int8_lines},
+    // ... and an int4 rowwise arena: its rows are 36 bytes at D 64 (3 to a line), 20 at D 32 (6 to a line)
+    {"table_int4_lines", 0, 1, nullptr, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_int4_lines; }, nullptr, set_table_int4_lines},
     {"table_spacer", 0, kBig, nullptr, 0, [](drs_engine* e) -> int64_t { return (int64_t)e->spacers.size() << 30; }, nullptr, set_table_spacer},
     // what the engine tells its feeder (read only)
     OPT_RO("preferred_coalesce", return e->mlp_streams > 1 ? DRS_MAX_COALESCE : (e->kind == DRS_MODEL_DLRM ? 12 : 8);),

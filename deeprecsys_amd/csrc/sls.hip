@@ -100,8 +100,8 @@ __device__ __forceinline__ uint16_t ld_nt(const uint16_t* p) { return __builtin_
 //   sb: what a lane loads per row besides its piece (int8 rowwise: the row's fp32 scale and bias; int4 rowwise: one dword,
 //   its fp16 scale and bias; nothing otherwise)
 //   pieces_per_row(D): the row stride in pieces; a.tab_off counts `elem`s
-//   row_piece(r, pr, ln): where row r starts in its table, in pieces (pr: the row stride) -- r * pr, but for I8L, whose
-//   launch constants `ln` a kernel reads with DRS_ROW_LINES (nothing for every other policy)
+//   row_piece(r, pr, ln): where row r starts in its table, in pieces (pr: the row stride) -- r * pr, but for I8L and I4L,
+//   whose launch constants `ln` a kernel reads with DRS_ROW_LINES (nothing for every other policy)
 //   add(acc, keep, piece, sb): acc += the row's values (keep == false: the row contributes +0)
 struct NoSb {};
 template <class Self>
@@ -226,6 +226,15 @@ struct I4 {
     acc.z = row1(s, b, (float)((p >> 8) & 15u), acc.z);
     acc.w = row1(s, b, (float)(p >> 12), acc.w);
   }
+};
+// The same rows in the line-packed layout ("table_int4_lines" 1): I8L's rule with int4's S and 2-byte pieces -- n = 128 / S
+// rows to a line, row r at r * PR + (r / n) * pad pieces with PR = S / 2 and pad = 64 - n * PR.  Every form sums the same
+// values in the same order as I4; the range check stays r < rows.
+struct I4L : I4 {
+  static constexpr bool lines = true;
+  using ln_t = LineMap;
+  static constexpr const char* tag = "i4l";
+  __device__ static __forceinline__ uint32_t row_piece(uint32_t r, uint32_t pr, LineMap ln) { return I8L::row_piece(r, pr, ln); }
 };
 #define DRS_ROW_LINES(E, a, ln) \
   typename E::ln_t ln{};        \
@@ -787,7 +796,7 @@ __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
       if constexpr (E::rowwise) {
         // byte loads of the codes; every lane of the wave reads the row's scale and bias
         const uint8_t* row;
-        if constexpr (E::lines) row = W + (int64_t)E::row_piece(r, E::pieces_per_row(D), ln) * 4;
+        if constexpr (E::lines) row = W + (int64_t)E::row_piece(r, E::pieces_per_row(D), ln) * kPieceElems<E>;
         else row = W + (int64_t)r * (int64_t)E::pieces_per_row(D) * kPieceElems<E>;
         const float2 sb = E::row_sb(row, D);
 #pragma unroll
@@ -819,7 +828,7 @@ __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
 
 int lanes_per_row(int D) { return D <= 8 ? 2 : D <= 16 ? 4 : D <= 32 ? 8 : D <= 64 ? 16 : D <= 128 ? 32 : 64; }
 
-// the launch for tables of element type E (F32 / F16 / BF16 / I8 / I8L / I4): the plan's dispatch-log line, then its instance
+// the launch for tables of element type E (F32 / F16 / BF16 / I8 / I8L / I4 / I4L): the plan's dispatch-log line, then its instance
 template <class E>
 hipError_t launch_sls_e(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hipStream_t s, hipEvent_t stop) {
   // dispatch log: the dtype token ("" for fp32), then "mean" under "sls_pool" 1 (nothing for sum)
@@ -953,7 +962,7 @@ hipError_t launch_sls(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hipS
     case DRS_TABLE_FP16: return launch_sls_e<F16>(a, p, tune, s, stop);
     case DRS_TABLE_BF16: return launch_sls_e<BF16>(a, p, tune, s, stop);
     case DRS_TABLE_INT8_ROWWISE: return a.ln_pad ? launch_sls_e<I8L>(a, p, tune, s, stop) : launch_sls_e<I8>(a, p, tune, s, stop);
-    case DRS_TABLE_INT4_ROWWISE: return launch_sls_e<I4>(a, p, tune, s, stop);
+    case DRS_TABLE_INT4_ROWWISE: return a.ln_pad ? launch_sls_e<I4L>(a, p, tune, s, stop) : launch_sls_e<I4>(a, p, tune, s, stop);
     default: return launch_sls_e<F32>(a, p, tune, s, stop);
   }
 }
@@ -1043,11 +1052,15 @@ struct SrcI8 {         // each int8 rowwise row's value, fmaf(scale, q, 0.0f + b
     return I8::row1(sb.x, sb.y, I8::code(row, c), 0.0f);
   }
 };
-// int4 rowwise rows (layout: struct I4; always plain): `base` is the TABLE's first byte, the launch's row r its row first + r
+// int4 rowwise rows (layout: struct I4), as I8Rows: `base` is the TABLE's first byte, the launch's row r its row first + r of
+// `total`, n = I8Lines::n of the layout ("table_int4_lines"; 0: plain)
 struct I4Rows {
   uint8_t* base;
-  int64_t first;
-  __device__ __forceinline__ uint8_t* row(int64_t r, int D) const { return base + (first + r) * (int64_t)(I4::padded(D) + 4); }
+  int64_t first, total;
+  int32_t n;
+  __device__ __forceinline__ uint8_t* row(int64_t r, int D) const { return base + i8_row_offset(first + r, I4::padded(D) + 4, n); }
+  // the bytes of its line behind row r that belong to no row (I8Rows::tail; a multiple of 4 here)
+  __device__ __forceinline__ int tail(int64_t r, int D) const { return I8Rows{base, first, total, n}.tail(r, I4::padded(D) + 4); }
 };
 struct SrcI4 {         // each int4 rowwise row's value
   I4Rows rows;
@@ -1155,6 +1168,7 @@ __global__ __launch_bounds__(256) void pack4_rows_kernel(Src src, I4Rows dst, in
     }
     if (lane == 0)
       *reinterpret_cast<uint32_t*>(row + P) = (uint32_t)__builtin_bit_cast(uint16_t, scale_h) | ((uint32_t)__builtin_bit_cast(uint16_t, bias_h) << 16);
+    for (int c = lane * 4, z = dst.tail(r, D); c < z; c += 64 * 4) *reinterpret_cast<uint32_t*>(row + P + 4 + c) = 0u;
   }
 }
 // int4 rows -> elements of type dt: each row's value fmaf(scale, q, 0.0f + bias) (the one-row bag), rounded to dt
@@ -1162,6 +1176,17 @@ __global__ __launch_bounds__(256) void unpack4_rows_kernel(SrcI4 src, void* dst,
   const int lane = threadIdx.x & 63;
   for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4)
     for (int c = lane; c < D; c += 64) store_elem(dst, dt, r * D + c, src(r, D, c));
+}
+// int4 rows from one layout to the other ("table_int4_lines" set on an int4 arena): the rows' bytes as they are
+__global__ __launch_bounds__(256) void relayout4_rows_kernel(I4Rows src, I4Rows dst, int64_t rows, int D) {
+  const int lane = threadIdx.x & 63;
+  const int S = I4::padded(D) + 4;
+  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
+    const uint8_t* from = src.row(r, D);
+    uint8_t* to = dst.row(r, D);
+    for (int c = lane * 4; c < S; c += 64 * 4) *reinterpret_cast<uint32_t*>(to + c) = *reinterpret_cast<const uint32_t*>(from + c);
+    for (int c = lane * 4, z = dst.tail(r, D); c < z; c += 64 * 4) *reinterpret_cast<uint32_t*>(to + S + c) = 0u;
+  }
 }
 static unsigned row_grid(int64_t rows) {
   const int64_t want = (rows + 3) / 4;
@@ -1306,7 +1331,7 @@ hipError_t launch_fill_uniform_dtype(void* W, int dtype, int64_t rows, int D, in
   if (dtype == DRS_TABLE_INT4_ROWWISE) {
     if (D & 1) return hipErrorInvalidValue;   // (internal guard: the engine refuses table_dtype 9 on odd D before any launch)
     hipLaunchKernelGGL(pack4_rows_kernel<SrcFill>, dim3(row_grid(rows)), dim3(256), 0, s, SrcFill{t, lo, hi - lo, seed},
-                       I4Rows{static_cast<uint8_t*>(W), 0}, rows, D);
+                       I4Rows{static_cast<uint8_t*>(W), 0, rows, n_lines}, rows, D);
     return hipGetLastError();
   }
   if (dtype == DRS_TABLE_INT8_ROWWISE) {
@@ -1328,12 +1353,13 @@ hipError_t launch_convert_rows(const void* src, int src_dtype, void* dst, int ds
   const bool si8 = src_dtype == DRS_TABLE_INT8_ROWWISE, di8 = dst_dtype == DRS_TABLE_INT8_ROWWISE;
   const bool si4 = src_dtype == DRS_TABLE_INT4_ROWWISE, di4 = dst_dtype == DRS_TABLE_INT4_ROWWISE;
   if (si4 || di4) {
-    // (internal guards, unreachable through the engine: convert_tables refuses odd D, and 9 -> 9 returns before it)
-    if ((D & 1) || (si4 && di4)) return hipErrorInvalidValue;
+    // (internal guard, unreachable through the engine: convert_tables refuses odd D)
+    if (D & 1) return hipErrorInvalidValue;
     const dim3 grid(row_grid(rows)), block(256);
-    const SrcI4 from4{I4Rows{from.base, first}};
-    const I4Rows to4{to.base, first};
-    if (si4 && di8) hipLaunchKernelGGL(rows4_to_rows8_kernel, grid, block, 0, s, from4, to, rows, D);
+    const SrcI4 from4{I4Rows{from.base, first, total, n_src}};
+    const I4Rows to4{to.base, first, total, n_dst};
+    if (si4 && di4) hipLaunchKernelGGL(relayout4_rows_kernel, grid, block, 0, s, from4.rows, to4, rows, D);
+    else if (si4 && di8) hipLaunchKernelGGL(rows4_to_rows8_kernel, grid, block, 0, s, from4, to, rows, D);
     else if (si4) hipLaunchKernelGGL(unpack4_rows_kernel, grid, block, 0, s, from4, dst, dst_dtype, rows, D);
     else if (si8) hipLaunchKernelGGL(pack4_rows_kernel<SrcI8>, grid, block, 0, s, SrcI8{from}, to4, rows, D);
     else hipLaunchKernelGGL(pack4_rows_kernel<SrcElems>, grid, block, 0, s, SrcElems{src, src_dtype}, to4, rows, D);

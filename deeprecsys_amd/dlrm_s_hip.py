@@ -74,6 +74,14 @@ def _table_int8_lines(args):
     return v
 
 
+def _table_int4_lines(args):
+    """--accel_table_int4_lines -> the engine's "table_int4_lines" value (0 when the flag is absent)."""
+    v = int(getattr(args, "accel_table_int4_lines", 0) or 0)
+    if v not in (0, 1):
+        raise ValueError("--accel_table_int4_lines %r: 0 or 1" % (v,))
+    return v
+
+
 _SLS_POOLS = {"sum": N.POOL_SUM, "mean": N.POOL_MEAN}
 
 
@@ -139,6 +147,7 @@ class _HipNet(object):
         mlp_dtype = _mlp_dtype(a)
         bf16_fuse = _mlp_bf16_fuse(a)
         int8_lines = _table_int8_lines(a)
+        int4_lines = _table_int4_lines(a)
         pool = _sls_pool(a)
         def make(n_slots):
             eng = N.Engine(self.kind, self.ln_emb, self.m_spa, ln_bot_cfg, ln_top_cfg,
@@ -151,6 +160,9 @@ class _HipNet(object):
             # --accel_table_int8_lines: ahead of table_dtype, so that the int8 arena is laid out once; only when asked for
             if int8_lines:
                 eng.set_option("table_int8_lines", int8_lines)
+            # --accel_table_int4_lines: the same for an int4 arena
+            if int4_lines:
+                eng.set_option("table_int4_lines", int4_lines)
             # --accel_table_dtype: first, while the arena is empty -- the engine then re-derives its by-model launch
             # forms (and "preferred_slots") for the element size, and every table write below is rounded on the device
             if dtype != N.TABLE_FP32:

@@ -315,6 +315,9 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  *                 "table_int8_lines" 0|1 (1 with "table_dtype" 8: no int8 row crosses a 128-byte line -- 128 / S rows of
  *                 S = round_up(D, 8) + 8 bytes share a line where S < 128 does not divide 128; set before or after
  *                 "table_dtype", the same arena; same results)
+ *                 "table_int4_lines" 0|1 (1 with "table_dtype" 9: no int4 row crosses a 128-byte line -- 128 / S rows of
+ *                 S = round_up(D / 2, 4) + 4 bytes share a line where S < 128 does not divide 128: three at D 64, six
+ *                 at D 32; independent of "table_int8_lines"; either order with "table_dtype"; same results)
  *   read only     "preferred_coalesce"  "preferred_slots"  "gather_bound"  "device"
  *                 "table_placements"  "table_bytes"  "table_address"
  * Options belong to the handle: two engines in one process (the mixed-model accelerator engine) keep their own.
