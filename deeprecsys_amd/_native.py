@@ -85,6 +85,13 @@ SYMBOLS = [
     ("drs_comm_last_error", C.c_char_p, []),
 ]
 COMM_ID_BYTES = 128
+# per-sample weights (SparseLengthsWeightedSum): symbols of the HIP build alone.  SYMBOLS above stays the list every
+# implementation of the ABI exports (the CPU restatement binds it); lib() binds these on top of it.
+WEIGHT_SYMBOLS = [
+    ("drs_stage_batch_weights", C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(_f32p), _i64p]),
+    ("drs_sls_weighted", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int64, C.c_int64, C.c_void_p, C.c_int32]),
+]
 
 
 class ModelCfg(C.Structure):
@@ -132,6 +139,10 @@ def lib():
         if not backend.startswith(b"hip:"):
             raise ImportError("%s identifies itself as %r: deeprecsys_amd binds the HIP build only "
                               "(the CPU restatement of the ABI is test infrastructure)" % (LIB_PATH, backend))
+        for name, res, args in WEIGHT_SYMBOLS:     # (the HIP build alone exports these)
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
         _lib = L
     return _lib
 
@@ -250,7 +261,9 @@ class Engine(object):
         lp = (_i32p * T)(*[l.ctypes.data_as(_i32p) for l in lengths])
         return idx, lengths, n_idx, ip, lp
 
-    def stage_batch(self, batch_id, dense, idx, lengths):
+    def stage_batch(self, batch_id, dense, idx, lengths, weights=None):
+        """weights: None (an unweighted batch), or one entry per table -- an fp32 weight per index of that table, or None
+        for a table whose weights are all 1.0 (SparseLengthsWeightedSum; staging a batch again drops its weights)."""
         n = int(np.asarray(lengths[0]).size)
         idx, lengths, n_idx, ip, lp = self._pack_sparse(idx, lengths)
         dp = None
@@ -259,6 +272,19 @@ class Engine(object):
             dp = dense.ctypes.data_as(_f32p)
         self._check(lib().drs_stage_batch(self._h, batch_id, n, dp, ip, n_idx.ctypes.data_as(_i64p), lp),
                     "drs_stage_batch")
+        if weights is not None:
+            self.stage_batch_weights(batch_id, weights)
+
+    def stage_batch_weights(self, batch_id, weights):
+        """Attach per-index weights to a batch already staged: one entry per table, an fp32 array as long as that table's
+        staged indices, or None (every weight 1.0)."""
+        if len(weights) != self.T:
+            raise ValueError("one weight array (or None) per table: %d for %d tables" % (len(weights), self.T))
+        w = [None if a is None else _f32(a).reshape(-1) for a in weights]
+        wp = (_f32p * self.T)(*[None if a is None else a.ctypes.data_as(_f32p) for a in w])
+        n_w = np.array([-1 if a is None else a.size for a in w], dtype=np.int64)
+        self._check(lib().drs_stage_batch_weights(self._h, batch_id, wp, n_w.ctypes.data_as(_i64p)),
+                    "drs_stage_batch_weights")
 
     # -- hot path -----------------------------------------------------------------
     def forward(self, batch_id, bs):
@@ -385,7 +411,12 @@ class Engine(object):
         return R
 
     # -- operator level (device pointers, e.g. torch.Tensor.data_ptr()) -------------
-    def sls(self, d_W, rows, D, d_idx, d_len, n_bags, n_idx, d_out, exact_order=True):
+    def sls(self, d_W, rows, D, d_idx, d_len, n_bags, n_idx, d_out, exact_order=True, wgt_ptr=None):
+        """wgt_ptr: device pointer to one fp32 weight per index (SparseLengthsWeightedSum), or None."""
+        if wgt_ptr is not None:
+            self._check(lib().drs_sls_weighted(self._h, d_W, rows, D, d_idx, wgt_ptr, d_len, n_bags, n_idx, d_out,
+                                               int(bool(exact_order))), "drs_sls_weighted")
+            return
         self._check(lib().drs_sls(self._h, d_W, rows, D, d_idx, d_len, n_bags, n_idx, d_out,
                                   int(bool(exact_order))), "drs_sls")
 

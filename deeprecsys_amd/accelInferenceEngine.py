@@ -72,7 +72,7 @@ def _build_hip_model(args, engine_id):
     nbatches, lT = datagen.generate_output_data()
     model = M.WRAPPERS[args.model_type](args)
     model.create(lX[0], lS_l[0], lS_i[0], lT[0])
-    model.net.stage_batches(lX, lS_l, lS_i)
+    model.net.stage_batches(lX, lS_l, lS_i, M.sls_weights(args, lS_i))   # (--accel_sls_weights: None unless asked for)
     # where the table arena lands in HBM moves the gather by a few per cent for the engine's lifetime: try a few places
     # with the model's own launch sets (about 30 ms each) and keep the fastest (--accel_table_placements, 1 = off)
     n_place = int(getattr(args, "accel_table_placements", 12))

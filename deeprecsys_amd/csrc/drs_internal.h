@@ -32,6 +32,9 @@ struct SlsArgs {
   QTable q;                   // which query a bag belongs to
   const int32_t* idx[DRS_MAX_COALESCE];   // per query: [T][idx_stride] int32 indices (Cast op done)
   const int32_t* off[DRS_MAX_COALESCE];   // per query: [T][off_stride] exclusive prefix sums of lengths
+  // per query: [T][idx_stride] fp32 per-sample weights, laid out like idx (SparseLengthsWeightedSum), or nullptr: the query is
+  // unweighted, every weight 1.0f.  A launch with at least one non-null entry is a WEIGHTED launch (SlsPlan::weighted).
+  const float* wgt[DRS_MAX_COALESCE];
   int32_t uniform_len[DRS_MAX_COALESCE];  // per query: >= 0 -> every bag has this many indices
   int64_t idx_stride;
   int64_t off_stride;
@@ -106,6 +109,8 @@ hipError_t fused_bf16_set_attrs();  // mlp_fused_bf16.hip's kernels, on the curr
 //   exact: the sequential summation order (bit-identical to Caffe2's SparseLengthsSum)
 //   G, NL, BPW, BW, L, nt: the instance -- lanes per row, loads per lane, bags per wave, samples per wave, bag length,
 //   non-temporal row loads; tiles: one-lookup sample tiles per table; grid: workgroups (0: nothing to launch)
+//   weighted: a query of the launch carries per-sample weights (SlsArgs::wgt): the ring walk or the any-width form, in
+//   their weighted instances -- never flat, flatc or one
 //   dtype: element type of the tables a.tables points at (DRS_TABLE_*; a.tab_off counts units of that type:
 //   table_unit_bytes) -- the same decisions and grids for every type, rows widened to fp32 before they are summed
 enum class SlsForm { any, ring, one, flat, flatc };
@@ -116,6 +121,7 @@ struct SlsPlan {
   int tiles = 0;
   int64_t grid = 0;
   int dtype = DRS_TABLE_FP32;
+  bool weighted = false;
 };
 // exact: the caller asks for the sequential order ("sls_exact", drs_sls's exact_order); short_bags: every bag of the
 // launch is short ("sls_short_bag"), so the sequential order is taken unless the flat variant takes the launch

@@ -10,7 +10,8 @@
 //   weights  one arena: all biases back to back (layer order, padded to 4 floats), then per
 //            layer W [N, K] dense row-major (as fed by the reference)
 //   batches  per staged batch: dense [max_batch, m_den] f32 | idx [T, cap] i32 |
-//            off [T, max_batch+1] i32 (exclusive prefix sums of the lengths)
+//            off [T, max_batch+1] i32 (exclusive prefix sums of the lengths); wgt [T, cap] f32 once the batch has
+//            carried per-sample weights (drs_stage_batch_weights)
 //   slots    per in-flight launch set (up to DRS_MAX_COALESCE coalesced queries): interaction buffer(s),
 //            layer scratch, device output buffer, [flag | err | out] in host-mapped pinned
 //            memory, and a host-mapped pinned input block for per-call inputs
@@ -75,6 +76,8 @@ struct Batch {
   float* dense = nullptr;
   int32_t* idx = nullptr;
   int32_t* off = nullptr;
+  float* wgt = nullptr;        // [T, cap] per-sample weights, laid out like idx (drs_stage_batch_weights; allocated on first use)
+  bool weighted = false;       // ... and whether the staged batch carries them (drs_stage_batch drops them)
   int32_t n_samples = 0;
   int32_t uniform_len = -1;    // all bags of all tables have this length, else -1
   std::vector<int32_t> h_off;  // [T][max_batch+1] host copy (gather_bytes, validation)

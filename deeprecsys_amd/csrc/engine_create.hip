@@ -93,6 +93,7 @@ void free_batch(Batch& b) {
   if (b.dense) (void)hipFree(b.dense);
   if (b.idx) (void)hipFree(b.idx);
   if (b.off) (void)hipFree(b.off);
+  if (b.wgt) (void)hipFree(b.wgt);
   b = Batch();
 }
 

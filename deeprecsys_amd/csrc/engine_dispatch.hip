@@ -308,6 +308,7 @@ static int32_t launch_gather(SetCtx& x) {
   for (int i = 0; i < q.n_q; ++i) {
     a.idx[i] = x.qb[i]->idx;
     a.off[i] = x.qb[i]->off;
+    a.wgt[i] = x.qb[i]->weighted ? x.qb[i]->wgt : nullptr;   // (staged batches only: the per-call input paths carry no weights)
     a.uniform_len[i] = e->sls_uniform ? x.qb[i]->uniform_len : -1;
   }
   a.idx_stride = e->cap; a.off_stride = e->max_batch + 1;
@@ -331,7 +332,7 @@ static int32_t launch_gather(SetCtx& x) {
     int64_t bytes = 0;
     for (int i = 0; i < q.n_q; ++i)
       for (int t = 0; t < e->T; ++t)
-        bytes += (int64_t)x.qb[i]->h_off[(size_t)t * (e->max_batch + 1) + q.bs[i]] * (table_row_bytes(e->table_dtype, e->D) + 4) +
+        bytes += (int64_t)x.qb[i]->h_off[(size_t)t * (e->max_batch + 1) + q.bs[i]] * (table_row_bytes(e->table_dtype, e->D) + 4 + (x.qb[i]->weighted ? 4 : 0)) +
                  (int64_t)q.bs[i] * (4 + (int64_t)e->D * 4);
     // (the fused DIN launch writes the 4 D floats of the top MLP's input row per sample instead
     // of T pooled vectors)
@@ -812,8 +813,9 @@ int32_t drs_interaction_width(drs_handle e, int32_t* num_int) {
 }
 
 // ---- operator-level entry points ---------------------------------------------
-int32_t drs_sls(drs_handle e, const float* d_W, int64_t rows, int32_t D, const int32_t* d_idx,
-                const int32_t* d_len, int64_t n_bags, int64_t n_idx, float* d_out, int32_t exact_order) {
+// drs_sls and drs_sls_weighted (d_wgt: one weight per index, or nullptr)
+static int32_t sls_op(drs_handle e, const float* d_W, int64_t rows, int32_t D, const int32_t* d_idx, const float* d_wgt,
+                      const int32_t* d_len, int64_t n_bags, int64_t n_idx, float* d_out, int32_t exact_order) {
   int32_t rc = check_handle(e);
   if (rc) return rc;
   if (!d_W || !d_len || !d_out || (!d_idx && n_idx > 0) || n_bags < 0 || n_idx < 0 || rows <= 0)
@@ -851,6 +853,7 @@ int32_t drs_sls(drs_handle e, const float* d_W, int64_t rows, int32_t D, const i
     a.tables = d_W; a.tab_off = e->d_op_tab; a.tab_rows = e->d_op_tab + 1;
     a.q.n_q = 1; a.q.vstart[1] = (int32_t)n_bags; a.q.cum[1] = (int32_t)n_bags; a.q.bs[0] = (int32_t)n_bags;
     a.idx[0] = d_idx; a.off[0] = d_off; a.uniform_len[0] = -1;
+    a.wgt[0] = d_wgt;        // (null: drs_sls; the table is one table, so the weights line up with the indices)
     a.out = d_out; a.ld_out = D; a.col0 = 0; a.T = 1; a.D = D; a.err = d_err; a.ts = nullptr;
     a.pool = e->sls_pool;    // the operator follows the handle: SparseLengthsMean under "sls_pool" 1
     r = launch_sls(a, plan_sls(a, exact_order != 0, false, e->tune, DRS_TABLE_FP32), e->tune, s.stream);
@@ -862,6 +865,20 @@ int32_t drs_sls(drs_handle e, const float* d_W, int64_t rows, int32_t D, const i
   if (r != hipSuccess) return fail(e, DRS_ERR_HIP, "drs_sls: %s", hipGetErrorString(r));
   if (h_err) return fail(e, DRS_ERR_INDEX_RANGE, "an index is outside [0, %lld)", (long long)rows);
   return DRS_OK;
+}
+
+int32_t drs_sls(drs_handle e, const float* d_W, int64_t rows, int32_t D, const int32_t* d_idx,
+                const int32_t* d_len, int64_t n_bags, int64_t n_idx, float* d_out, int32_t exact_order) {
+  return sls_op(e, d_W, rows, D, d_idx, nullptr, d_len, n_bags, n_idx, d_out, exact_order);
+}
+
+int32_t drs_sls_weighted(drs_handle e, const float* d_W, int64_t rows, int32_t D, const int32_t* d_idx, const float* d_wgt,
+                         const int32_t* d_len, int64_t n_bags, int64_t n_idx, float* d_out, int32_t exact_order) {
+  int32_t rc = check_handle(e);
+  if (rc) return rc;
+  if (!d_wgt && n_idx > 0) return fail(e, DRS_ERR_BAD_ARG, "drs_sls_weighted: null weights");
+  if (e->sls_pool) return fail(e, DRS_ERR_UNSUPPORTED, "drs_sls_weighted: \"sls_pool\" 1 has no weighted form (there is no weighted mean)");
+  return sls_op(e, d_W, rows, D, d_idx, d_wgt, d_len, n_bags, n_idx, d_out, exact_order);
 }
 
 int32_t drs_fc(drs_handle e, const float* d_x, int64_t M, int32_t K, const float* d_W, const float* d_b,

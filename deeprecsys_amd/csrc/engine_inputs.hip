@@ -260,7 +260,46 @@ int32_t drs_stage_batch(drs_handle e, int32_t batch_id, int32_t n_samples, const
   if (batch_id < 0 || batch_id >= e->n_batches) return fail(e, DRS_ERR_BAD_ARG, "batch_id %d of %d", batch_id, e->n_batches);
   // make sure no in-flight query still reads this batch
   for (auto& s : e->slots) if (s.busy) HIP_TRY(e, hipStreamSynchronize(s.stream));
-  return stage_into(e, e->batches[batch_id], n_samples, h_dense, h_idx, n_idx, h_len, e->slots[0].stream, nullptr);
+  rc = stage_into(e, e->batches[batch_id], n_samples, h_dense, h_idx, n_idx, h_len, e->slots[0].stream, nullptr);
+  if (rc == DRS_OK) e->batches[batch_id].weighted = false;   // new indices: the weights of the old ones are dropped (a failed call changed nothing)
+  return rc;
+}
+
+// Per-sample weights of a staged batch (SparseLengthsWeightedSum): one fp32 per staged index, laid out like the indices
+// ([T, cap]); a table without weights gets 1.0f throughout, so the kernels read one array whatever the mix.  The batch then
+// makes every launch set it is part of a weighted one (launch_gather, plan_sls).
+int32_t drs_stage_batch_weights(drs_handle e, int32_t batch_id, const float* const* h_wgt, const int64_t* n_idx) {
+  int32_t rc = check_handle(e);
+  if (rc) return rc;
+  if (batch_id < 0 || batch_id >= e->n_batches) return fail(e, DRS_ERR_BAD_ARG, "batch_id %d of %d", batch_id, e->n_batches);
+  if (e->kind == DRS_MODEL_DIN || e->kind == DRS_MODEL_DIEN)
+    return fail(e, DRS_ERR_UNSUPPORTED, "drs_stage_batch_weights: DIN and DIEN pool their bags by the plain sum only");
+  if (e->sls_pool) return fail(e, DRS_ERR_UNSUPPORTED, "drs_stage_batch_weights: \"sls_pool\" 1 has no weighted form (there is no weighted mean)");
+  if (!h_wgt || !n_idx) return fail(e, DRS_ERR_BAD_ARG, "null weight/count arrays");
+  Batch& b = e->batches[batch_id];
+  if (!b.staged) return fail(e, DRS_ERR_STATE, "batch %d is not staged", batch_id);
+  const size_t stride = (size_t)e->max_batch + 1;
+  for (int t = 0; t < e->T; ++t) {
+    const int64_t staged = b.h_off[(size_t)t * stride + (size_t)b.n_samples];
+    if (h_wgt[t] && n_idx[t] != staged)
+      return fail(e, DRS_ERR_LENGTHS_SUM, "table %d: %lld weights for %lld staged indices", t, (long long)n_idx[t], (long long)staged);
+  }
+  // make sure no in-flight query still reads this batch
+  for (auto& s : e->slots) if (s.busy) HIP_TRY(e, hipStreamSynchronize(s.stream));
+  if (!b.wgt) HIP_TRY(e, hipMalloc(&b.wgt, sizeof(float) * (size_t)e->T * e->cap));
+  std::vector<float> ones;
+  for (int t = 0; t < e->T; ++t) {
+    const int64_t n = b.h_off[(size_t)t * stride + (size_t)b.n_samples];
+    if (n <= 0) continue;
+    const float* src = h_wgt[t];
+    if (!src) {
+      if ((int64_t)ones.size() < n) ones.assign((size_t)n, 1.0f);
+      src = ones.data();
+    }
+    HIP_TRY(e, hipMemcpy(b.wgt + (size_t)t * e->cap, src, sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
+  }
+  b.weighted = true;
+  return DRS_OK;
 }
 
 int32_t drs_forward_inputs_async(drs_handle e, int32_t slot, int32_t bs, const float* h_dense,

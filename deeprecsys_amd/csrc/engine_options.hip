@@ -210,6 +210,11 @@ int32_t set_mlp_dtype(drs_engine* e, int64_t value) {
   return DRS_OK;
 }
 
+// "sls_weighted": staged batches that carry per-sample weights (drs_stage_batch_weights)
+int64_t weighted_batches(drs_engine* e) {
+  return (int64_t)std::count_if(e->batches.begin(), e->batches.end(), [](const Batch& b) { return b.staged && b.weighted; });
+}
+
 int32_t set_sls_pool(drs_engine* e, int64_t value) {
   // Mean pooling: the gather kernels divide every bag's finished sum by its length (sls.hip pool_finish).  One field that
   // every later launch copies into its SlsArgs: nothing is converted, allocated or chosen again.  DIN and DIEN
@@ -217,6 +222,9 @@ int32_t set_sls_pool(drs_engine* e, int64_t value) {
   if (value == e->sls_pool) return DRS_OK;
   if (e->kind == DRS_MODEL_DIN || e->kind == DRS_MODEL_DIEN)
     return fail(e, DRS_ERR_UNSUPPORTED, "sls_pool %lld: DIN and DIEN pool their bags by sum only", (long long)value);
+  // (there is no weighted mean: torch's EmbeddingBag takes per_sample_weights under mode="sum" only)
+  if (value && weighted_batches(e))
+    return fail(e, DRS_ERR_UNSUPPORTED, "sls_pool %lld: %lld staged batches carry per-sample weights", (long long)value, (long long)weighted_batches(e));
   e->sls_pool = (int)value;
   return DRS_OK;
 }
@@ -299,6 +307,7 @@ const OptDesc kOptions[] = {
     OPT_RO("table_placements", return (int64_t)e->arenas.size();),
     OPT_RO("table_bytes", return (int64_t)e->tables_bytes;),
     OPT_RO("table_address", return (int64_t)(uintptr_t)e->tables;),
+    OPT_RO("sls_weighted", return weighted_batches(e);),
 };
 #undef OPT
 #undef OPT_RO
@@ -597,7 +606,8 @@ int32_t drs_gather_bytes(drs_handle e, int32_t batch_id, int32_t bs, int64_t* by
   int64_t total = 0;
   for (int t = 0; t < e->T; ++t) {
     const int64_t n = b.h_off[(size_t)t * (e->max_batch + 1) + bs];
-    total += n * (table_row_bytes(e->table_dtype, e->D) + 4) + (int64_t)bs * (4 + (int64_t)e->D * 4);
+    // (a batch that carries weights reads 4 more bytes per looked-up row)
+    total += n * (table_row_bytes(e->table_dtype, e->D) + 4 + (b.weighted ? 4 : 0)) + (int64_t)bs * (4 + (int64_t)e->D * 4);
   }
   *bytes = total;
   return DRS_OK;

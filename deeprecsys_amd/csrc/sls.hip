@@ -35,6 +35,11 @@
 //     all 256 CUs; workgroups never cooperate.
 //   - index range is checked per row (Caffe2 ENFORCEs it): an out-of-range index
 //     raises bit 0 of *err and contributes zero instead of faulting.
+//   - WEIGHTED launches (SparseLengthsWeightedSum, SlsArgs::wgt): the ring walk (sequential and split) and the any-width
+//     form have a weighted instance (template parameter WGT) in which a row's weight travels with its index -- staged in a
+//     second LDS array by the same coalesced read, read beside the index when the row load is issued, and applied as
+//     acc = fma(w, x, acc) per column (rowwise types: s = w * scale, b = w * bias into the same row step).  The unweighted
+//     instances are the code they were; the flat and one-lookup forms carry no weights (plan_sls).
 #include "drs_internal.h"
 #include "launch_host.h"
 #include "owner_dev.h"
@@ -115,6 +120,15 @@ struct PlainRow {
   __device__ static __forceinline__ NoSb load_sb(const P*, int) { return NoSb{}; }
   template <class P>
   __device__ static __forceinline__ void add(float4& acc, bool keep, const P& p, NoSb) { vadd(acc, vsel(keep, Self::up(p))); }
+  // the weighted step, acc = fma(w, x, acc) per column: torch's CPU embedding_bag(per_sample_weights=), one rounding per
+  // column and row.  w == 1.0f is add's acc + x; a row that must not count comes with w == 0.0f -- fma(0, x, acc) == acc
+  // for every finite x (acc is never -0: it starts at +0 and a sum that cancels is +0).
+  template <class P>
+  __device__ static __forceinline__ void addw(float4& acc, float w, const P& p, NoSb) {
+    const float4 x = Self::up(p);
+    acc.x = __fmaf_rn(w, x.x, acc.x); acc.y = __fmaf_rn(w, x.y, acc.y); acc.z = __fmaf_rn(w, x.z, acc.z); acc.w = __fmaf_rn(w, x.w, acc.w);
+  }
+  __device__ static __forceinline__ float addw1(float acc, float w, float x) { return __fmaf_rn(w, x, acc); }
 };
 struct F32 : PlainRow<F32> {
   using elem = float;
@@ -175,6 +189,16 @@ struct I8 {
     acc.z = row1(s, b, (float)((p >> 16) & 0xffu), acc.z);
     acc.w = row1(s, b, (float)(p >> 24), acc.w);
   }
+  // the weighted step (FBGEMM's and torch's embedding_bag_byte_rowwise_offsets with per_sample_weights): the row's scale
+  // and bias are multiplied by its weight first -- two fp32 products -- and go through row1 as they are.  w == 1.0f
+  // is add; w == 0.0f (a row that must not count) adds acc + 0 + 0 * q == acc.
+  __device__ static __forceinline__ void addw(float4& acc, float w, uint32_t p, float2 sb) {
+    const float s = __fmul_rn(w, sb.x), b = __fmul_rn(w, sb.y);
+    acc.x = row1(s, b, (float)(p & 0xffu), acc.x);
+    acc.y = row1(s, b, (float)((p >> 8) & 0xffu), acc.y);
+    acc.z = row1(s, b, (float)((p >> 16) & 0xffu), acc.z);
+    acc.w = row1(s, b, (float)(p >> 24), acc.w);
+  }
 };
 // The same rows in the line-packed layout ("table_int8_lines" 1, drs_internal.h I8Lines): n = 128 / S rows to a 128-byte
 // line, so that no row crosses one.  Only where a row starts differs -- r * PR + (r / n) * pad pieces into its table, the
@@ -226,6 +250,16 @@ struct I4 {
     acc.z = row1(s, b, (float)((p >> 8) & 15u), acc.z);
     acc.w = row1(s, b, (float)(p >> 12), acc.w);
   }
+  // the weighted step: I8's, on the widened fp16 scale and bias (embedding_bag_4bit_rowwise_offsets with per_sample_weights)
+  __device__ static __forceinline__ void addw(float4& acc, float w, uint16_t p16, uint32_t w32) {
+    const float2 f = up_sb(w32);
+    const float s = __fmul_rn(w, f.x), b = __fmul_rn(w, f.y);
+    const uint32_t p = p16;
+    acc.x = row1(s, b, (float)(p & 15u), acc.x);
+    acc.y = row1(s, b, (float)((p >> 4) & 15u), acc.y);
+    acc.z = row1(s, b, (float)((p >> 8) & 15u), acc.z);
+    acc.w = row1(s, b, (float)(p >> 12), acc.w);
+  }
 };
 // The same rows in the line-packed layout ("table_int4_lines" 1): I8L's rule with int4's S and 2-byte pieces -- n = 128 / S
 // rows to a line, row r at r * PR + (r / n) * pad pieces with PR = S / 2 and pad = 64 - n * PR.  Every form sums the same
@@ -261,16 +295,20 @@ __device__ __forceinline__ int sb_delta(int D, int col) {
 // G lanes per row, 4 elements per lane.  U (row loads per register ring and lane) is 4: two rings, so 4..8 loads in
 // flight per lane, the waves per CU provide the rest of the memory-level parallelism.  (8, 16 and 20 were options until
 // round 4 -- measured equal or slower on every shape -- as was a 16-lane x 8-byte form for D == 32.)
-template <int G, bool EXACT, bool NT = false, class E = F32>
+// WGT: the weighted instance (a.wgt; a query whose entry is null weighs every row 1.0f and keeps its unweighted bits).  With
+// WGT == false nothing below that names a weight exists: the unweighted instances compile to what they were.
+template <int G, bool EXACT, bool NT = false, class E = F32, bool WGT = false>
 __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
   using piece = typename E::piece;
   using sbt = typename E::sb;
+  using wt = std::conditional_t<WGT, float, NoSb>;   // a row's weight beside its piece in the rings
   constexpr int U = 4;
   constexpr int NG = 64 / G;                  // lane groups per wave
   constexpr int BAGS = EXACT ? NG : 1;        // bags per wave
   constexpr int STEP = EXACT ? 1 : NG;        // row stride between a lane's loads
   constexpr int OWNERS = EXACT ? G : 64;      // lanes that stage one bag's indices
   __shared__ __attribute__((aligned(16))) int32_t s_idx[BAGS][kChunk];
+  __shared__ __attribute__((aligned(16))) float s_wgt[WGT ? BAGS : 1][WGT ? kChunk : 1];   // (never referenced without WGT)
 
   // live timing (bench.py roofline leg): first/last constant-rate clock tick of every
   // workgroup; the host takes max(end) - min(start) as the launch duration
@@ -301,6 +339,13 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
     end = bag_ok ? offp[b + 1] : 0;
   }
   const int32_t* __restrict__ ip = qidx + (int64_t)t * a.idx_stride;
+  // the owning query's weights, laid out like its indices (null: an unweighted query inside a weighted launch)
+  [[maybe_unused]] const float* wp = nullptr;
+  if constexpr (WGT) {
+    const float* qwgt = a.wgt[0];
+    DRS_OWNER_CHAIN(a.q, smp, qwgt = in ? a.wgt[i] : qwgt;)
+    wp = qwgt ? qwgt + (int64_t)t * a.idx_stride : nullptr;
+  }
   const typename E::elem* __restrict__ W = table_base<E>(a.tables) + a.tab_off[t] + col_elems<E>(col);
   const uint32_t rows = (uint32_t)a.tab_rows[t];
   const int64_t D = a.D;
@@ -311,6 +356,7 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
   DRS_ROW_LINES(E, a, ln)
 
   int32_t* my_idx = s_idx[EXACT ? g : 0];
+  [[maybe_unused]] float* my_wgt = s_wgt[WGT && EXACT ? g : 0];
   const int me = EXACT ? gl : lane;           // my slot among the owners
   const int first = EXACT ? 0 : g;            // first row (within a chunk) of this lane
   float4 acc = vzero4();
@@ -340,26 +386,43 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
 #pragma unroll
       for (int q = 0; q < 4; ++q)
         if (c0 + q * OWNERS + me < kChunk) my_idx[c0 + q * OWNERS + me] = tmp[q];
+      if constexpr (WGT) {   // the weights of the same positions (< n only, like the indices), by the same coalesced read
+        float wtmp[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) wtmp[q] = n > 0 && wp ? wp[j0 + min(c0 + q * OWNERS + me, last)] : 1.0f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (c0 + q * OWNERS + me < kChunk) my_wgt[c0 + q * OWNERS + me] = wtmp[q];
+      }
     }
     __builtin_amdgcn_wave_barrier();
 
     // U independent, unconditional row loads
-    auto issue = [&](piece (&ring)[U], sbt (&rsb)[U], int pos) {
+    // (weighted: a row's weight is read beside its index, and an out-of-range row takes the weight 0)
+    auto issue = [&](piece (&ring)[U], sbt (&rsb)[U], wt (&rw)[U], int pos) {
       uint32_t r[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) r[u] = (uint32_t)my_idx[min(pos + u * STEP, last)];
+      for (int u = 0; u < U; ++u) {
+        r[u] = (uint32_t)my_idx[min(pos + u * STEP, last)];
+        if constexpr (WGT) rw[u] = my_wgt[min(pos + u * STEP, last)];
+      }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         bad |= (pos + u * STEP < n) && (r[u] >= rows);
+        if constexpr (WGT) rw[u] = r[u] < rows ? rw[u] : 0.0f;
         r[u] = r[u] < rows ? r[u] : 0u;
         const piece* rp_ = reinterpret_cast<const piece*>(W) + (uint64_t)E::row_piece(r[u], Dv, ln);
         if constexpr (NT) ring[u] = ld_nt(rp_); else ring[u] = *rp_;
         rsb[u] = E::template load_sb<NT>(rp_, sbd);
       }
     };
-    auto consume = [&](const piece (&ring)[U], const sbt (&rsb)[U], int pos) {
+    // (weighted: the clamped re-reads past the bag's end take the weight 0 -- they must not add w * x)
+    auto consume = [&](const piece (&ring)[U], const sbt (&rsb)[U], const wt (&rw)[U], int pos) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) E::add(acc, pos + u * STEP < n, ring[u], rsb[u]);
+      for (int u = 0; u < U; ++u) {
+        if constexpr (WGT) E::addw(acc, pos + u * STEP < n ? rw[u] : 0.0f, ring[u], rsb[u]);
+        else E::add(acc, pos + u * STEP < n, ring[u], rsb[u]);
+      }
     };
 
     // software pipeline over two register rings: while ring A (round k) is summed
@@ -369,27 +432,28 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
     constexpr int R = U * STEP;
     piece ringA[U], ringB[U];
     sbt sbA[U], sbB[U];
+    wt wA[U], wB[U];
     int jj = first;                                 // per-lane row position
     int ju = 0;                                     // uniform round position
-    issue(ringA, sbA, jj);
+    issue(ringA, sbA, wA, jj);
     for (;;) {
       if (ju + R < n_u) {
-        issue(ringB, sbB, jj + R);
+        issue(ringB, sbB, wB, jj + R);
         __builtin_amdgcn_sched_barrier(0);   // loads first, then the sums
-        consume(ringA, sbA, jj);
+        consume(ringA, sbA, wA, jj);
         asm volatile("; drs sls: A summed, B in flight" ::: "memory");
       } else {
-        consume(ringA, sbA, jj);
+        consume(ringA, sbA, wA, jj);
         asm volatile("; drs sls: A summed, tail" ::: "memory");
         break;
       }
       if (ju + 2 * R < n_u) {
-        issue(ringA, sbA, jj + 2 * R);
+        issue(ringA, sbA, wA, jj + 2 * R);
         __builtin_amdgcn_sched_barrier(0);
-        consume(ringB, sbB, jj + R);
+        consume(ringB, sbB, wB, jj + R);
         asm volatile("; drs sls: B summed, A in flight" ::: "memory");
       } else {
-        consume(ringB, sbB, jj + R);
+        consume(ringB, sbB, wB, jj + R);
         asm volatile("; drs sls: B summed, tail" ::: "memory");
         break;
       }
@@ -763,7 +827,9 @@ __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
 // every shipped config satisfies.  Other widths -- D = 10, 50, 300 -- take this one: a wave per bag, lane c takes columns
 // c, c + 64, ... (dword loads: rows need no alignment), rows strictly in index order, i.e. Caffe2's own summation order
 // (bit-identical to the oracle), ragged bags through the prefix sums.  Slow by design (one row at a time), never wrong.
-template <class E = F32>
+// WGT: the weighted instance -- row j's weight is read beside its index (1.0f for a query without weights, 0.0f for an
+// out-of-range row) and the row adds acc = fma(w, x, acc), or with s = w * scale, b = w * bias for the rowwise types.
+template <class E = F32, bool WGT = false>
 __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
   if (a.ts && threadIdx.x == 0) a.ts[2 * blockIdx.x] = wall_clock64();
   const int lane = threadIdx.x;
@@ -781,6 +847,12 @@ __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
     end = offp[b + 1];
   }
   const int32_t* __restrict__ ip = qidx + (int64_t)t * a.idx_stride;
+  [[maybe_unused]] const float* wp = nullptr;
+  if constexpr (WGT) {
+    const float* qwgt = a.wgt[0];
+    DRS_OWNER_CHAIN(a.q, smp, qwgt = in ? a.wgt[i] : qwgt;)
+    wp = qwgt ? qwgt + (int64_t)t * a.idx_stride : nullptr;
+  }
   const typename E::elem* __restrict__ W = table_base<E>(a.tables) + a.tab_off[t];
   const uint32_t rows = (uint32_t)a.tab_rows[t];
   const int D = a.D;
@@ -792,13 +864,19 @@ __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
     for (int j = beg; j < end; ++j) {
       uint32_t r = (uint32_t)ip[j];
       bad |= r >= rows;
+      [[maybe_unused]] float w = 1.0f;
+      if constexpr (WGT) {
+        w = wp ? wp[j] : 1.0f;
+        w = r < rows ? w : 0.0f;
+      }
       r = r < rows ? r : 0u;
       if constexpr (E::rowwise) {
         // byte loads of the codes; every lane of the wave reads the row's scale and bias
         const uint8_t* row;
         if constexpr (E::lines) row = W + (int64_t)E::row_piece(r, E::pieces_per_row(D), ln) * kPieceElems<E>;
         else row = W + (int64_t)r * (int64_t)E::pieces_per_row(D) * kPieceElems<E>;
-        const float2 sb = E::row_sb(row, D);
+        float2 sb = E::row_sb(row, D);
+        if constexpr (WGT) sb = make_float2(__fmul_rn(w, sb.x), __fmul_rn(w, sb.y));
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const int c = c0 + lane + 64 * k;
@@ -809,7 +887,8 @@ __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const int c = c0 + lane + 64 * k;
-          acc[k] += c < D ? E::up1(row[c]) : 0.f;
+          if constexpr (WGT) acc[k] = c < D ? E::addw1(acc[k], w, E::up1(row[c])) : acc[k];
+          else acc[k] += c < D ? E::up1(row[c]) : 0.f;
         }
       }
     }
@@ -831,9 +910,11 @@ int lanes_per_row(int D) { return D <= 8 ? 2 : D <= 16 ? 4 : D <= 32 ? 8 : D <= 
 // the launch for tables of element type E (F32 / F16 / BF16 / I8 / I8L / I4 / I4L): the plan's dispatch-log line, then its instance
 template <class E>
 hipError_t launch_sls_e(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hipStream_t s, hipEvent_t stop) {
-  // dispatch log: the dtype token ("" for fp32), then "mean" under "sls_pool" 1 (nothing for sum)
-  char tags[16];
-  snprintf(tags, sizeof tags, "%s%s%s", E::tag, *E::tag && a.pool ? "," : "", a.pool ? "mean" : "");
+  // dispatch log: the dtype token ("" for fp32), then "mean" under "sls_pool" 1 (nothing for sum), then "w" on a weighted
+  // launch (nothing otherwise)
+  char tags[24];
+  snprintf(tags, sizeof tags, "%s%s%s%s%s", E::tag, *E::tag && a.pool ? "," : "", a.pool ? "mean" : "",
+           p.weighted && (*E::tag || a.pool) ? "," : "", p.weighted ? "w" : "");
   const char* dt = tags;
   const char* sep = *dt ? "," : "";
   const long long wg = (long long)p.grid;
@@ -856,10 +937,13 @@ hipError_t launch_sls_e(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hi
       break;
   }
   if (!wg) return hipSuccess;             // an empty launch enqueues nothing
+  // (the flat and one-lookup forms have no weighted instance: plan_sls never sends a weighted launch there)
+  if (p.weighted && p.form != SlsForm::any && p.form != SlsForm::ring) return hipErrorInvalidValue;
   const dim3 grid((unsigned)p.grid);
   switch (p.form) {
     case SlsForm::any:
-      launch_k(sls_any_kernel<E>, grid, s, stop, a);
+      if (p.weighted) launch_k(sls_any_kernel<E, true>, grid, s, stop, a);
+      else launch_k(sls_any_kernel<E>, grid, s, stop, a);
       break;
     case SlsForm::flatc:
       with_int<8, 16, 32>(p.G, [&](auto G) { with_int<5, 10, 20>(p.NL, [&](auto NL) { with_int<0, 1>(p.nt, [&](auto NT) {
@@ -880,7 +964,10 @@ hipError_t launch_sls_e(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hi
       break;
     case SlsForm::ring:
       with_int<2, 4, 8, 16, 32, 64>(p.G, [&](auto G) { with_int<0, 1>(p.exact, [&](auto EXACT) { with_int<0, 1>(p.nt, [&](auto NT) {
-        if constexpr (!(EXACT && NT)) launch_k(sls_kernel<G, EXACT != 0, NT != 0, E>, grid, s, stop, a);
+        if constexpr (!(EXACT && NT)) {
+          if (p.weighted) launch_k(sls_kernel<G, EXACT != 0, NT != 0, E, true>, grid, s, stop, a);
+          else launch_k(sls_kernel<G, EXACT != 0, NT != 0, E>, grid, s, stop, a);
+        }
       }); }); });
       break;
   }
@@ -896,6 +983,10 @@ SlsPlan plan_sls(const SlsArgs& a, bool exact, bool short_bags, const Tune& tune
   p.dtype = dtype;
   const int D = a.D, n_q = a.q.n_q, n_smp = a.q.cum[n_q];
   const int64_t n_bags = (int64_t)n_smp * a.T;
+  // a weighted launch: at least one of its queries carries per-sample weights.  It takes the any-width form or the ring
+  // walk below -- sequential or split by the same rule as ever -- and never the flat or the one-lookup forms, which
+  // have no weighted instance.
+  for (int i = 0; i < n_q; ++i) p.weighted = p.weighted || a.wgt[i] != nullptr;
   // widths that are not whole 16-byte pieces, or wider than a wave: the generic form (sequential order)
   if ((D & 3) || D > 256) {
     p.form = SlsForm::any;
@@ -908,7 +999,7 @@ SlsPlan plan_sls(const SlsArgs& a, bool exact, bool short_bags, const Tune& tune
   // BPW * L rows must fit NL loads per lane
   const int G = lanes_per_row(D), NG = 64 / G;
   const int L = n_q >= 1 ? a.uniform_len[0] : -1;
-  bool flat = !exact && tune.sls_flat && n_q >= 1 && L >= 2 && (G == 8 || G == 16 || G == 32);
+  bool flat = !p.weighted && !exact && tune.sls_flat && n_q >= 1 && L >= 2 && (G == 8 || G == 16 || G == 32);
   for (int i = 1; flat && i < n_q; ++i) flat = a.uniform_len[i] == L;
   int bpw = 1;
   if (flat && tune.sls_bpw > 0) {
@@ -936,7 +1027,7 @@ SlsPlan plan_sls(const SlsArgs& a, bool exact, bool short_bags, const Tune& tune
   // lane group per bag is both faster there and bit-exact -- unless the flat variant took the launch above
   p.exact = exact || short_bags;
   // the one-lookup copy form: every coalesced query has fixed bags of ONE row, a row is 4 / 8 / 16 / 32 lanes x 16 B
-  bool one = p.exact && tune.sls_one && n_q >= 1 && (D == 16 || D == 32 || D == 64 || D == 128);
+  bool one = !p.weighted && p.exact && tune.sls_one && n_q >= 1 && (D == 16 || D == 32 || D == 64 || D == 128);
   for (int i = 0; one && i < n_q; ++i) one = a.uniform_len[i] == 1;
   if (one) {
     p.form = SlsForm::one;

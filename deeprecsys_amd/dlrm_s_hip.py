@@ -93,6 +93,22 @@ def _sls_pool(args):
     return _SLS_POOLS[name]
 
 
+_SLS_WEIGHTS = ("none", "uniform")
+
+
+def sls_weights(args, lS_i):
+    """--accel_sls_weights -> per-index weights of the generated input sets, or None ("none", and when the flag is absent).
+    "uniform": one fp32 weight in [0, 1) per index (k / 2^24, so never 1.0), drawn from a RandomState of its own seeded
+    with numpy_rand_seed: the global stream -- indices, dense inputs, tables -- is what it is without the flag."""
+    name = str(getattr(args, "accel_sls_weights", "none") or "none")
+    if name not in _SLS_WEIGHTS:
+        raise ValueError("--accel_sls_weights %r: one of %s" % (name, ", ".join(_SLS_WEIGHTS)))
+    if name == "none":
+        return None
+    rs = np.random.RandomState(int(getattr(args, "numpy_rand_seed", 0)))
+    return [[(rs.randint(0, 1 << 24, size=len(i)) * np.float32(2.0 ** -24)).astype(np.float32) for i in per] for per in lS_i]
+
+
 def _init_table(n, m):
     # models/dlrm_s_caffe2.py:297-299
     return np.random.uniform(low=-np.sqrt(1 / n), high=np.sqrt(1 / n), size=(n, m)).astype(np.float32)
@@ -212,20 +228,23 @@ class _HipNet(object):
         return self
 
     # -- execution ----------------------------------------------------------------
-    def run(self, X=None, S_lengths=None, S_indices=None, enable_prof=False):
+    def run(self, X=None, S_lengths=None, S_indices=None, enable_prof=False, S_weights=None):
         """One forward of a fed batch; returns the time at which input hand-over ended,
-        like the reference's run() (models/dlrm_s_caffe2.py:549-569)."""
+        like the reference's run() (models/dlrm_s_caffe2.py:549-569).  S_weights (stand-alone runs only: the resident
+        input set carries them, the per-call input path is unweighted): per-index weights, one array or None per table."""
         if X is None and S_indices is None:
             X, S_lengths, S_indices = self._cur_inputs
         else:
             self._cur_inputs = (X, S_lengths, S_indices)
+        if S_weights is not None and not getattr(self, "split_load", False):
+            raise ValueError("per-index weights travel with staged batches only (stage_batches, or a stand-alone run)")
         bs = len(S_lengths[0])
         if getattr(self, "split_load", False):
             # stand-alone runs (main() below): the reference's run() feeds the blobs, takes the time, then
             # runs the net (models/dlrm_s_caffe2.py:551-568) -- "data loading" vs "computation".  Same split
             # here: narrow + ENFORCE-check + copy the inputs into a resident input set (synchronous), take the
             # time, then the forward on resident inputs.
-            self.engine.stage_batch(0, X, S_indices, S_lengths)
+            self.engine.stage_batch(0, X, S_indices, S_lengths, weights=S_weights)
             load_time = time.time()
             if enable_prof:
                 self._run_profiled(None, None, None, bs, staged=0)
@@ -285,9 +304,11 @@ class _HipNet(object):
         self._out = outs[-1]
         return outs
 
-    def stage_batches(self, lX, lS_l, lS_i):
+    def stage_batches(self, lX, lS_l, lS_i, lS_w=None):
+        """lS_w: per-index weights of every input set (sls_weights), or None."""
         for j in range(len(lS_l)):
-            self.engine.stage_batch(j, None if lX is None else lX[j], lS_i[j], lS_l[j])
+            self.engine.stage_batch(j, None if lX is None else lX[j], lS_i[j], lS_l[j],
+                                    weights=None if lS_w is None else lS_w[j])
         self._n_staged = len(lS_l)
 
     def tune_table_placement(self, candidates=12, sets=128, spacer_gb=None, policies=(1, 0), max_extra_gb=48, sharers=1):
@@ -570,14 +591,16 @@ class _NoDenseNet(_HipNet):
     """Models whose query is sparse features only (NCF, DIN): the dense argument of the
     reference's signatures is accepted and ignored, as the reference ignores it."""
 
-    def run(self, X=None, S_lengths=None, S_indices=None, enable_prof=False):
+    def run(self, X=None, S_lengths=None, S_indices=None, enable_prof=False, S_weights=None):
         if S_indices is None:
             X, S_lengths, S_indices = self._cur_inputs
         else:
             self._cur_inputs = (X, S_lengths, S_indices)
+        if S_weights is not None and not getattr(self, "split_load", False):
+            raise ValueError("per-index weights travel with staged batches only (stage_batches, or a stand-alone run)")
         bs = len(S_lengths[0])
         if getattr(self, "split_load", False):      # stand-alone runs: see _HipNet.run
-            self.engine.stage_batch(0, None, S_indices, S_lengths)
+            self.engine.stage_batch(0, None, S_indices, S_lengths, weights=S_weights)
             load_time = time.time()
             if enable_prof:
                 self._run_profiled(None, None, None, bs, staged=0)
@@ -595,9 +618,9 @@ class _NoDenseNet(_HipNet):
         self._out = self.engine.forward_inputs(None, list(ids), list(lengths), int(batch_size))
         return self._out
 
-    def stage_batches(self, lX, lS_l, lS_i):
+    def stage_batches(self, lX, lS_l, lS_i, lS_w=None):
         for j in range(len(lS_l)):
-            self.engine.stage_batch(j, None, lS_i[j], lS_l[j])
+            self.engine.stage_batch(j, None, lS_i[j], lS_l[j], weights=None if lS_w is None else lS_w[j])
         self._n_staged = len(lS_l)
 
 
@@ -823,6 +846,7 @@ def standalone(args):
     (nbatches, lT) = dc.generate_output_data()
     lS_l = [[np.asarray(l, dtype=np.int32) for l in per] for per in lS_l]
     lS_i = [[np.asarray(i, dtype=np.int64) for i in per] for per in lS_i]
+    lS_w = sls_weights(args, lS_i)                              # --accel_sls_weights (None: unweighted bags)
     print("Trying to initialize %s" % args.model_type.upper())
     net_cls = WRAPPERS[args.model_type].net_cls
     resident, args.num_batches = args.num_batches, 1      # one resident input set: run() re-feeds it per batch
@@ -836,13 +860,14 @@ def standalone(args):
     print("Created network")
     no_dense = net.engine.m_den == 0
     total_time = dload_time = 0.0
-    net.run(None if no_dense else lX[0], lS_l[0], lS_i[0])          # (first launch: code objects, clocks)
+    net.run(None if no_dense else lX[0], lS_l[0], lS_i[0], S_weights=None if lS_w is None else lS_w[0])   # (first launch: code objects, clocks)
     time_start = time.time()
     print("Running networks")
     for _k in range(args.nepochs):
         for j in range(nbatches):
             time_load_start = time.time()
-            time_load_end = net.run(None if no_dense else lX[j], lS_l[j], lS_i[j], args.enable_profiling)
+            time_load_end = net.run(None if no_dense else lX[j], lS_l[j], lS_i[j], args.enable_profiling,
+                                    S_weights=None if lS_w is None else lS_w[j])
             dload_time += (time_load_end - time_load_start)
     time_end = time.time()
     dload_time *= 1000.

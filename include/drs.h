@@ -192,6 +192,8 @@ int32_t drs_stage_batch(drs_handle h, int32_t batch_id, int32_t n_samples,
                         const int64_t* const* h_idx /*[T] -> [n_idx[t]]*/,
                         const int64_t* n_idx /*[T]*/,
                         const int32_t* const* h_len /*[T] -> [n_samples]*/);
+/* Per-sample weights (SparseLengthsWeightedSum) for a batch that is already staged: drs_stage_batch_weights,
+ * declared in drs_weights.h (included at the end of this header).  drs_stage_batch on the same batch_id drops them. */
 
 /* ---- hot path ---------------------------------------------------------------
  * replaces: run_queues(...) + workspace.RunNet(net) + FetchBlob
@@ -273,6 +275,7 @@ int32_t drs_interaction_width(drs_handle h, int32_t* num_int);
 int32_t drs_sls(drs_handle h, const float* d_W, int64_t rows, int32_t D,
                 const int32_t* d_idx, const int32_t* d_len, int64_t n_bags,
                 int64_t n_idx, float* d_out /*[n_bags, D]*/, int32_t exact_order);
+/* drs_sls_weighted == SparseLengthsWeightedSum([tbl, w, idx, len]): declared in drs_weights.h */
 /* drs_fc == FC([x,W,b]) + Relu|Sigmoid (models/dlrm_s_caffe2.py:258-272)
  *   y = act(x . W^T + b); accumulation is a k-ordered fp32 fma chain (MFMA).   */
 int32_t drs_fc(drs_handle h, const float* d_x, int64_t M, int32_t K, const float* d_W /*[N,K]*/,
@@ -295,7 +298,8 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  *   gather        "sls_exact" 0|1 (1: sequential order, bit-identical to Caffe2's SparseLengthsSum)
  *                 "sls_pool" 0|1 (1: mean pooling, SparseLengthsMean / EmbeddingBag(mode="mean") -- the same form's fp32 sum
  *                 divided by (float)len, one correctly rounded division per element, an empty bag stays +0.0; DLRM, W&D,
- *                 MT-WnD and NCF only; set before or after the table options; same launch forms, same drs_gather_bytes)
+ *                 MT-WnD and NCF only; set before or after the table options; same launch forms, same drs_gather_bytes;
+ *                 refused while a staged batch carries weights, drs_stage_batch_weights)
  *                 "sls_flat" 0|1|2   "sls_bpw" 0|1|2|4   "sls_nt" 0|1   "sls_one" 0|1|16|64
  *                 "din_fused" 0|1   "din_pipe" 0|1   "din_s" 0|1|2|4   "din_nt" 0|1
  *                 "dien_mfma" 0|1|2|3   "dien_fuse_top" 0|1
@@ -320,6 +324,7 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  *                 at D 32; independent of "table_int8_lines"; either order with "table_dtype"; same results)
  *   read only     "preferred_coalesce"  "preferred_slots"  "gather_bound"  "device"
  *                 "table_placements"  "table_bytes"  "table_address"
+ *                 "sls_weighted" (staged batches that carry per-sample weights, drs_stage_batch_weights)
  * Options belong to the handle: two engines in one process (the mixed-model accelerator engine) keep their own.
  * The lab build (make -C deeprecsys_amd/csrc lab-lib, -DDRS_LAB) also takes the lab's instruments and the options
  * of every form that lost its measurement (docs/OPTIONS.md, last section); the product library refuses them.      */
@@ -359,7 +364,8 @@ int32_t drs_debug_gather_stamps(drs_handle h, int32_t slot, uint64_t* out, int64
  * (off by default: DRS_ERR_STATE).                                                                      */
 int32_t drs_last_dispatch(drs_handle h, int32_t slot, char* buf, int64_t cap);
 /* algorithmic bytes of the gather for a query of `bs` samples of `batch_id`:
- * sum over bags of len*D*4 + len*4 + 4 + D*4  (SURVEY.md 8d / BASELINE.md 2)   */
+ * sum over bags of len*D*4 + len*4 + 4 + D*4  (SURVEY.md 8d / BASELINE.md 2);
+ * a batch that carries weights (drs_stage_batch_weights): len*4 more per bag   */
 int32_t drs_gather_bytes(drs_handle h, int32_t batch_id, int32_t bs, int64_t* bytes);
 
 /* ---- multi-GPU: the single collective ---------------------
@@ -383,6 +389,12 @@ int32_t drs_comm_barrier(drs_comm c);
  * of latencies), [2] MIN (first completion time), [3] MAX (last completion time / elapsed) */
 int32_t drs_stats_allreduce(drs_comm c, int64_t* hist, int32_t nbins, double* sum_min_max /*[4]*/);
 const char* drs_comm_last_error(void);
+
+/* ---- entry points of the HIP library beyond the symbol set above ------------------
+ * The declarations above are the ABI that every implementation restates (the CPU restatement under oracle/ among
+ * them) and that DRS_ABI_VERSION counts.  drs_weights.h adds the per-sample-weight entry points, which libdrs_hip.so
+ * alone exports; nothing above changed for them, so the version stays what it is.                                */
+#include "drs_weights.h"
 
 #ifdef __cplusplus
 }
