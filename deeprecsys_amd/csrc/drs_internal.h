@@ -46,7 +46,7 @@ struct SlsArgs {
   int32_t* err;               // device error word: bit0 = index out of range
   uint64_t* ts;               // optional [2 * gridDim.x] start/end wall_clock64() per workgroup
   int32_t nt;                 // fused DIN launch: table rows by non-temporal loads ("sls_nt"; set by launch_din_fused)
-  int32_t pool;               // "sls_pool": 0 a bag's sum | 1 its mean, the finished sum / (float)length (sls.hip pool_finish)
+  int32_t pool;               // "sls_pool": 0 a bag's sum | 1 its mean, the finished sum / (float)length (sls_dev.h pool_finish)
   // int8 / int4 rowwise tables in the line-packed layout ("table_int8_lines" / "table_int4_lines", I8Lines below): row r
   // starts r * PR + (r / n) * ln_pad pieces into its table, r / n == ln_mul ? umulhi(r, ln_mul) >> ln_shift : r.  ln_pad == 0: every other layout.
   uint32_t ln_mul, ln_shift, ln_pad;
@@ -73,7 +73,8 @@ struct Tune {
   uint32_t w_zero_off = 0;          // ... whose first 64 floats are zeros (float offset of them)
   int sls_flat = 1;              // fixed-length bags: all row loads of a wave in flight at once
   int sls_bpw = 0;               // ... bags per wave of that variant (0 = auto | 1 | 2 | 4)
-  int sls_nt = 1;                // table rows are read with non-temporal loads (every gather kernel of sls.hip)
+  int sls_nt = 1;                // table rows are read with non-temporal loads (every gather kernel of sls.hip and sls_wflat.hip)
+  int sls_weighted_flat = 0;     // a WEIGHTED launch may take the flat, flatc and one-lookup forms (their weighted instances: sls_wflat.hip); 0: the ring walk or the any-width form only
   int sls_one = 1;               // fixed bags of ONE row (W&D, MT-WnD, NCF, DIEN): the copy form (sls_one_kernel); 1 = 64 samples per wave, 16 for small launches | 64 | 16 | 0 off
   int din_nt = 1;                // fused DIN launch: non-temporal row loads ("din_nt": +2.5 % queries/s, 0.527 -> 0.545 of peak)
   int din_pipe = 1;              // fused DIN launch, hidden width 1: indices staged in LDS, units pipelined (din_pipe_kernel)
@@ -104,13 +105,14 @@ hipError_t gemm_set_attrs();   // gemm.hip's kernels, on the current device
 hipError_t gemm_bf16_set_attrs();   // gemm_bf16.hip's kernels, on the current device
 hipError_t fused_bf16_set_attrs();  // mlp_fused_bf16.hip's kernels, on the current device
 
-// One gather launch, decided once by plan_sls and run by launch_sls (sls.hip).  Host-only.
+// One gather launch, decided once by plan_sls and run by launch_sls (sls.hip, sls_wflat.hip).  Host-only.
 //   form: any (any row width) | ring (sls_kernel) | one (one lookup per bag) | flat | flatc (fixed-length bags)
 //   exact: the sequential summation order (bit-identical to Caffe2's SparseLengthsSum)
 //   G, NL, BPW, BW, L, nt: the instance -- lanes per row, loads per lane, bags per wave, samples per wave, bag length,
 //   non-temporal row loads; tiles: one-lookup sample tiles per table; grid: workgroups (0: nothing to launch)
-//   weighted: a query of the launch carries per-sample weights (SlsArgs::wgt): the ring walk or the any-width form, in
-//   their weighted instances -- never flat, flatc or one
+//   weighted: a query of the launch carries per-sample weights (SlsArgs::wgt): the weighted instance of the form.  With
+//   "sls_weighted_flat" 0 (the default) that is the ring walk or the any-width form, never flat, flatc or one; with 1 the
+//   form is the one the unweighted launch would take
 //   dtype: element type of the tables a.tables points at (DRS_TABLE_*; a.tab_off counts units of that type:
 //   table_unit_bytes) -- the same decisions and grids for every type, rows widened to fp32 before they are summed
 enum class SlsForm { any, ring, one, flat, flatc };
@@ -129,6 +131,8 @@ SlsPlan plan_sls(const SlsArgs& a, bool exact, bool short_bags, const Tune& tune
 // stop_event (optional): recorded by the gather dispatch itself when it completes
 hipError_t launch_sls(const SlsArgs& a, const SlsPlan& plan, const Tune& tune, hipStream_t stream,
                       hipEvent_t stop_event = nullptr);
+// the weighted flat, flatc and one-lookup launches of launch_sls (sls_wflat.hip; plan.weighted, plan.grid > 0)
+hipError_t launch_sls_wflat(const SlsArgs& a, const SlsPlan& plan, hipStream_t stream, hipEvent_t stop_event);
 // "table_dtype" layouts.  Stored bytes of one row: D elements of 4 (fp32) or 2 (fp16 / bf16) bytes; int8 rowwise: D codes,
 // zero padding to round_up(D, 8), fp32 scale, fp32 bias (every row 8-byte aligned); int4 rowwise: D / 2 code bytes, zero
 // padding to round_up(D / 2, 4), fp16 scale, fp16 bias (every row 4-byte aligned; D even)

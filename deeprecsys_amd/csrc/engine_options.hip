@@ -216,7 +216,7 @@ int64_t weighted_batches(drs_engine* e) {
 }
 
 int32_t set_sls_pool(drs_engine* e, int64_t value) {
-  // Mean pooling: the gather kernels divide every bag's finished sum by its length (sls.hip pool_finish).  One field that
+  // Mean pooling: the gather kernels divide every bag's finished sum by its length (sls_dev.h pool_finish).  One field that
   // every later launch copies into its SlsArgs: nothing is converted, allocated or chosen again.  DIN and DIEN
   // pool by sum only (the fused DIN launch has a gather of its own, din.hip): refused, like their other result-changing options.
   if (value == e->sls_pool) return DRS_OK;
@@ -240,6 +240,8 @@ const OptDesc kOptions[] = {
     OPT("sls_bpw", 0, 4, [](int64_t v) { return v != 3; }, 0, tune.sls_bpw),
     OPT("sls_nt", 0, 1, nullptr, O_BOOL, tune.sls_nt),
     OPT("sls_one", 0, 64, [](int64_t v) { return v == 0 || v == 1 || v == 16 || v == 64; }, 0, tune.sls_one),
+    // 1: a weighted launch takes the form its unweighted twin takes (flat, flatc, one-lookup: sls_wflat.hip); 0: ring / any only
+    OPT("sls_weighted_flat", 0, 1, nullptr, 0, tune.sls_weighted_flat),
     // 1: SparseLengthsMean / EmbeddingBag(mode="mean") -- the same gather form's fp32 sum, divided by the bag's length
     {"sls_pool", 0, 1, nullptr, O_SYNC, [](drs_engine* e) -> int64_t { return e->sls_pool; }, nullptr, set_sls_pool},
     OPT("din_fused", 0, 1, nullptr, O_BOOL, din_fused),

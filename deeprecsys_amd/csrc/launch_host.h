@@ -1,4 +1,4 @@
-// Host helpers shared by the translation units that pick a kernel instance at run time (sls.hip, din.hip, dien.hip).
+// Host helpers shared by the translation units that pick a kernel instance at run time (sls.hip, sls_wflat.hip, din.hip, dien.hip).
 #pragma once
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>

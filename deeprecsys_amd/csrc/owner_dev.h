@@ -1,4 +1,4 @@
-// Device helper shared by the gather translation units (sls.hip, din.hip, dien.hip, din_any.hip): which query of a coalesced
+// Device helper shared by the gather translation units (sls.hip, sls_wflat.hip, din.hip, dien.hip, din_any.hip): which query of a coalesced
 // launch set owns valid-sample number `smp`.
 #pragma once
 #include <hip/hip_runtime.h>

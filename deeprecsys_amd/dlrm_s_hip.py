@@ -93,6 +93,14 @@ def _sls_pool(args):
     return _SLS_POOLS[name]
 
 
+def _sls_weighted_flat(args):
+    """--accel_sls_weighted_flat -> the engine's "sls_weighted_flat" value (0 when the flag is absent)."""
+    v = int(getattr(args, "accel_sls_weighted_flat", 0) or 0)
+    if v not in (0, 1):
+        raise ValueError("--accel_sls_weighted_flat %r: 0 or 1" % (v,))
+    return v
+
+
 _SLS_WEIGHTS = ("none", "uniform")
 
 
@@ -165,6 +173,7 @@ class _HipNet(object):
         int8_lines = _table_int8_lines(a)
         int4_lines = _table_int4_lines(a)
         pool = _sls_pool(a)
+        weighted_flat = _sls_weighted_flat(a)
         def make(n_slots):
             eng = N.Engine(self.kind, self.ln_emb, self.m_spa, ln_bot_cfg, ln_top_cfg,
                            interaction_op=interaction_op, interaction_itself=itself,
@@ -193,6 +202,10 @@ class _HipNet(object):
             # --accel_sls_pool mean: every bag's pooled vector is its mean (only when asked for: a sum engine is never told)
             if pool != N.POOL_SUM:
                 eng.set_option("sls_pool", pool)
+            # --accel_sls_weighted_flat 1: weighted launch sets keep the flat and one-lookup forms (only when asked for: the
+            # CPU restatement of the ABI does not know the key)
+            if weighted_flat:
+                eng.set_option("sls_weighted_flat", weighted_flat)
             return eng
         eng = make(self._num_slots())
         if int(getattr(a, "accel_slots", 0) or 0) <= 0 and eng.get_option("preferred_slots") != eng.num_slots:

@@ -74,6 +74,7 @@ EXTRA_FLAGS = [
     ("accel_sls_pool", _S, "sum"),    # how the accel engines pool an embedding bag: sum (SparseLengthsSum) | mean (SparseLengthsMean, torch's EmbeddingBag(mode="mean"): the fp32 sum / the bag's length; engine option "sls_pool")
     ("accel_table_int4_lines", _I, 0),  # 1 with --accel_table_dtype int4_rowwise: no int4 row crosses a 128-byte line, rows packed 128 // S to a line (engine option "table_int4_lines"; same results)
     ("accel_sls_weights", _S, "none"),  # per-index weights of the staged input sets (SparseLengthsWeightedSum, EmbeddingBag(per_sample_weights=)): none | uniform (one fp32 weight in [0, 1) per index from a RandomState of its own seeded with numpy_rand_seed: indices and dense inputs stay what they are without the flag)
+    ("accel_sls_weighted_flat", _I, 0),  # 1 with --accel_sls_weights: a weighted launch set takes the gather form its unweighted twin takes (flat, flat-coalesced, one-lookup; engine option "sls_weighted_flat") instead of the ring walk
     ("accel_mlp_dtype", _S, "fp32"),  # arithmetic of the wide FC layers (K, N >= 64) on the accel engines: fp32 | bf16 (bf16 operands, fp32 accumulation)
     ("accel_mlp_bf16_fuse", _I, 0),   # 1 with --accel_mlp_dtype bf16: DLRM's bottom MLP + interaction + top MLP, and NCF's Sum + MLP branch + predictor, stay one launch, the bf16 layers inside it (engine option "mlp_bf16_fuse")
     ("accel_table_placements", _I, 12),  # places in HBM tried for the table arena at engine start (1 = wherever hipMalloc put it)
@@ -98,7 +99,7 @@ def debugPrint(args, system_tag, message):
 # EXTRA_FLAGS that take one of a few words
 FLAG_CHOICES = {"accel_table_dtype": ("fp32", "fp16", "bf16", "int8_rowwise", "int4_rowwise"), "accel_mlp_dtype": ("fp32", "bf16"),
                 "accel_mlp_bf16_fuse": (0, 1), "accel_table_int8_lines": (0, 1), "accel_table_int4_lines": (0, 1), "accel_sls_pool": ("sum", "mean"),
-                "accel_sls_weights": ("none", "uniform")}
+                "accel_sls_weights": ("none", "uniform"), "accel_sls_weighted_flat": (0, 1)}
 
 
 def build_parser():

@@ -301,6 +301,9 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  *                 MT-WnD and NCF only; set before or after the table options; same launch forms, same drs_gather_bytes;
  *                 refused while a staged batch carries weights, drs_stage_batch_weights)
  *                 "sls_flat" 0|1|2   "sls_bpw" 0|1|2|4   "sls_nt" 0|1   "sls_one" 0|1|16|64
+ *                 "sls_weighted_flat" 0|1 (1: a launch set that carries per-sample weights, drs_stage_batch_weights, takes
+ *                 the gather form its unweighted twin takes -- flat, flat-coalesced, one-lookup -- in that form's order;
+ *                 0, the default: the ring walk or the any-width form)
  *                 "din_fused" 0|1   "din_pipe" 0|1   "din_s" 0|1|2|4   "din_nt" 0|1
  *                 "dien_mfma" 0|1|2|3   "dien_fuse_top" 0|1
  *   MLP side      "mlp_fuse" 0|1   "mlp_split" 0|1   "mlp_wide_kn" n   "gemm_split" 0|1

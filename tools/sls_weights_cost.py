@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """What per-sample weights cost the gather launch at RMC1's shape (8 tables x D 64, fixed L 80, 256 samples per query).
 
-Three arms on one engine, same tables and indices, the launch timed by the kernels' own clock stamps (drs_kernel_time,
+Four arms on one engine, same tables and indices, the launch timed by the kernels' own clock stamps (drs_kernel_time,
 DRS_KERNEL_SLS_CLOCK), alternating `--rounds` times:
   flatc     the unweighted default (sls_flatc_kernel<16,20,nt>)
   ring      the unweighted ring walk, forced with "sls_flat" 0 (sls_kernel<16,split,nt>)
   ring,w    the weighted ring walk (sls_kernel<16,split,nt,w>): the batches carry uniform [0, 1) weights
-for single queries and for launch sets of `--coalesce` queries.  The byte model allows the weighted ring walk
-(row bytes + 8) / (row bytes + 4) over the unweighted one: a looked-up row moves its bytes, a 4-byte index and now a
-4-byte weight.  Prints one JSON line.  Needs a GPU.
+  flatc,w   the same weighted batches under "sls_weighted_flat" 1: the form of the unweighted default with weights
+            (sls_flatc_kernel<16,20,nt,w>)
+for single queries and for launch sets of `--coalesce` queries.  The byte model allows a weighted launch
+(row bytes + 8) / (row bytes + 4) over its unweighted twin: a looked-up row moves its bytes, a 4-byte index and now a
+4-byte weight.  With `--lookups 1 --dim 32` the arms are the one-lookup copy form and the sequential walk (the arm names
+stay; the `form` of every run is in the output).  Prints one JSON line.  Needs a GPU.
 """
 import argparse
 import json
@@ -70,25 +73,33 @@ def main():
         form = [tok for tok in eng.last_dispatch(0 if n_q == 1 else 1) if tok.startswith("sls_")][0]
         return 1e3 * ms / max(n, 1), eng.kernel_bytes(N.KERNEL_SLS_CLOCK) / max(n, 1), form
 
-    arms = [("flatc", 1, False), ("ring", 0, False), ("ring,w", 1, True)]
+    # (name, "sls_flat" / "sls_one", weights staged, "sls_weighted_flat")
+    arms = [("flatc", 1, False, 0), ("ring", 0, False, 0), ("ring,w", 1, True, 0), ("flatc,w", 1, True, 1)]
     out = {"shape": dict(tables=T, rows=a.rows, D=D, L=L, batch=B), "iters": a.iters, "runs": []}
     for r in range(a.rounds):
-        for name, flat, weighted in arms:
+        for name, flat, weighted, wflat in arms:
             stage(weighted)
             eng.set_option("sls_flat", flat)
+            eng.set_option("sls_one", flat)
+            eng.set_option("sls_weighted_flat", wflat)
             for n_q in (1, a.coalesce):
                 us, nbytes, form = timed(n_q)
                 out["runs"].append(dict(round=r, arm=name, queries=n_q, us_per_launch=round(us, 2), bytes_per_launch=int(nbytes),
                                         gbs=round(nbytes / us / 1e3, 1), form=form))
     eng.set_option("sls_flat", 1)
+    eng.set_option("sls_one", 1)
+    eng.set_option("sls_weighted_flat", 0)
     row_bytes = D * 4
     out["byte_model_ring_w_over_ring"] = round((row_bytes + 8) / (row_bytes + 4), 4)
+    out["byte_model_flatc_w_over_flatc"] = out["byte_model_ring_w_over_ring"]
     for n_q in (1, a.coalesce):
         med = {name: float(np.median([x["us_per_launch"] for x in out["runs"] if x["arm"] == name and x["queries"] == n_q]))
-               for name, _, _ in arms}
+               for name, _, _, _ in arms}
         out["median_us_%dq" % n_q] = med
         out["ring_w_over_ring_%dq" % n_q] = round(med["ring,w"] / med["ring"], 4)
         out["ring_w_over_flatc_%dq" % n_q] = round(med["ring,w"] / med["flatc"], 4)
+        out["flatc_w_over_flatc_%dq" % n_q] = round(med["flatc,w"] / med["flatc"], 4)
+        out["flatc_w_over_ring_w_%dq" % n_q] = round(med["flatc,w"] / med["ring,w"], 4)
     eng.close()
     print(json.dumps(out))
 
