@@ -126,7 +126,7 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
 
   // Control flow is kept WAVE-UNIFORM: every lane runs as many rounds as the
   // longest bag in the wave needs (shorter bags re-read their last row, an L1
-  // hit, and add +0.0f).  With scalar branches each pipeline arm below is one
+  // hit, and add +0.0f in its place, weighted or not: the row's value is dropped).  With scalar branches each pipeline arm below is one
   // straight-line block, so the compiler's s_waitcnt vmcnt(N) counts stay exact
   // and U..2U row loads per lane remain outstanding.
   const int len = end - beg;
@@ -178,11 +178,12 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
         rsb[u] = E::template load_sb<NT>(rp_, sbd);
       }
     };
-    // (weighted: the clamped re-reads past the bag's end take the weight 0 -- they must not add w * x)
+    // (weighted: the clamped re-reads past the bag's end, and row 0 read for an empty bag, are dropped by keep like the
+    // unweighted ones -- masking the weight would turn an inf or NaN element of such a row into fma(0, x, acc) == NaN)
     auto consume = [&](const piece (&ring)[U], const sbt (&rsb)[U], const wt (&rw)[U], int pos) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        if constexpr (WGT) E::addw(acc, pos + u * STEP < n ? rw[u] : 0.0f, ring[u], rsb[u]);
+        if constexpr (WGT) E::addw(acc, pos + u * STEP < n, rw[u], ring[u], rsb[u]);
         else E::add(acc, pos + u * STEP < n, ring[u], rsb[u]);
       }
     };

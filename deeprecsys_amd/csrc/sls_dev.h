@@ -84,11 +84,12 @@ struct PlainRow {
   template <class P>
   __device__ static __forceinline__ void add(float4& acc, bool keep, const P& p, NoSb) { vadd(acc, vsel(keep, Self::up(p))); }
   // the weighted step, acc = fma(w, x, acc) per column: torch's CPU embedding_bag(per_sample_weights=), one rounding per
-  // column and row.  w == 1.0f is add's acc + x; a row that must not count comes with w == 0.0f -- fma(0, x, acc) == acc
-  // for every finite x (acc is never -0: it starts at +0 and a sum that cancels is +0).
+  // column and row.  w == 1.0f is add's acc + x.  A row that must not count comes with keep == false and is zeroed before
+  // the fma, as add zeroes it: fma(w, +0, acc) == acc for every finite w (acc is never -0: it starts at +0 and a sum that
+  // cancels is +0).  Its weight alone must not mask it -- fma(0, x, acc) is acc for a finite x only, NaN for +-inf and NaN.
   template <class P>
-  __device__ static __forceinline__ void addw(float4& acc, float w, const P& p, NoSb) {
-    const float4 x = Self::up(p);
+  __device__ static __forceinline__ void addw(float4& acc, bool keep, float w, const P& p, NoSb) {
+    const float4 x = vsel(keep, Self::up(p));
     acc.x = __fmaf_rn(w, x.x, acc.x); acc.y = __fmaf_rn(w, x.y, acc.y); acc.z = __fmaf_rn(w, x.z, acc.z); acc.w = __fmaf_rn(w, x.w, acc.w);
   }
   __device__ static __forceinline__ float addw1(float acc, float w, float x) { return __fmaf_rn(w, x, acc); }
@@ -154,12 +155,14 @@ struct I8 {
   }
   // the weighted step (FBGEMM's and torch's embedding_bag_byte_rowwise_offsets with per_sample_weights): the row's scale
   // and bias are multiplied by its weight first -- two fp32 products -- and go through row1 as they are.  w == 1.0f
-  // is add; w == 0.0f (a row that must not count) adds acc + 0 + 0 * q == acc.
+  // is add; a row that must not count (keep == false) takes w = 0.0f and adds acc + 0 + 0 * q == acc: exact for the finite
+  // scale and bias a rowwise row has by contract.
   // (The two products are written under contract(off): __fmul_rn is a plain, contractable `x * y` to this compiler, which
   // folds w * bias into row1's acc + b as one fma in some instances -- the weighted flat forms at 20 loads per lane --
   // and then rounds once where the operator rounds twice.  The pragma does not reach into an inlined callee.)
-  __device__ static __forceinline__ void addw(float4& acc, float w, uint32_t p, float2 sb) {
+  __device__ static __forceinline__ void addw(float4& acc, bool keep, float w, uint32_t p, float2 sb) {
 #pragma clang fp contract(off)
+    w = keep ? w : 0.0f;
     const float s = w * sb.x, b = w * sb.y;
     acc.x = row1(s, b, (float)(p & 0xffu), acc.x);
     acc.y = row1(s, b, (float)((p >> 8) & 0xffu), acc.y);
@@ -218,8 +221,9 @@ struct I4 {
     acc.w = row1(s, b, (float)(p >> 12), acc.w);
   }
   // the weighted step: I8's, on the widened fp16 scale and bias (embedding_bag_4bit_rowwise_offsets with per_sample_weights)
-  __device__ static __forceinline__ void addw(float4& acc, float w, uint16_t p16, uint32_t w32) {
+  __device__ static __forceinline__ void addw(float4& acc, bool keep, float w, uint16_t p16, uint32_t w32) {
 #pragma clang fp contract(off)   // (as I8::addw: the two products stay products)
+    w = keep ? w : 0.0f;
     const float2 f = up_sb(w32);
     const float s = w * f.x, b = w * f.y;
     const uint32_t p = p16;
@@ -335,7 +339,7 @@ __global__ __launch_bounds__(64) void sls_one_kernel(SlsArgs a, int tiles) {
     for (int j = 0; j < M; ++j)
       if (vr[j] >= 0) {
         float4 o = vzero4();                                  // 0.0f + row: the one-row bag's value
-        if constexpr (WGT) E::addw(o, kp[j] != 0 ? wj[j] : 0.0f, v[j], sb[j]);
+        if constexpr (WGT) E::addw(o, kp[j] != 0, wj[j], v[j], sb[j]);
         else E::add(o, kp[j] != 0, v[j], sb[j]);
         pool_finish(o, a.pool, 1);                            // a one-row bag's mean: x / 1.0f == x, the same bits
         *reinterpret_cast<float4*>(out + (int64_t)vr[j] * a.ld_out) = o;
@@ -353,8 +357,9 @@ __global__ __launch_bounds__(64) void sls_one_kernel(SlsArgs a, int tiles) {
 // T % BPW == 0 (checked by plan_sls).
 // WGT: the weighted instance ("sls_weighted_flat" 1).  A row's weight lies where its index lies in the owning query's
 // a.wgt entry (the sample is wave-uniform: a scalar pointer; null: every weight 1.0f): phase 1 loads it through the
-// address pattern of the index, and bag k adds E::addw with it -- with 0.0f for a row of another bag, past the wave's
-// rows or out of range -- in the order of the unweighted sums.  WGT is E::weighted (E = Wgt<policy>); with it false nothing
+// address pattern of the index, and bag k adds E::addw with it in the order of the unweighted sums -- a row of another bag
+// or past the wave's rows is dropped (keep == false: its value never reaches the sum, whatever it holds), an out-of-range
+// row takes the weight 0.0f.  WGT is E::weighted (E = Wgt<policy>); with it false nothing
 // that names a weight exists.
 template <int G, int NL, int BPW, bool NT = false, class E = F32>
 __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_order) {
@@ -492,7 +497,7 @@ __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_
     const int j = g + NG * u;
     if constexpr (WGT) {
 #pragma unroll
-      for (int k = 0; k < BPW; ++k) E::addw(acc[k], j < R && kj[u] == k ? wr[u] : 0.0f, v[u], sb[u]);
+      for (int k = 0; k < BPW; ++k) E::addw(acc[k], j < R && kj[u] == k, wr[u], v[u], sb[u]);
     } else if (BPW == 1) {
       E::add(acc[0], j < R, v[u], sb[u]);
     } else {
@@ -532,8 +537,9 @@ __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_
 // take this one ("sls_flat" 1) and the phased form serves the several-bags-per-wave shapes.
 // WGT: the weighted instance ("sls_weighted_flat" 1).  The lane that owns flattened row i reads its weight beside its index
 // -- the same coalesced pattern on the owning query's a.wgt entry (the sample is wave-uniform: a scalar pointer; null:
-// every weight 1.0f), 0.0f for i >= R and for an out-of-range row -- and at sum time the loading lanes fetch it as they
-// fetched the row offset; the sum is E::addw in the same u order, then the same butterfly.  WGT is E::weighted
+// every weight 1.0f), 0.0f for an out-of-range row -- and at sum time the loading lanes fetch it as they fetched the row
+// offset; the sum is E::addw in the same u order with the unweighted j < R as its keep (the re-read row R - 1 is dropped,
+// whatever it holds), then the same butterfly.  WGT is E::weighted
 // (E = Wgt<policy>); with it false nothing that names a weight exists.
 template <int G, int NL, bool NT, class E = F32>
 __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
@@ -636,9 +642,9 @@ __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
 #pragma unroll
   for (int u = 0; u < NL; ++u) {
     const int j = g + NG * u;
-    if constexpr (WGT) {   // (one bag per wave; row j >= R has the weight 0 of its owner)
+    if constexpr (WGT) {   // (one bag per wave; row j >= R is the re-read row R - 1: dropped like the unweighted one)
       static_assert(BPW == 1, "one bag per wave");
-      E::addw(acc[0], __shfl(rwgt[(NG * u) >> 6], j & 63), v[u], sb[u]);
+      E::addw(acc[0], j < R, __shfl(rwgt[(NG * u) >> 6], j & 63), v[u], sb[u]);
     } else if (BPW == 1) {
       E::add(acc[0], j < R, v[u], sb[u]);
     } else {
