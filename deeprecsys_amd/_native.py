@@ -18,6 +18,7 @@ OK, ERR_BAD_ARG, ERR_OOM, ERR_HIP, ERR_INDEX_RANGE, ERR_LENGTHS_SUM, ERR_STATE, 
 MODEL_DLRM, MODEL_WND, MODEL_NCF, MODEL_MTWND, MODEL_DIN, MODEL_DIEN = 0, 1, 2, 3, 4, 5
 INTERACT_DOT, INTERACT_CAT = 0, 1
 TABLE_FP32, TABLE_FP16, TABLE_BF16 = 0, 1, 2   # option "table_dtype": element type of the stored tables
+TABLE_FP8_E4M3 = 4                              # ... OCP fp8 e4m3 codes (torch's float8_e4m3fn) under one power-of-two scale per table (Engine.table_fp8_exponent)
 TABLE_INT8_ROWWISE = 8                          # ... 8-bit codes with an fp32 scale and bias per row (Caffe2's Fused8BitRowwise)
 TABLE_INT4_ROWWISE = 9                          # ... 4-bit codes with an fp16 scale and bias per row (torch's embedding_bag_4bit_prepack; even D)
 POOL_SUM, POOL_MEAN = 0, 1                      # option "sls_pool": a bag's pooled vector is its sum | its mean (the fp32 sum / length)
@@ -94,6 +95,12 @@ WEIGHT_SYMBOLS = [
 ]
 
 
+# fp8 e4m3 tables ("table_dtype" 4): the read-back of a table's scale exponent, include/drs_fp8.h -- the HIP build alone, as above
+FP8_SYMBOLS = [
+    ("drs_table_fp8_exponent", C.c_int32, [C.c_void_p, C.c_int32, _i32p]),
+]
+
+
 class ModelCfg(C.Structure):
     _fields_ = [
         ("model_kind", C.c_int32), ("num_tables", C.c_int32), ("table_rows", _i64p),
@@ -139,7 +146,7 @@ def lib():
         if not backend.startswith(b"hip:"):
             raise ImportError("%s identifies itself as %r: deeprecsys_amd binds the HIP build only "
                               "(the CPU restatement of the ABI is test infrastructure)" % (LIB_PATH, backend))
-        for name, res, args in WEIGHT_SYMBOLS:     # (the HIP build alone exports these)
+        for name, res, args in WEIGHT_SYMBOLS + FP8_SYMBOLS:     # (the HIP build alone exports these)
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -230,6 +237,13 @@ class Engine(object):
 
     def fill_table_uniform(self, t, lo, hi, seed):
         self._check(lib().drs_fill_table_uniform(self._h, t, lo, hi, seed), "drs_fill_table_uniform")
+
+    def table_fp8_exponent(self, t):
+        """k of table t under "table_dtype" 4: its stored codes are e4m3_rne(x * 2**k), served as decode(code) * 2**-k
+        (ERR_UNSUPPORTED unless the tables are fp8)."""
+        k = C.c_int32(0)
+        self._check(lib().drs_table_fp8_exponent(self._h, int(t), C.byref(k)), "drs_table_fp8_exponent")
+        return int(k.value)
 
     def set_fc(self, mlp, layer, W, b):
         W, b = _f32(W), _f32(b)

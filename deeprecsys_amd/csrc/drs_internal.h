@@ -29,6 +29,9 @@ struct SlsArgs {
   const float* tables;        // base of the table arena
   const int64_t* tab_off;     // [T] offset of table t in the arena, in units of its type (table_unit_bytes)
   const int64_t* tab_rows;    // [T]
+  // fp8 e4m3 tables ("table_dtype" 4): [T] each table's 2^-k (fp8_exponent below).  The fp8 instances multiply a bag's
+  // finished sum of decoded codes by it; no other instance reads it (null for every other type).
+  const float* tab_scale;
   QTable q;                   // which query a bag belongs to
   const int32_t* idx[DRS_MAX_COALESCE];   // per query: [T][idx_stride] int32 indices (Cast op done)
   const int32_t* off[DRS_MAX_COALESCE];   // per query: [T][off_stride] exclusive prefix sums of lengths
@@ -135,10 +138,14 @@ hipError_t launch_sls(const SlsArgs& a, const SlsPlan& plan, const Tune& tune, h
 hipError_t launch_sls_wflat(const SlsArgs& a, const SlsPlan& plan, hipStream_t stream, hipEvent_t stop_event);
 // "table_dtype" layouts.  Stored bytes of one row: D elements of 4 (fp32) or 2 (fp16 / bf16) bytes; int8 rowwise: D codes,
 // zero padding to round_up(D, 8), fp32 scale, fp32 bias (every row 8-byte aligned); int4 rowwise: D / 2 code bytes, zero
-// padding to round_up(D / 2, 4), fp16 scale, fp16 bias (every row 4-byte aligned; D even)
+// padding to round_up(D / 2, 4), fp16 scale, fp16 bias (every row 4-byte aligned; D even); fp8 e4m3: D codes of one byte,
+// no header (the table's power-of-two scale lives beside tab_off: SlsArgs::tab_scale)
 inline bool table_rowwise(int dtype) { return dtype == DRS_TABLE_INT8_ROWWISE || dtype == DRS_TABLE_INT4_ROWWISE; }
+// the types whose arena is laid out in bytes, table by table (table_unit_bytes 1): conversions into or out of them run per table
+inline bool table_bytewise(int dtype) { return table_rowwise(dtype) || dtype == DRS_TABLE_FP8_E4M3; }
 inline int64_t table_row_stride(int dtype, int64_t D) {
   if (dtype == DRS_TABLE_INT4_ROWWISE) return (D / 2 + 3) / 4 * 4 + 4;
+  if (dtype == DRS_TABLE_FP8_E4M3) return D;
   return dtype == DRS_TABLE_INT8_ROWWISE ? (D + 7) / 8 * 8 + 8 : D * (dtype == DRS_TABLE_FP32 ? 4 : 2);
 }
 // bytes a gathered row moves (the algorithmic count of drs_gather_bytes and of the launch-form choice): int8 rowwise D + 8,
@@ -147,8 +154,19 @@ inline int64_t table_row_bytes(int dtype, int64_t D) {
   if (dtype == DRS_TABLE_INT4_ROWWISE) return D / 2 + 4;
   return dtype == DRS_TABLE_INT8_ROWWISE ? D + 8 : table_row_stride(dtype, D);
 }
-// what a table offset (SlsArgs::tab_off, drs_engine::tab_off) counts: elements (4 / 2 bytes), or bytes for the rowwise types
-inline int64_t table_unit_bytes(int dtype) { return dtype == DRS_TABLE_FP32 ? 4 : table_rowwise(dtype) ? 1 : 2; }
+// what a table offset (SlsArgs::tab_off, drs_engine::tab_off) counts: elements (4 / 2 bytes), or bytes for the rowwise types and fp8
+inline int64_t table_unit_bytes(int dtype) { return dtype == DRS_TABLE_FP32 ? 4 : table_bytewise(dtype) ? 1 : 2; }
+
+// fp8 e4m3 tables: the scale exponent of a table whose largest finite |x| is absmax -- the largest k with
+// absmax * 2^k <= 448 = 0.875 * 2^9, clamped to [-64, 64]; 0 for an all-zero table
+inline int32_t fp8_exponent(float absmax) {
+  if (!(absmax > 0.0f) || __builtin_isinf(absmax)) return 0;
+  int e = 0;
+  const float m = __builtin_frexpf(absmax, &e);           // absmax = m * 2^e, m in [0.5, 1)
+  const int k = m <= 0.875f ? 9 - e : 8 - e;
+  return k < -64 ? -64 : k > 64 ? 64 : k;
+}
+inline float fp8_pow2(int32_t k) { return __builtin_ldexpf(1.0f, k); }
 
 // "table_int8_lines" / "table_int4_lines": rowwise rows that never cross a 128-byte line.  When the row stride S =
 // table_row_stride(dtype, D) < 128 does not divide 128, n = 128 / S rows share a line: row r starts at byte
@@ -360,7 +378,17 @@ hipError_t launch_convert_table(const void* src, int src_dtype, void* dst, int d
 // rows' bytes moved from one layout to the other.  A rowwise side is the TABLE's base, in the layout n_src / n_dst
 // (I8Lines::n of its own type), and the rows are its rows first .. first + rows - 1 of `total` (the last row of a table
 // clears the rest of its line); the other side is the rows themselves, D elements each.
+// An fp8 e4m3 source (src: the table's codes, rows x D bytes; dst_dtype any other type): each code's value
+// decode(code) * src_scale, rounded or quantized as dst_dtype asks.
 hipError_t launch_convert_rows(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t rows, int D, hipStream_t stream,
-                               int32_t n_src = 0, int32_t n_dst = 0, int64_t first = 0, int64_t total = -1);
+                               int32_t n_src = 0, int32_t n_dst = 0, int64_t first = 0, int64_t total = -1, float src_scale = 1.0f);
+// Into fp8 e4m3 ("table_dtype" 4).  The source is rows x D elements of type src_dtype (fp32 / fp16 / bf16: the engine
+// refuses 8 -> 4 and 9 -> 4) or the device fill's values of table t.
+//   launch_absmax_rows: atomicMax of the bits of |x| over the source's FINITE values into *d_bits (a device word the caller zeroed)
+//   launch_rows_to_fp8 / launch_fill_uniform_fp8: dst[r * D + c] = e4m3_rne(x * mul), mul = 2^k -- torch's float8_e4m3fn
+//   conversion bit for bit (round to nearest even, subnormals included; NaN and +-inf: 0x7F with the sign bit)
+hipError_t launch_absmax_rows(const void* src, int src_dtype, int64_t rows, int D, uint32_t* d_bits, hipStream_t stream);
+hipError_t launch_rows_to_fp8(const void* src, int src_dtype, uint8_t* dst, int64_t rows, int D, float mul, hipStream_t stream);
+hipError_t launch_fill_uniform_fp8(uint8_t* dst, int64_t rows, int D, int32_t t, float lo, float hi, uint64_t seed, float mul, hipStream_t stream);
 
 }  // namespace drs

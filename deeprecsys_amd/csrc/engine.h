@@ -6,7 +6,8 @@
 //   tables   one arena, rows row-major ("table_dtype": rows*D fp32, fp16 or bf16, table t at a 64-element aligned offset;
 //            int8 rowwise: rows of round_up(D, 8) + 8 bytes, table t at a 256-byte aligned offset; "table_int8_lines" 1:
 //            128 / S rows to a 128-byte line where S does not divide 128; int4 rowwise: rows of round_up(D / 2, 4) + 4
-//            bytes, table t at a 256-byte aligned offset, "table_int4_lines" 1: the same line packing -- table_layout)
+//            bytes, table t at a 256-byte aligned offset, "table_int4_lines" 1: the same line packing; fp8 e4m3: rows of D
+//            bytes, table t at a 256-byte aligned offset, one power-of-two scale per table in d_tab_scale -- table_layout)
 //   weights  one arena: all biases back to back (layer order, padded to 4 floats), then per
 //            layer W [N, K] dense row-major (as fed by the reference)
 //   batches  per staged batch: dense [max_batch, m_den] f32 | idx [T, cap] i32 |
@@ -212,6 +213,11 @@ struct drs_engine {
   int vmm_shuffle = 0;              // lab: map the chunks in a permuted order (neighbouring addresses, distant memory)
   int64_t* d_tab_off = nullptr;
   int64_t* d_tab_rows = nullptr;
+  // "table_dtype" 4 (fp8 e4m3): each table's scale exponent k (drs_table_fp8_exponent; 0 under every other type), its
+  // 2^-k on the device (SlsArgs::tab_scale), and the word the device absmax reduction of a conversion lands in
+  std::vector<int32_t> fp8_k;
+  float* d_tab_scale = nullptr;
+  uint32_t* d_absmax = nullptr;
   std::vector<bool> table_set;
   Mlp bot, top, fin;
   std::vector<Mlp> tasks;        // MT-WnD task heads
@@ -316,6 +322,7 @@ std::vector<Mlp*> served_mlps(drs_engine* e);
 hipError_t build_bf16_twin(Layer& L);
 // where the tables of an arena of type `dtype` start (*off, units of table_unit_bytes) and its bytes; lines: "table_int8_lines" / "table_int4_lines", the option of that type
 size_t table_layout(const drs_engine* e, int dtype, std::vector<int64_t>* off, int lines = 0);
+hipError_t upload_fp8_scales(drs_engine* e);   // fp8_k -> d_tab_scale
 int32_t fail(drs_engine* e, int32_t code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
 int32_t set_device(drs_engine* e);
 int32_t alloc_batch(drs_engine* e, Batch& b);

@@ -222,14 +222,21 @@ void drs::eng::choose_launch_forms(drs_engine* e) {
   if (e->kind == DRS_MODEL_WND) { e->tune.gemm32_small = 12; e->tune.gemm32_small_blocks = 384; }
 }
 
+// each table's 2^-k where the fp8 gather instances read it (SlsArgs::tab_scale)
+hipError_t drs::eng::upload_fp8_scales(drs_engine* e) {
+  std::vector<float> sc((size_t)e->T);
+  for (int t = 0; t < e->T; ++t) sc[(size_t)t] = fp8_pow2(-e->fp8_k[(size_t)t]);
+  return hipMemcpy(e->d_tab_scale, sc.data(), sizeof(float) * sc.size(), hipMemcpyHostToDevice);
+}
+
 size_t drs::eng::table_layout(const drs_engine* e, int dtype, std::vector<int64_t>* off, int lines) {
   int64_t o = 0;
   const int32_t n = table_lines(dtype, e->D, lines).n;
   off->resize((size_t)e->T);
   for (int t = 0; t < e->T; ++t) {
     (*off)[(size_t)t] = o;
-    o += table_rowwise(dtype) ? round_up(i8_table_bytes(e->rows[t], table_row_stride(dtype, e->D), n), 256)   // bytes
-                              : round_up(e->rows[t] * e->D, 64);                                    // elements
+    o += table_bytewise(dtype) ? round_up(i8_table_bytes(e->rows[t], table_row_stride(dtype, e->D), n), 256)   // bytes (fp8: rows * D)
+                               : round_up(e->rows[t] * e->D, 64);                                    // elements
   }
   return (size_t)o * (size_t)table_unit_bytes(dtype);
 }
@@ -401,6 +408,10 @@ int32_t drs_create(const drs_model_cfg* cfg, int32_t device_id, drs_handle* out)
   CREATE_TRY(hipMalloc(&e->d_op_tab, sizeof(int64_t) * 2));
   CREATE_TRY(hipMemcpy(e->d_tab_off, e->tab_off.data(), sizeof(int64_t) * T, hipMemcpyHostToDevice));
   CREATE_TRY(hipMemcpy(e->d_tab_rows, e->rows.data(), sizeof(int64_t) * T, hipMemcpyHostToDevice));
+  e->fp8_k.assign(T, 0);
+  CREATE_TRY(hipMalloc(&e->d_tab_scale, sizeof(float) * T));
+  CREATE_TRY(hipMalloc(&e->d_absmax, sizeof(uint32_t)));
+  CREATE_TRY(upload_fp8_scales(e));
 
   e->cap = (int64_t)e->max_batch * e->max_lookups;
   e->max_rows = (int64_t)DRS_MAX_COALESCE * ((e->max_batch + 63) / 64 * 64);
@@ -584,6 +595,8 @@ int32_t drs_destroy(drs_handle e) {
   if (e->probe_err) (void)hipFree(e->probe_err);
   if (e->d_tab_off) (void)hipFree(e->d_tab_off);
   if (e->d_tab_rows) (void)hipFree(e->d_tab_rows);
+  if (e->d_tab_scale) (void)hipFree(e->d_tab_scale);
+  if (e->d_absmax) (void)hipFree(e->d_absmax);
   if (e->d_op_tab) (void)hipFree(e->d_op_tab);
   DTR("device memory freed");
   delete e;
@@ -607,6 +620,18 @@ int32_t drs_set_table(drs_handle e, int32_t t, const float* h_W, int64_t rows) {
     // elements), and are rounded or quantized on the device
     const int dt = e->table_dtype;
     const int64_t D = e->D, chunk = std::min<int64_t>(rows, std::max<int64_t>(((int64_t)16 << 20) / D, 1));
+    // fp8 e4m3: the table's scale first -- one pass over the caller's array for the largest finite |x|
+    float mul = 1.0f;
+    if (dt == DRS_TABLE_FP8_E4M3) {
+      float absmax = 0.0f;
+      for (int64_t i = 0, n = rows * D; i < n; ++i) {
+        const float v = fabsf(h_W[i]);
+        if (v > absmax && v < INFINITY) absmax = v;
+      }
+      e->fp8_k[(size_t)t] = fp8_exponent(absmax);
+      mul = fp8_pow2(e->fp8_k[(size_t)t]);
+      HIP_TRY(e, upload_fp8_scales(e));
+    }
     char* dst = reinterpret_cast<char*>(e->tables) + e->tab_off[t] * table_unit_bytes(dt);
     float* stage = nullptr;
     HIP_TRY(e, hipMalloc(&stage, sizeof(float) * (size_t)(chunk * D)));
@@ -614,7 +639,9 @@ int32_t drs_set_table(drs_handle e, int32_t t, const float* h_W, int64_t rows) {
     for (int64_t i = 0; i < rows && r == hipSuccess; i += chunk) {
       const int64_t m = std::min(chunk, rows - i);
       r = hipMemcpy(stage, h_W + i * D, sizeof(float) * (size_t)(m * D), hipMemcpyHostToDevice);
-      if (r == hipSuccess)
+      if (r == hipSuccess && dt == DRS_TABLE_FP8_E4M3)
+        r = launch_rows_to_fp8(stage, DRS_TABLE_FP32, reinterpret_cast<uint8_t*>(dst) + i * D, m, (int)D, mul, nullptr);
+      else if (r == hipSuccess)
         // (rowwise: the kernel places rows i .. i + m - 1 of the table itself -- an int8 chunk may start inside a line)
         r = table_rowwise(dt) ? launch_convert_rows(stage, DRS_TABLE_FP32, dst, dt, m, (int)D, nullptr, 0, e->i8l.n, i, rows)
                               : launch_convert_table(stage, DRS_TABLE_FP32, dst + i * table_row_stride(dt, D), dt, m * D, nullptr);
@@ -632,10 +659,32 @@ int32_t drs_fill_table_uniform(drs_handle e, int32_t t, float lo, float hi, uint
   if (rc) return rc;
   if (t < 0 || t >= e->T) return fail(e, DRS_ERR_BAD_ARG, "bad table id");
   if (e->arenas.size() > 1) { if ((rc = drs_sync(e))) return rc; drop_other_placements(e); }
+  if (e->table_dtype == DRS_TABLE_FP8_E4M3) {
+    // fp8 e4m3: the scale comes from the bounds, max(|lo|, |hi|) -- the samples are not inspected, so k may be one less
+    // than the conversion of the same fp32 fill would pick
+    if ((rc = drs_sync(e))) return rc;
+    e->fp8_k[(size_t)t] = fp8_exponent(std::max(fabsf(lo), fabsf(hi)));
+    HIP_TRY(e, upload_fp8_scales(e));
+    HIP_TRY(e, launch_fill_uniform_fp8(reinterpret_cast<uint8_t*>(e->tables) + e->tab_off[t], e->rows[t], e->D, t, lo, hi, seed,
+                                       fp8_pow2(e->fp8_k[(size_t)t]), e->slots[0].stream));
+    HIP_TRY(e, hipStreamSynchronize(e->slots[0].stream));
+    e->table_set[t] = true;
+    return DRS_OK;
+  }
   HIP_TRY(e, launch_fill_uniform_dtype(reinterpret_cast<char*>(e->tables) + e->tab_off[t] * table_unit_bytes(e->table_dtype), e->table_dtype,
                                        e->rows[t], e->D, t, lo, hi, seed, e->slots[0].stream, e->i8l.n));
   HIP_TRY(e, hipStreamSynchronize(e->slots[0].stream));
   e->table_set[t] = true;
+  return DRS_OK;
+}
+
+int32_t drs_table_fp8_exponent(drs_handle e, int32_t t, int32_t* k) {
+  int32_t rc = check_handle(e);
+  if (rc) return rc;
+  if (t < 0 || t >= e->T || !k) return fail(e, DRS_ERR_BAD_ARG, "bad table id / null k");
+  if (e->table_dtype != DRS_TABLE_FP8_E4M3)
+    return fail(e, DRS_ERR_UNSUPPORTED, "drs_table_fp8_exponent: the tables are not fp8 (\"table_dtype\" %d)", e->table_dtype);
+  *k = e->fp8_k[(size_t)t];
   return DRS_OK;
 }
 

@@ -316,6 +316,7 @@ static int32_t launch_gather(SetCtx& x) {
   a.T = e->T; a.D = e->D; a.err = reinterpret_cast<int32_t*>(s.d_err);
   a.ts = prof ? s.d_ts : nullptr;
   a.ln_mul = e->i8l.mul; a.ln_shift = e->i8l.shift; a.ln_pad = e->i8l.pad;   // ("table_int8_lines" / "table_int4_lines": zeros for every other layout)
+  a.tab_scale = e->table_dtype == DRS_TABLE_FP8_E4M3 ? e->d_tab_scale : nullptr;   // (read by the fp8 instances alone)
   a.pool = e->sls_pool;      // ("sls_pool": DIN and DIEN refuse 1, so the fused DIN launch never sees it)
   // short bags (W&D / NCF: one lookup per table) take the sequential lane-group-per-bag form (plan_sls); the queries'
   // own bag lengths count here, also when "sls_uniform" 0 keeps them from the kernels

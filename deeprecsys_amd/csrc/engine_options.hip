@@ -101,7 +101,8 @@ int32_t convert_tables(drs_engine* e, int dt, int lines) {
   // forms that depend on the gathered bytes are chosen again (choose_launch_forms): set these options first.
   const int from = e->table_dtype;
   const I8Lines to_l = table_lines(dt, e->D, lines), from_l = e->i8l;
-  const bool rowwise = table_rowwise(dt) || table_rowwise(from);
+  const bool rowwise = table_bytewise(dt) || table_bytewise(from);   // (table by table, into offsets of its own)
+  const bool to8 = dt == DRS_TABLE_FP8_E4M3, from8 = from == DRS_TABLE_FP8_E4M3;
   // the gather kernels address a row in 32-bit counts of 4-byte pieces: rows * S / 4 < 2^32 per int8 table, or
   // ceil(rows / n) * 32 < 2^32 when n rows share a line
   if (dt == DRS_TABLE_INT8_ROWWISE)
@@ -127,7 +128,28 @@ int32_t convert_tables(drs_engine* e, int dt, int lines) {
   hipError_t ar = arena_alloc(e, bytes, &fresh);
   if (ar != hipSuccess) { (void)hipGetLastError(); return fail(e, DRS_ERR_OOM, "table_dtype: arena allocation: %s", hipGetErrorString(ar)); }
   hipError_t r = hipSuccess;
-  if (!rowwise) {    // (fp32 / fp16 / bf16 arenas share their element offsets: one pass over the whole arena)
+  // fp8 e4m3: each table's scale exponent from a device reduction over the source's values (the largest finite |x|), then
+  // the quantizing pass; out of fp8, each code's value decode * 2^-k goes through the new type's own rounding or quantizer
+  std::vector<int32_t> k_new((size_t)e->T, 0);
+  if (to8 || from8) {
+    for (int t = 0; t < e->T && r == hipSuccess; ++t) {
+      const char* src = reinterpret_cast<const char*>(e->tables) + e->tab_off[t] * table_unit_bytes(from);
+      char* dst = reinterpret_cast<char*>(fresh.p) + off[t] * table_unit_bytes(dt);
+      if (from8) {
+        r = launch_convert_rows(src, from, dst, dt, e->rows[t], e->D, nullptr, 0, to_l.n, 0, -1, fp8_pow2(-e->fp8_k[(size_t)t]));
+        continue;
+      }
+      uint32_t bits = 0;
+      r = hipMemset(e->d_absmax, 0, sizeof(uint32_t));
+      if (r == hipSuccess) r = launch_absmax_rows(src, from, e->rows[t], e->D, e->d_absmax, nullptr);
+      if (r == hipSuccess) r = hipMemcpy(&bits, e->d_absmax, sizeof bits, hipMemcpyDeviceToHost);
+      float absmax = 0.0f;
+      memcpy(&absmax, &bits, sizeof absmax);
+      k_new[(size_t)t] = fp8_exponent(absmax);
+      if (r == hipSuccess)
+        r = launch_rows_to_fp8(src, from, reinterpret_cast<uint8_t*>(dst), e->rows[t], e->D, fp8_pow2(k_new[(size_t)t]), nullptr);
+    }
+  } else if (!rowwise) {    // (fp32 / fp16 / bf16 arenas share their element offsets: one pass over the whole arena)
     r = launch_convert_table(e->tables, from, fresh.p, dt, (int64_t)(e->tables_bytes / (size_t)table_unit_bytes(from)), nullptr);
   } else {
     for (int t = 0; t < e->T && r == hipSuccess; ++t)
@@ -151,6 +173,11 @@ int32_t convert_tables(drs_engine* e, int dt, int lines) {
   e->tab_off = off;
   e->table_dtype = dt;
   e->i8l = to_l;
+  e->fp8_k = k_new;
+  if (to8 || from8) {
+    const hipError_t ru = upload_fp8_scales(e);
+    if (ru != hipSuccess) return fail(e, DRS_ERR_HIP, "table_dtype: the tables' scales: %s", hipGetErrorString(ru));
+  }
   choose_launch_forms(e);
   apply_stream_mode(e);
   return DRS_OK;
@@ -160,6 +187,10 @@ int32_t set_table_dtype(drs_engine* e, int64_t value) {
   if (value == e->table_dtype) return DRS_OK;
   if (e->kind == DRS_MODEL_DIN || e->kind == DRS_MODEL_DIEN)
     return fail(e, DRS_ERR_UNSUPPORTED, "table_dtype %lld: DIN and DIEN gather fp32 tables only", (long long)value);
+  // a rowwise arena keeps refusing 4 as it always has (DRS_ERR_BAD_ARG, nothing changes): quantizing quantized rows a second
+  // time is not offered in one step -- 8 -> 0 -> 4 says what is meant
+  if (value == DRS_TABLE_FP8_E4M3 && table_rowwise(e->table_dtype))
+    return fail(e, DRS_ERR_BAD_ARG, "table_dtype 4 on an int8 / int4 rowwise arena (\"table_dtype\" %d): convert to 0, 1 or 2 first", e->table_dtype);
   return convert_tables(e, (int)value, value == DRS_TABLE_INT4_ROWWISE ? e->table_int4_lines : e->table_int8_lines);
 }
 
@@ -289,7 +320,7 @@ const OptDesc kOptions[] = {
 #else
     OPT("table_alloc", 0, 2, nullptr, 0, table_alloc),
 #endif
-    {"table_dtype", 0, 9, [](int64_t v) { return v <= DRS_TABLE_BF16 || v == DRS_TABLE_INT8_ROWWISE || v == DRS_TABLE_INT4_ROWWISE; }, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_dtype; }, nullptr, set_table_dtype},
+    {"table_dtype", 0, 9, [](int64_t v) { return v <= DRS_TABLE_BF16 || v == DRS_TABLE_FP8_E4M3 || v == DRS_TABLE_INT8_ROWWISE || v == DRS_TABLE_INT4_ROWWISE; }, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_dtype; }, nullptr, set_table_dtype},
     // an int8 rowwise arena keeps every row inside one 128-byte line: 128 / S rows to a line where S < 128 does not divide 128
     {"table_int8_lines", 0, 1, nullptr, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_int8_lines; }, nullptr, set_table_int8_lines},
     // ... and an int4 rowwise arena: its rows are 36 bytes at D 64 (3 to a line), 20 at D 32 (6 to a line)

@@ -231,6 +231,7 @@ __global__ __launch_bounds__(64) void sls_kernel(SlsArgs a) {
     for (int m = G; m < 64; m <<= 1) vadd(acc, vshfl_xor(acc, m));
   }
   if (bad) atomicOr(a.err, 1);
+  scale_finish<E>(acc, a, t);
   pool_finish(acc, a.pool, len);   // (behind the loops and the butterfly: the pipeline arms above keep their waitcnt counts)
   if (bag_ok && col_ok && (EXACT || g == 0)) {
     float* o = a.out + (int64_t)vrow * a.ld_out + a.col0 + (int64_t)t * D + col;
@@ -317,6 +318,7 @@ __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int c = c0 + lane + 64 * k;
+      if constexpr (E::scaled) acc[k] = __fmul_rn(acc[k], a.tab_scale[t]);
       if (c < D) o[c] = pool_finish(acc[k], a.pool, end - beg);
     }
   }
@@ -329,7 +331,7 @@ __global__ __launch_bounds__(64) void sls_any_kernel(SlsArgs a) {
 
 int lanes_per_row(int D) { return D <= 8 ? 2 : D <= 16 ? 4 : D <= 32 ? 8 : D <= 64 ? 16 : D <= 128 ? 32 : 64; }
 
-// the launch for tables of element type E (F32 / F16 / BF16 / I8 / I8L / I4 / I4L): the plan's dispatch-log line, then its instance
+// the launch for tables of element type E (F32 / F16 / BF16 / F8 / I8 / I8L / I4 / I4L): the plan's dispatch-log line, then its instance
 template <class E>
 hipError_t launch_sls_e(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hipStream_t s, hipEvent_t stop) {
   // dispatch log: the dtype token ("" for fp32), then "mean" under "sls_pool" 1 (nothing for sum), then "w" on a weighted
@@ -477,6 +479,7 @@ hipError_t launch_sls(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hipS
   switch (p.dtype) {
     case DRS_TABLE_FP16: return launch_sls_e<F16>(a, p, tune, s, stop);
     case DRS_TABLE_BF16: return launch_sls_e<BF16>(a, p, tune, s, stop);
+    case DRS_TABLE_FP8_E4M3: return a.tab_scale ? launch_sls_e<F8>(a, p, tune, s, stop) : hipErrorInvalidValue;
     case DRS_TABLE_INT8_ROWWISE: return a.ln_pad ? launch_sls_e<I8L>(a, p, tune, s, stop) : launch_sls_e<I8>(a, p, tune, s, stop);
     case DRS_TABLE_INT4_ROWWISE: return a.ln_pad ? launch_sls_e<I4L>(a, p, tune, s, stop) : launch_sls_e<I4>(a, p, tune, s, stop);
     default: return launch_sls_e<F32>(a, p, tune, s, stop);
@@ -651,7 +654,7 @@ __global__ __launch_bounds__(256) void relayout_rows_kernel(I8Rows src, I8Rows d
 // any even D; the row is read twice (the second time from the cache).  Rows holding inf or NaN, or values beyond fp16's
 // range, are outside the contract: the clamp keeps every code a nibble.
 template <class Src>
-__global__ __launch_bounds__(256) void pack4_rows_kernel(Src src, I4Rows dst, int64_t rows, int D) {
+__device__ __forceinline__ void pack4_rows(Src src, I4Rows dst, int64_t rows, int D) {
   const int lane = threadIdx.x & 63;
   const int P = I4::padded(D);
   for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
@@ -687,6 +690,10 @@ __global__ __launch_bounds__(256) void pack4_rows_kernel(Src src, I4Rows dst, in
     for (int c = lane * 4, z = dst.tail(r, D); c < z; c += 64 * 4) *reinterpret_cast<uint32_t*>(row + P + 4 + c) = 0u;
   }
 }
+template <class Src>
+__global__ __launch_bounds__(256) void pack4_rows_kernel(Src src, I4Rows dst, int64_t rows, int D) {
+  pack4_rows(src, dst, rows, D);
+}
 // int4 rows -> elements of type dt: each row's value fmaf(scale, q, 0.0f + bias) (the one-row bag), rounded to dt
 __global__ __launch_bounds__(256) void unpack4_rows_kernel(SrcI4 src, void* dst, int dt, int64_t rows, int D) {
   const int lane = threadIdx.x & 63;
@@ -708,6 +715,79 @@ static unsigned row_grid(int64_t rows) {
   const int64_t want = (rows + 3) / 4;
   return (unsigned)(want < 16384 ? want : 16384);
 }
+
+// ---------------------------------------------------------------------------
+// "table_dtype" 4, fp8 e4m3 tables (layout: struct F8).  e4m3_rne: an fp32 value as its OCP e4m3 code, torch's
+// float8_e4m3fn conversion in integer arithmetic, bit for bit: round to nearest even, the subnormal codes (multiples of
+// 2^-9 below 2^-6) through the add of 2^14 whose ulp they are, 0x7F (NaN) with the sign bit for NaN, +-inf and everything
+// that rounds beyond 448 -- which no finite element does after the table's scale.
+__device__ __forceinline__ uint8_t e4m3_rne(float x) {
+  uint32_t b = __float_as_uint(x);
+  const uint32_t sign = b & 0x80000000u;
+  b ^= sign;
+  uint32_t q;
+  if (b >= 0x43F00000u) {                           // >= 480, +-inf, NaN
+    q = 0x7Fu;
+  } else if (b < (121u << 23)) {                    // below 2^-6
+    q = __float_as_uint(__fadd_rn(__uint_as_float(b), __uint_as_float(141u << 23))) - (141u << 23);
+  } else {
+    const uint32_t odd = (b >> 20) & 1u;
+    b += ((uint32_t)(7 - 127) << 23) + 0x7FFFFu + odd;
+    q = b >> 20;
+  }
+  return (uint8_t)(q | (sign >> 24));
+}
+struct SrcF8 {         // each fp8 code's value, decode(code) * 2^-k of its table
+  const uint8_t* codes;
+  float scale;
+  __device__ __forceinline__ float operator()(int64_t r, int D, int c) const { return __fmul_rn(F8::up1(codes[r * D + c]), scale); }
+};
+// the largest |x| over the source's finite values, as its bits: one atomicMax per wave into *out (zeroed by the caller)
+template <class Src>
+__global__ __launch_bounds__(256) void absmax_rows_kernel(Src src, int64_t rows, int D, uint32_t* out) {
+  const int64_t n = rows * D;
+  uint32_t m = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / D;
+    const uint32_t b = __float_as_uint(src(r, D, (int)(i - r * D))) & 0x7fffffffu;
+    m = b < 0x7f800000u && b > m ? b : m;
+  }
+#pragma unroll
+  for (int k = 1; k < 64; k <<= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor((int)m, k);
+    m = o > m ? o : m;
+  }
+  if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
+}
+// rows x D source values -> codes: dst[r * D + c] = e4m3_rne(x * mul), mul = 2^k
+template <class Src>
+__global__ __launch_bounds__(256) void to_fp8_rows_kernel(Src src, uint8_t* dst, int64_t rows, int D, float mul) {
+  const int64_t n = rows * D;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / D;
+    dst[i] = e4m3_rne(__fmul_rn(src(r, D, (int)(i - r * D)), mul));
+  }
+}
+// fp8 rows -> int8 / int4 rowwise rows ("table_dtype" 4 -> 8, 4 -> 9): each code's value, through that type's quantizer
+__global__ __launch_bounds__(256) void fp8_to_rows8_kernel(SrcF8 src, I8Rows dst, int64_t rows, int D) {
+  quantize_rows8(src, dst, rows, D);
+}
+__global__ __launch_bounds__(256) void fp8_to_rows4_kernel(SrcF8 src, I4Rows dst, int64_t rows, int D) {
+  pack4_rows(src, dst, rows, D);
+}
+// fp8 rows -> elements of type dt: each code's value, rounded to dt
+__global__ __launch_bounds__(256) void from_fp8_rows_kernel(SrcF8 src, void* dst, int dt, int64_t rows, int D) {
+  const int64_t n = rows * D;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / D;
+    store_elem(dst, dt, i, src(r, D, (int)(i - r * D)));
+  }
+}
+static unsigned elem_grid(int64_t n) {
+  const int64_t want = (n + 255) / 256;
+  return (unsigned)(want < 16384 ? want : 16384);
+}
+static bool plain_dtype(int dtype) { return dtype == DRS_TABLE_FP32 || dtype == DRS_TABLE_FP16 || dtype == DRS_TABLE_BF16; }
 
 #ifdef DRS_LAB   // probes of tools/placement_lab.py (libdrs_hip_lab.so: make lab-lib); not in the product library
 // ---------------------------------------------------------------------------
@@ -861,10 +941,43 @@ hipError_t launch_fill_uniform_dtype(void* W, int dtype, int64_t rows, int D, in
   return hipGetLastError();
 }
 
+hipError_t launch_absmax_rows(const void* src, int src_dtype, int64_t rows, int D, uint32_t* d_bits, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  if (!plain_dtype(src_dtype)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(absmax_rows_kernel<SrcElems>, dim3(elem_grid(rows * D)), dim3(256), 0, s, SrcElems{src, src_dtype}, rows, D, d_bits);
+  return hipGetLastError();
+}
+
+hipError_t launch_rows_to_fp8(const void* src, int src_dtype, uint8_t* dst, int64_t rows, int D, float mul, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  if (!plain_dtype(src_dtype)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(to_fp8_rows_kernel<SrcElems>, dim3(elem_grid(rows * D)), dim3(256), 0, s, SrcElems{src, src_dtype}, dst, rows, D, mul);
+  return hipGetLastError();
+}
+
+hipError_t launch_fill_uniform_fp8(uint8_t* dst, int64_t rows, int D, int32_t t, float lo, float hi, uint64_t seed, float mul, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(to_fp8_rows_kernel<SrcFill>, dim3(elem_grid(rows * D)), dim3(256), 0, s, SrcFill{t, lo, hi - lo, seed}, dst, rows, D, mul);
+  return hipGetLastError();
+}
+
 hipError_t launch_convert_rows(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t rows, int D, hipStream_t s,
-                               int32_t n_src, int32_t n_dst, int64_t first, int64_t total) {
+                               int32_t n_src, int32_t n_dst, int64_t first, int64_t total, float src_scale) {
   if (rows <= 0) return hipSuccess;
   if (total < 0) total = first + rows;
+  if (src_dtype == DRS_TABLE_FP8_E4M3) {   // (whole tables only: first == 0)
+    const SrcF8 from8{static_cast<const uint8_t*>(src), src_scale};
+    const dim3 grid(row_grid(rows)), block(256);
+    if (first != 0 || dst_dtype == DRS_TABLE_FP8_E4M3 || (dst_dtype == DRS_TABLE_INT4_ROWWISE && (D & 1))) return hipErrorInvalidValue;
+    if (dst_dtype == DRS_TABLE_INT8_ROWWISE)
+      hipLaunchKernelGGL(fp8_to_rows8_kernel, grid, block, 0, s, from8, I8Rows{static_cast<uint8_t*>(dst), 0, total, n_dst}, rows, D);
+    else if (dst_dtype == DRS_TABLE_INT4_ROWWISE)
+      hipLaunchKernelGGL(fp8_to_rows4_kernel, grid, block, 0, s, from8, I4Rows{static_cast<uint8_t*>(dst), 0, total, n_dst}, rows, D);
+    else
+      hipLaunchKernelGGL(from_fp8_rows_kernel, dim3(elem_grid(rows * D)), block, 0, s, from8, dst, dst_dtype, rows, D);
+    return hipGetLastError();
+  }
+  if (dst_dtype == DRS_TABLE_FP8_E4M3) return hipErrorInvalidValue;   // (launch_rows_to_fp8: it needs the table's scale first)
   const I8Rows from{static_cast<uint8_t*>(const_cast<void*>(src)), first, total, n_src}, to{static_cast<uint8_t*>(dst), first, total, n_dst};
   const bool si8 = src_dtype == DRS_TABLE_INT8_ROWWISE, di8 = dst_dtype == DRS_TABLE_INT8_ROWWISE;
   const bool si4 = src_dtype == DRS_TABLE_INT4_ROWWISE, di4 = dst_dtype == DRS_TABLE_INT4_ROWWISE;

@@ -60,7 +60,7 @@ __device__ __forceinline__ uint32_t ld_nt(const uint32_t* p) { return __builtin_
 __device__ __forceinline__ uint16_t ld_nt(const uint16_t* p) { return __builtin_nontemporal_load(p); }
 
 // Row-element policies ("table_dtype"): what a table element is, the PIECE a lane loads -- 4 elements, 16 B of fp32,
-// 8 B of fp16 / bf16, 4 B of int8 codes or 2 B of int4 codes, one load instruction -- and how a piece of a row is added
+// 8 B of fp16 / bf16, 4 B of fp8 or int8 codes or 2 B of int4 codes, one load instruction -- and how a piece of a row is added
 // into the fp32 accumulator.  Every fp16 / bf16 value is an fp32 value, so a half form sums exactly what its fp32 twin sums on the
 // upcast table, in the same order: the same bits.  tag: the dispatch log's dtype token (none for fp32).
 //   sb: what a lane loads per row besides its piece (int8 rowwise: the row's fp32 scale and bias; int4 rowwise: one dword,
@@ -69,12 +69,14 @@ __device__ __forceinline__ uint16_t ld_nt(const uint16_t* p) { return __builtin_
 //   row_piece(r, pr, ln): where row r starts in its table, in pieces (pr: the row stride) -- r * pr, but for I8L and I4L,
 //   whose launch constants `ln` a kernel reads with DRS_ROW_LINES (nothing for every other policy)
 //   add(acc, keep, piece, sb): acc += the row's values (keep == false: the row contributes +0)
+//   scaled: true for F8 alone -- a bag's FINISHED sum is multiplied by its table's SlsArgs::tab_scale entry just before
+//   pool_finish (scale_finish below); with it false nothing that names a scale exists
 //   weighted: false for every policy itself; Wgt<E> (below) is E with weighted == true, the element type of a WEIGHTED
 //   instance of the one-lookup, flat and flatc kernels -- their unweighted instances keep their symbols that way
 struct NoSb {};
 template <class Self>
 struct PlainRow {
-  static constexpr bool rowwise = false, lines = false, weighted = false;
+  static constexpr bool rowwise = false, lines = false, weighted = false, scaled = false;
   using sb = NoSb;
   using ln_t = NoSb;
   __host__ __device__ static constexpr uint32_t pieces_per_row(int D) { return (uint32_t)D >> 2; }
@@ -120,6 +122,24 @@ struct BF16 : PlainRow<BF16> {
                        __uint_as_float(p.y & 0xffff0000u));
   }
 };
+// fp8 e4m3 ("table_dtype" 4): OCP e4m3 codes (torch's float8_e4m3fn; gfx950's conversions are the OCP ones), a row is D
+// bytes and a piece one aligned dword, widened by two v_cvt_pk_f32_fp8.  Table t stores e4m3_rne(x * 2^k_t): the kernels
+// sum the decoded codes as F16 sums upcast halves and multiply a bag's finished accumulator by 2^-k_t (scale_finish).
+// A power of two commutes with every fp32 add, fma and division short of a subnormal or overflowing intermediate --
+// none with |k| <= 64 and codes that are multiples of 2^-9 up to 448 -- so every form serves the bits its fp32 twin
+// serves on the decoded table decode(code) * 2^-k_t, in the same order.  a.tab_off counts bytes.
+typedef float f2v_cvt __attribute__((ext_vector_type(2)));
+struct F8 : PlainRow<F8> {
+  static constexpr bool scaled = true;
+  using elem = uint8_t;
+  using piece = uint32_t;
+  static constexpr const char* tag = "f8";
+  __device__ static __forceinline__ float up1(uint8_t x) { return __builtin_amdgcn_cvt_f32_fp8((uint32_t)x, 0); }
+  __device__ static __forceinline__ float4 up(uint32_t p) {
+    const f2v_cvt lo = __builtin_amdgcn_cvt_pk_f32_fp8(p, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(p, true);
+    return make_float4(lo.x, lo.y, hi.x, hi.y);
+  }
+};
 // 8-bit rowwise ("table_dtype" 8, Caffe2's Fused8BitRowwise): a row is D uint8 codes, zero padding to round_up(D, 8)
 // bytes, then the fp32 scale and the fp32 bias (S = round_up(D, 8) + 8 bytes, every row 8-byte aligned).  a.tab_off
 // counts bytes.  A piece is one dword of codes (v_cvt_f32_ubyte0..3); the lanes of a row group load the same 8 bytes of
@@ -127,7 +147,7 @@ struct BF16 : PlainRow<BF16> {
 // sequential form is bit-identical to embedding_bag_byte_rowwise_offsets.  A masked row adds with scale = bias = 0:
 // acc + 0 + 0 * q == acc (acc is never -0: every step is an fma onto a sum with +0).
 struct I8 {
-  static constexpr bool rowwise = true, lines = false, weighted = false;
+  static constexpr bool rowwise = true, lines = false, weighted = false, scaled = false;
   using elem = uint8_t;
   using piece = uint32_t;
   using sb = float2;
@@ -192,7 +212,7 @@ struct I8L : I8 {
 // acc = fmaf(scale, q, acc + bias): the sequential form is bit-identical to embedding_bag_4bit_rowwise_offsets, and every
 // form sums the same values in the order its int8 twin does.
 struct I4 {
-  static constexpr bool rowwise = true, lines = false, weighted = false;
+  static constexpr bool rowwise = true, lines = false, weighted = false, scaled = false;
   using elem = uint8_t;
   using piece = uint16_t;
   using sb = uint32_t;
@@ -248,6 +268,14 @@ template <class E>
 struct Wgt : E {
   static constexpr bool weighted = true;
 };
+// E::scaled (fp8): the finished sum of table t's bag, out of the code domain -- times the table's 2^-k, before pool_finish
+template <class E>
+__device__ __forceinline__ void scale_finish(float4& acc, const SlsArgs& a, int t) {
+  if constexpr (E::scaled) {
+    const float s = a.tab_scale[t];
+    acc = make_float4(__fmul_rn(acc.x, s), __fmul_rn(acc.y, s), __fmul_rn(acc.z, s), __fmul_rn(acc.w, s));
+  }
+}
 #define DRS_ROW_LINES(E, a, ln) \
   typename E::ln_t ln{};        \
   if constexpr (E::lines) ln = LineMap{(a).ln_mul, (a).ln_shift, (a).ln_pad};
@@ -341,6 +369,7 @@ __global__ __launch_bounds__(64) void sls_one_kernel(SlsArgs a, int tiles) {
         float4 o = vzero4();                                  // 0.0f + row: the one-row bag's value
         if constexpr (WGT) E::addw(o, kp[j] != 0, wj[j], v[j], sb[j]);
         else E::add(o, kp[j] != 0, v[j], sb[j]);
+        scale_finish<E>(o, a, t);
         pool_finish(o, a.pool, 1);                            // a one-row bag's mean: x / 1.0f == x, the same bits
         *reinterpret_cast<float4*>(out + (int64_t)vr[j] * a.ld_out) = o;
       }
@@ -512,7 +541,10 @@ __global__ __launch_bounds__(64) void sls_flat_kernel(SlsArgs a, int L, int xcd_
 
   if (bad) atomicOr(a.err, 1);
 #pragma unroll
-  for (int k = 0; k < BPW; ++k) pool_finish(acc[k], a.pool, L);
+  for (int k = 0; k < BPW; ++k) {
+    scale_finish<E>(acc[k], a, t0 + k);
+    pool_finish(acc[k], a.pool, L);
+  }
   // every group holds every sum after the butterfly; group 0 stores them, one 128..512-B row per
   // bag.  (Letting group k store bag k needs acc[g]: the optimiser turns that select chain into a
   // dynamically indexed array, i.e. SCRATCH memory -- which capped the BPW > 1 variants at half
@@ -660,7 +692,10 @@ __global__ __launch_bounds__(64) void sls_flatc_kernel(SlsArgs a, int L) {
 
   if (bad) atomicOr(a.err, 1);
 #pragma unroll
-  for (int k = 0; k < BPW; ++k) pool_finish(acc[k], a.pool, L);
+  for (int k = 0; k < BPW; ++k) {
+    scale_finish<E>(acc[k], a, t0 + k);
+    pool_finish(acc[k], a.pool, L);
+  }
   // lane group k stores bag k (every group holds every sum after the butterfly)
   if (col_ok && g < BPW) {
     float4 o4 = acc[0];

@@ -44,6 +44,7 @@ hipError_t launch_sls_wflat(const SlsArgs& a, const SlsPlan& p, hipStream_t s, h
   switch (p.dtype) {
     case DRS_TABLE_FP16: return launch_wflat_e<F16>(a, p, s, stop);
     case DRS_TABLE_BF16: return launch_wflat_e<BF16>(a, p, s, stop);
+    case DRS_TABLE_FP8_E4M3: return a.tab_scale ? launch_wflat_e<F8>(a, p, s, stop) : hipErrorInvalidValue;
     case DRS_TABLE_INT8_ROWWISE: return a.ln_pad ? launch_wflat_e<I8L>(a, p, s, stop) : launch_wflat_e<I8>(a, p, s, stop);
     case DRS_TABLE_INT4_ROWWISE: return a.ln_pad ? launch_wflat_e<I4L>(a, p, s, stop) : launch_wflat_e<I4>(a, p, s, stop);
     default: return launch_wflat_e<F32>(a, p, s, stop);

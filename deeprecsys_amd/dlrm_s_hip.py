@@ -36,7 +36,7 @@ def _ints(s):
 
 
 _TABLE_DTYPES = {"fp32": N.TABLE_FP32, "fp16": N.TABLE_FP16, "bf16": N.TABLE_BF16, "int8_rowwise": N.TABLE_INT8_ROWWISE,
-                 "int4_rowwise": N.TABLE_INT4_ROWWISE}
+                 "int4_rowwise": N.TABLE_INT4_ROWWISE, "fp8_e4m3": N.TABLE_FP8_E4M3}
 
 
 def _table_dtype(args):

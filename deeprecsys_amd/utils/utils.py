@@ -69,7 +69,7 @@ EXTRA_FLAGS = [
     ("accel_backend", _S, "hip"),     # "hip": real forward on the GPU | "sim": latency table
     ("accel_device_offset", _I, 0),   # first GPU ordinal used by the accel engines
     ("accel_table_init", _S, "numpy"),  # "numpy": reference RNG stream | "device": counter-based fill
-    ("accel_table_dtype", _S, "fp32"),  # element type the accel engines store the tables in: fp32 | fp16 | bf16 | int8_rowwise | int4_rowwise (sums stay fp32)
+    ("accel_table_dtype", _S, "fp32"),  # element type the accel engines store the tables in: fp32 | fp16 | bf16 | int8_rowwise | int4_rowwise | fp8_e4m3 (sums stay fp32; fp8_e4m3: OCP e4m3 codes under one power-of-two scale per table, about 2 % rms element error)
     ("accel_table_int8_lines", _I, 0),  # 1 with --accel_table_dtype int8_rowwise: no int8 row crosses a 128-byte line, rows packed 128 // S to a line (engine option "table_int8_lines"; same results)
     ("accel_sls_pool", _S, "sum"),    # how the accel engines pool an embedding bag: sum (SparseLengthsSum) | mean (SparseLengthsMean, torch's EmbeddingBag(mode="mean"): the fp32 sum / the bag's length; engine option "sls_pool")
     ("accel_table_int4_lines", _I, 0),  # 1 with --accel_table_dtype int4_rowwise: no int4 row crosses a 128-byte line, rows packed 128 // S to a line (engine option "table_int4_lines"; same results)
@@ -97,7 +97,7 @@ def debugPrint(args, system_tag, message):
 
 
 # EXTRA_FLAGS that take one of a few words
-FLAG_CHOICES = {"accel_table_dtype": ("fp32", "fp16", "bf16", "int8_rowwise", "int4_rowwise"), "accel_mlp_dtype": ("fp32", "bf16"),
+FLAG_CHOICES = {"accel_table_dtype": ("fp32", "fp16", "bf16", "int8_rowwise", "int4_rowwise", "fp8_e4m3"), "accel_mlp_dtype": ("fp32", "bf16"),
                 "accel_mlp_bf16_fuse": (0, 1), "accel_table_int8_lines": (0, 1), "accel_table_int4_lines": (0, 1), "accel_sls_pool": ("sum", "mean"),
                 "accel_sls_weights": ("none", "uniform"), "accel_sls_weighted_flat": (0, 1)}
 

@@ -82,8 +82,12 @@ enum { DRS_INTERACT_DOT = 0, DRS_INTERACT_CAT = 1 };
  * fp32 scale and an fp32 bias; a row's value is fmaf(scale, q, 0.0f + bias).
  * DRS_TABLE_INT4_ROWWISE: FBGEMM's Fused4BitRowwise, torch's embedding_bag_4bit_prepack -- a row is D / 2 bytes of 4-bit
  * codes (column 2j the low nibble of byte j), zero padding to a multiple of 4 bytes, an fp16 scale and an fp16 bias; the
- * same value formula; D must be even */
-enum { DRS_TABLE_FP32 = 0, DRS_TABLE_FP16 = 1, DRS_TABLE_BF16 = 2, DRS_TABLE_INT8_ROWWISE = 8, DRS_TABLE_INT4_ROWWISE = 9 };
+ * same value formula; D must be even
+ * DRS_TABLE_FP8_E4M3: OCP fp8 e4m3 (torch's float8_e4m3fn, never an fnuz type) -- a row is D bytes, one code per element,
+ * no per-row header; table t carries one power-of-two scale: stored code = e4m3_rne(x * 2^k_t), a code's value is
+ * decode(code) * 2^-k_t, k_t the largest integer with absmax_t * 2^k_t <= 448 (clamped to [-64, 64]; 0 for absmax_t 0;
+ * absmax_t over the table's finite elements).  drs_fp8.h declares the entry point that reads k_t back */
+enum { DRS_TABLE_FP32 = 0, DRS_TABLE_FP16 = 1, DRS_TABLE_BF16 = 2, DRS_TABLE_FP8_E4M3 = 4, DRS_TABLE_INT8_ROWWISE = 8, DRS_TABLE_INT4_ROWWISE = 9 };
 
 /* arithmetic of the wide FC layers (option "mlp_dtype").  DRS_MLP_BF16: a layer of the bottom, top, final or task MLP
  * with K >= 64 and N >= 64 rounds its input and its weights to bf16 (nearest even, NaN stays NaN) and accumulates the
@@ -314,11 +318,15 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  *   streams, host "shared_stream" 0|1|2   "mlp_streams" 1..8   "host_threads" -1..64
  *                 "zero_copy_inputs" 1|2|3   "out_dma" bytes   "dispatch_log" 0|1
  *   table arena   "table_placement" -1|-2|k   "table_alloc" 0|1|2   "table_spacer" bytes
- *                 "table_dtype" 0|1|2|8|9 (DRS_TABLE_FP32 | DRS_TABLE_FP16 | DRS_TABLE_BF16 | DRS_TABLE_INT8_ROWWISE |
- *                 DRS_TABLE_INT4_ROWWISE: converts the arena in use; DLRM, W&D, MT-WnD and NCF only.  8: FBGEMM's
+ *                 "table_dtype" 0|1|2|4|8|9 (DRS_TABLE_FP32 | DRS_TABLE_FP16 | DRS_TABLE_BF16 | DRS_TABLE_FP8_E4M3 |
+ *                 DRS_TABLE_INT8_ROWWISE | DRS_TABLE_INT4_ROWWISE: converts the arena in use; DLRM, W&D, MT-WnD and NCF only.  8: FBGEMM's
  *                 embedding_bag_byte_prepack quantization, and with sls_exact 1 the pooled sums of
  *                 embedding_bag_byte_rowwise_offsets, bit for bit.  9: embedding_bag_4bit_prepack's quantization and
- *                 embedding_bag_4bit_rowwise_offsets' sums likewise; even D only, DRS_ERR_UNSUPPORTED otherwise)
+ *                 embedding_bag_4bit_rowwise_offsets' sums likewise; even D only, DRS_ERR_UNSUPPORTED otherwise.
+ *                 4: a row is D bytes of OCP fp8 e4m3 codes under one power-of-two scale per table (about 2 % rms
+ *                 relative element error: an explicit accuracy cost); every form sums the bits its fp32 twin sums on
+ *                 the decoded table.  drs_fill_table_uniform takes the scale from max(|lo|, |hi|), not from the samples.
+ *                 From an int8 / int4 rowwise arena 4 stays DRS_ERR_BAD_ARG: convert to 0, 1 or 2 first)
  *                 "table_int8_lines" 0|1 (1 with "table_dtype" 8: no int8 row crosses a 128-byte line -- 128 / S rows of
  *                 S = round_up(D, 8) + 8 bytes share a line where S < 128 does not divide 128; set before or after
  *                 "table_dtype", the same arena; same results)
@@ -396,8 +404,10 @@ const char* drs_comm_last_error(void);
 /* ---- entry points of the HIP library beyond the symbol set above ------------------
  * The declarations above are the ABI that every implementation restates (the CPU restatement under oracle/ among
  * them) and that DRS_ABI_VERSION counts.  drs_weights.h adds the per-sample-weight entry points, which libdrs_hip.so
- * alone exports; nothing above changed for them, so the version stays what it is.                                */
+ * alone exports; nothing above changed for them, so the version stays what it is.  drs_fp8.h likewise adds the
+ * read-back of an fp8 table's scale exponent ("table_dtype" 4).                                                    */
 #include "drs_weights.h"
+#include "drs_fp8.h"
 
 #ifdef __cplusplus
 }
