@@ -536,7 +536,10 @@ __global__ void fill_uniform_round_kernel(void* W, int dt, int64_t n, int32_t t,
 // "table_dtype" 8, 8-bit rowwise tables (layout: struct I8).  Quantizing a row, FBGEMM's embedding_bag_byte_prepack in
 // IEEE fp32 without contraction: mn = min, mx = max, range = mx - mn, scale = range / 255, bias = mn,
 // inv = 255 / (range + 1e-8), q = rint((x - mn) * inv).  One wave per row, any D; the row is read twice (the second
-// time from the cache).  Rows holding inf or NaN are outside the contract: the clamp keeps every code a byte.
+// time from the cache).  Rows holding inf or NaN are outside the contract: the clamp keeps every code a byte.  A finite
+// row with mx - mn = inf (+3e38 beside -3e38) is inside it: scale = inf, inv = 0 and every code 0 (fminf(fmaxf(NaN, 0), 255)
+// is 0 for the element whose x - mn is inf) -- embedding_bag_byte_prepack's bytes; the row decodes to inf * 0 = NaN and
+// the gather keeps that NaN to the bags that name it (I8::addw).
 struct SrcElems {      // row r of a table of element type dt at src (D elements per row)
   const void* src;
   int dt;
@@ -652,7 +655,9 @@ __global__ __launch_bounds__(256) void relayout_rows_kernel(I8Rows src, I8Rows d
 // fp32 without contraction: bias = fp16(min), scale = fp16((max - (float)bias) / 15), a zero scale becomes 1,
 // inv = 1 / (float)scale (infinite: scale = inv = 1), q = clamp(rint((x - (float)bias) * inv), 0, 15).  One wave per row,
 // any even D; the row is read twice (the second time from the cache).  Rows holding inf or NaN, or values beyond fp16's
-// range, are outside the contract: the clamp keeps every code a nibble.
+// range, are outside the contract: the clamp keeps every code a nibble.  A finite row with (max - bias) / 15 >= 65520 --
+// one element of 1e6 -- takes the scale +inf, inv = 0 and every code 0, embedding_bag_4bit_prepack's bytes: it decodes to
+// inf * 0 = NaN in every column, and the gather keeps that NaN to the bags that name it (I4::addw).
 template <class Src>
 __device__ __forceinline__ void pack4_rows(Src src, I4Rows dst, int64_t rows, int D) {
   const int lane = threadIdx.x & 63;

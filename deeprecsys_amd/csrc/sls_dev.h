@@ -145,7 +145,11 @@ struct F8 : PlainRow<F8> {
 // counts bytes.  A piece is one dword of codes (v_cvt_f32_ubyte0..3); the lanes of a row group load the same 8 bytes of
 // scale and bias beside it.  A row adds acc = fmaf(scale, q, acc + bias) per column: FBGEMM's and Caffe2's order, so the
 // sequential form is bit-identical to embedding_bag_byte_rowwise_offsets.  A masked row adds with scale = bias = 0:
-// acc + 0 + 0 * q == acc (acc is never -0: every step is an fma onto a sum with +0).
+// acc + 0 + 0 * q == acc (acc is never -0: every step is an fma onto a sum with +0) -- the zeros are SELECTED, never the
+// product of a zero weight and the row's header.  A finite fp32 row whose range overflows its header (max - min above
+// fp32's largest value here, (max - bias) / 15 above fp16's for int4) is stored with the scale +inf and the codes 0, as
+// torch's prepack operators store it, and decodes to inf * 0 = NaN in every column: that NaN reaches the bags that name
+// the row, as in torch's rowwise bags, and no other.
 struct I8 {
   static constexpr bool rowwise = true, lines = false, weighted = false, scaled = false;
   using elem = uint8_t;
@@ -175,15 +179,16 @@ struct I8 {
   }
   // the weighted step (FBGEMM's and torch's embedding_bag_byte_rowwise_offsets with per_sample_weights): the row's scale
   // and bias are multiplied by its weight first -- two fp32 products -- and go through row1 as they are.  w == 1.0f
-  // is add; a row that must not count (keep == false) takes w = 0.0f and adds acc + 0 + 0 * q == acc: exact for the finite
-  // scale and bias a rowwise row has by contract.
+  // is add.  A row that must not count (keep == false) is dropped AFTER the products, as add drops it: s = b = +0 and
+  // acc + 0 + 0 * q == acc.  Masking its weight instead (w = 0) leaves s = 0 * scale, which is NaN for the scale +inf
+  // of a row whose header overflowed -- row 0, which every empty bag reads, above all.
   // (The two products are written under contract(off): __fmul_rn is a plain, contractable `x * y` to this compiler, which
   // folds w * bias into row1's acc + b as one fma in some instances -- the weighted flat forms at 20 loads per lane --
   // and then rounds once where the operator rounds twice.  The pragma does not reach into an inlined callee.)
   __device__ static __forceinline__ void addw(float4& acc, bool keep, float w, uint32_t p, float2 sb) {
 #pragma clang fp contract(off)
-    w = keep ? w : 0.0f;
-    const float s = w * sb.x, b = w * sb.y;
+    const float ws = w * sb.x, wb = w * sb.y;
+    const float s = keep ? ws : 0.f, b = keep ? wb : 0.f;
     acc.x = row1(s, b, (float)(p & 0xffu), acc.x);
     acc.y = row1(s, b, (float)((p >> 8) & 0xffu), acc.y);
     acc.z = row1(s, b, (float)((p >> 16) & 0xffu), acc.z);
@@ -242,10 +247,10 @@ struct I4 {
   }
   // the weighted step: I8's, on the widened fp16 scale and bias (embedding_bag_4bit_rowwise_offsets with per_sample_weights)
   __device__ static __forceinline__ void addw(float4& acc, bool keep, float w, uint16_t p16, uint32_t w32) {
-#pragma clang fp contract(off)   // (as I8::addw: the two products stay products)
-    w = keep ? w : 0.0f;
+#pragma clang fp contract(off)   // (as I8::addw: the two products stay products, and the row is dropped after them)
     const float2 f = up_sb(w32);
-    const float s = w * f.x, b = w * f.y;
+    const float ws = w * f.x, wb = w * f.y;
+    const float s = keep ? ws : 0.f, b = keep ? wb : 0.f;
     const uint32_t p = p16;
     acc.x = row1(s, b, (float)(p & 15u), acc.x);
     acc.y = row1(s, b, (float)((p >> 4) & 15u), acc.y);

@@ -61,12 +61,12 @@ def _check_pooled(where, form, got, clean, cls_ref, seq, hot, empty):
     assert not np.any(_bits(got)[empty]), (where, "an empty bag is not +0.0")
 
 
-@pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("n", range(len(SHAPES)), ids=[nf_shape_id(s) for s in SHAPES])
-def test_non_finite_rows_reach_the_bags_that_name_them_and_no_other(kind, n):
+def run_poison_case(c, n, kind, tag, after_load=None):
+    """every run mode, query size and launch set of SHAPES[n] on two engines of stored type `kind` (tests/test_sls_weights.py's
+    _engine) that hold c["poisoned"] and c["clean"]; c: poison_case's layout and references, tag: the kind's dispatch token;
+    after_load(poisoned engine, clean engine): a check of the loaded tables (tests/test_sls_nonfinite_quant.py)"""
     shape = SHAPES[n]
     D, T, L, opts = shape
-    c = poison_case(shape, kind)
     fixed = isinstance(L, int)
     Lmax = max(int(ln.max()) for b in range(N_BATCHES) for ln in c["lens"][b])
     rng = np.random.RandomState(n)
@@ -78,6 +78,8 @@ def test_non_finite_rows_reach_the_bags_that_name_them_and_no_other(kind, n):
     try:
         _load(po, 11, c["poisoned"], D, T)
         _load(cl, 11, c["clean"], D, T)
+        if after_load:
+            after_load(po, cl)
         for eng in engines:
             eng.set_option("dispatch_log", 1)
             for k, v in sorted(opts.items()):
@@ -102,7 +104,7 @@ def test_non_finite_rows_reach_the_bags_that_name_them_and_no_other(kind, n):
                         outs.append(eng.forward(b, bs))                        # (raises on any error: poison is none)
                         Rs.append(eng.fetch_interaction(bs))
                         tok = _tokens(eng)
-                        assert len(tok) == 1 and tok[0].startswith(token_of(form, nt, TAG[kind], m)), (where, tok, form)
+                        assert len(tok) == 1 and tok[0].startswith(token_of(form, nt, tag, m)), (where, tok, form)
                     bb = batch(b)
                     hot = named_columns(c["named"][bb], D, bs)
                     _check_pooled(where, form, Rs[0][:, D:], Rs[1][:, D:], c["cls"][m][bb][:bs], c["seq"][m][bb][:bs], hot, empty[bb][:bs])
@@ -116,7 +118,7 @@ def test_non_finite_rows_reach_the_bags_that_name_them_and_no_other(kind, n):
             got_p, got_c = _run_set(po, JOBS12), _run_set(cl, JOBS12)
             for eng in engines:
                 tok = _tokens(eng, 1)
-                assert len(tok) == 1 and tok[0].startswith(token_of(form, nt, TAG[kind], mode)), (kind, n, mode, tok, form)
+                assert len(tok) == 1 and tok[0].startswith(token_of(form, nt, tag, mode)), (kind, n, mode, tok, form)
             for (b, q), Rp, Rc in zip(JOBS12, got_p, got_c):
                 if not q:
                     continue
@@ -147,6 +149,12 @@ def test_non_finite_rows_reach_the_bags_that_name_them_and_no_other(kind, n):
     finally:
         for eng in engines:
             eng.close()
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("n", range(len(SHAPES)), ids=[nf_shape_id(s) for s in SHAPES])
+def test_non_finite_rows_reach_the_bags_that_name_them_and_no_other(kind, n):
+    run_poison_case(poison_case(SHAPES[n], kind), n, kind, TAG[kind])
 
 
 # ------------------------------------------------------------------------------------------------------------------------

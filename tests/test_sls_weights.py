@@ -27,6 +27,8 @@ pytestmark = pytest.mark.gpu
 TYPES = {"fp32": (N.TABLE_FP32, None), "fp16": (N.TABLE_FP16, None), "bf16": (N.TABLE_BF16, None),
          "int8": (N.TABLE_INT8_ROWWISE, None), "int8_lines": (N.TABLE_INT8_ROWWISE, "table_int8_lines"),
          "int4": (N.TABLE_INT4_ROWWISE, None), "int4_lines": (N.TABLE_INT4_ROWWISE, "table_int4_lines")}
+# ... and the types _engine builds besides: the weighted cases of fp8 tables are tests/test_fp8_tables.py's
+ENGINE_TYPES = dict(TYPES, fp8=(N.TABLE_FP8_E4M3, None))
 T, B = 3, 48
 ROWS = [1501 + 13 * t for t in range(T)]
 
@@ -35,7 +37,7 @@ def _engine(rows, D, L, B_, kind, slots=2, staged=3):
     n = len(rows)
     eng = N.Engine(N.MODEL_DLRM, rows, D, [8, D], [D * (n + 1), 4, 1], N.INTERACT_CAT, sigmoid_top=2,
                    max_batch=B_, max_lookups=L, num_staged_batches=staged, num_slots=slots)
-    dtype, lines = TYPES[kind]
+    dtype, lines = ENGINE_TYPES[kind]
     if lines:
         eng.set_option(lines, 1)
     if dtype != N.TABLE_FP32:

@@ -11,7 +11,7 @@ DRS_KERNEL_SLS_CLOCK), alternating `--rounds` times:
 for single queries and for launch sets of `--coalesce` queries.  The byte model allows a weighted launch
 (row bytes + 8) / (row bytes + 4) over its unweighted twin: a looked-up row moves its bytes, a 4-byte index and now a
 4-byte weight.  With `--lookups 1 --dim 32` the arms are the one-lookup copy form and the sequential walk (the arm names
-stay; the `form` of every run is in the output).  Prints one JSON line.  Needs a GPU.
+stay; the `form` of every run is in the output), with `--table_dtype 8` or `9` the rowwise instances of the same forms.  Prints one JSON line.  Needs a GPU.
 """
 import argparse
 import json
@@ -34,11 +34,15 @@ def main():
     ap.add_argument("--coalesce", type=int, default=12)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--table_dtype", type=int, default=0, choices=(0, 1, 2, 4, 8, 9),
+                    help='the engine\'s "table_dtype": 0 fp32, 1 fp16, 2 bf16, 4 fp8 e4m3, 8 int8 rowwise, 9 int4 rowwise')
     a = ap.parse_args()
     T, D, L, B = a.tables, a.dim, a.lookups, a.batch
     rng = np.random.RandomState(1)
     eng = N.Engine(N.MODEL_DLRM, [a.rows] * T, D, [128, 64, D], [D * (T + 1), 256, 64, 1], N.INTERACT_CAT, sigmoid_top=2,
                    max_batch=B, max_lookups=L, num_staged_batches=2, num_slots=2)
+    if a.table_dtype:
+        eng.set_option("table_dtype", a.table_dtype)   # (before the fill: the rows are written in their stored type)
     for t in range(T):
         eng.fill_table_uniform(t, -0.01, 0.01, 7)
     for mlp, ln in ((N.MLP_BOT, [128, 64, D]), (N.MLP_TOP, [D * (T + 1), 256, 64, 1])):
@@ -75,7 +79,7 @@ def main():
 
     # (name, "sls_flat" / "sls_one", weights staged, "sls_weighted_flat")
     arms = [("flatc", 1, False, 0), ("ring", 0, False, 0), ("ring,w", 1, True, 0), ("flatc,w", 1, True, 1)]
-    out = {"shape": dict(tables=T, rows=a.rows, D=D, L=L, batch=B), "iters": a.iters, "runs": []}
+    out = {"shape": dict(tables=T, rows=a.rows, D=D, L=L, batch=B, table_dtype=a.table_dtype), "iters": a.iters, "runs": []}
     for r in range(a.rounds):
         for name, flat, weighted, wflat in arms:
             stage(weighted)
@@ -89,7 +93,7 @@ def main():
     eng.set_option("sls_flat", 1)
     eng.set_option("sls_one", 1)
     eng.set_option("sls_weighted_flat", 0)
-    row_bytes = D * 4
+    row_bytes = {0: D * 4, 1: D * 2, 2: D * 2, 4: D, 8: (D + 7) // 8 * 8 + 8, 9: (D // 2 + 3) // 4 * 4 + 4}[a.table_dtype]
     out["byte_model_ring_w_over_ring"] = round((row_bytes + 8) / (row_bytes + 4), 4)
     out["byte_model_flatc_w_over_flatc"] = out["byte_model_ring_w_over_ring"]
     for n_q in (1, a.coalesce):
