@@ -358,37 +358,30 @@ inline int32_t bf16_kpad(int32_t K) { return (K + 63) / 64 * 64; }
 hipError_t launch_bf16_twin(const float* W, int32_t K, int32_t N, uint16_t* Wb, hipStream_t stream);
 
 // random 128- / 256- / 512-byte row reads over [base, base + bytes) in the gather's access shape, timed with events on `s`
-// (sls.hip probe_rows_kernel); sink: >= 1 KiB of device memory nobody reads
+// (sls_probe.hip probe_rows_kernel, lab build only); sink: >= 1 KiB of device memory nobody reads
 hipError_t probe_rows(const void* base, size_t bytes, int waves, int reps, float* sink, hipStream_t s, double* gbs,
                       int windows = 0, int sorted = 0, int row_bytes = 256, int nt = 1, int loads = 20);
 
 // dependent-load walk through each of n_chunks chunks of chunk_bytes (one lane per chunk); d_ticks[k] = 100 MHz ticks
 hipError_t probe_latency(const void* base, size_t chunk_bytes, int n_chunks, int steps, uint64_t* d_ticks, hipStream_t s);
 
-hipError_t launch_fill_uniform(float* W, int64_t n, int32_t t, float lo, float hi, uint64_t seed,
-                               hipStream_t stream);
-// the same values of a table of rows x D, stored as `dtype` (DRS_TABLE_*; fp32: launch_fill_uniform; fp16 / bf16: rounded;
-// int8 / int4 rowwise: each row quantized, n = I8Lines::n of the table's layout)
-hipError_t launch_fill_uniform_dtype(void* W, int dtype, int64_t rows, int D, int32_t t, float lo, float hi, uint64_t seed,
-                                     hipStream_t stream, int32_t n = 0);
-// n table elements of type src_dtype -> dst_dtype (rounded to nearest even; widening is exact); fp32 / fp16 / bf16 only
+// Writing tables (table_convert.hip).  One side of a pass: rows of D columns stored as `dtype` (DRS_TABLE_*).  A rowwise
+// side (int8 / int4) is the TABLE's first byte in the layout lines_n (I8Lines::n of its own type; 0: plain), and the window
+// names its rows first .. first + rows - 1 of `total` (the table's last row clears the rest of its line); a side of any
+// other type points at the window's first row.  scale: an fp8 side's decode scale 2^-k (source) or multiplier 2^k (destination).
+struct TableSide { void* base; int dtype; int32_t lines_n = 0; float scale = 1.0f; };
+struct RowWindow { int64_t first, rows, total; };
+// The window's rows of src, stored as dst asks: rounded to nearest even (widening is exact), quantized per row, encoded
+// as e4m3_rne(x * scale) (torch's float8_e4m3fn conversion bit for bit; NaN and +-inf: 0x7F with the sign bit), or -- the
+// same rowwise type on both sides -- the rows' bytes moved to the other layout.  A rowwise or fp8 source gives each row's
+// value (fmaf(scale, q, 0.0f + bias); decode(code) * scale).  hipErrorInvalidValue: fp8 from fp8 or a rowwise type, an
+// int4 side with odd D, an fp8 source with first != 0.
+hipError_t launch_convert_rows(const TableSide& src, const TableSide& dst, const RowWindow& w, int D, hipStream_t stream);
+// the uniform fill's values of table t (oracle/drs_oracle.c fill_value), stored as dst asks
+hipError_t launch_fill_rows(const TableSide& dst, int64_t rows, int D, int32_t t, float lo, float hi, uint64_t seed, hipStream_t stream);
+// atomicMax of the bits of |x| over the FINITE values of an fp32 / fp16 / bf16 source into *d_bits (a device word the caller zeroed)
+hipError_t launch_absmax_rows(const TableSide& src, int64_t rows, int D, uint32_t* d_bits, hipStream_t stream);
+// n elements of type src_dtype -> dst_dtype, fp32 / fp16 / bf16 only: a whole arena in one pass
 hipError_t launch_convert_table(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, hipStream_t stream);
-// rows x D of one table, into or out of int8 / int4 rowwise: quantized per row, each row's value fmaf(scale, q, 0.0f + bias)
-// rounded to dst_dtype (or quantized again, between the two rowwise types), or (the same rowwise type on both sides) the
-// rows' bytes moved from one layout to the other.  A rowwise side is the TABLE's base, in the layout n_src / n_dst
-// (I8Lines::n of its own type), and the rows are its rows first .. first + rows - 1 of `total` (the last row of a table
-// clears the rest of its line); the other side is the rows themselves, D elements each.
-// An fp8 e4m3 source (src: the table's codes, rows x D bytes; dst_dtype any other type): each code's value
-// decode(code) * src_scale, rounded or quantized as dst_dtype asks.
-hipError_t launch_convert_rows(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t rows, int D, hipStream_t stream,
-                               int32_t n_src = 0, int32_t n_dst = 0, int64_t first = 0, int64_t total = -1, float src_scale = 1.0f);
-// Into fp8 e4m3 ("table_dtype" 4).  The source is rows x D elements of type src_dtype (fp32 / fp16 / bf16: the engine
-// refuses 8 -> 4 and 9 -> 4) or the device fill's values of table t.
-//   launch_absmax_rows: atomicMax of the bits of |x| over the source's FINITE values into *d_bits (a device word the caller zeroed)
-//   launch_rows_to_fp8 / launch_fill_uniform_fp8: dst[r * D + c] = e4m3_rne(x * mul), mul = 2^k -- torch's float8_e4m3fn
-//   conversion bit for bit (round to nearest even, subnormals included; NaN and +-inf: 0x7F with the sign bit)
-hipError_t launch_absmax_rows(const void* src, int src_dtype, int64_t rows, int D, uint32_t* d_bits, hipStream_t stream);
-hipError_t launch_rows_to_fp8(const void* src, int src_dtype, uint8_t* dst, int64_t rows, int D, float mul, hipStream_t stream);
-hipError_t launch_fill_uniform_fp8(uint8_t* dst, int64_t rows, int D, int32_t t, float lo, float hi, uint64_t seed, float mul, hipStream_t stream);
 
 }  // namespace drs

@@ -322,6 +322,10 @@ std::vector<Mlp*> served_mlps(drs_engine* e);
 hipError_t build_bf16_twin(Layer& L);
 // where the tables of an arena of type `dtype` start (*off, units of table_unit_bytes) and its bytes; lines: "table_int8_lines" / "table_int4_lines", the option of that type
 size_t table_layout(const drs_engine* e, int dtype, std::vector<int64_t>* off, int lines = 0);
+// the first byte of table t in the arena of type `dtype` at `base` whose tables start at off[]
+inline char* table_ptr(void* base, const std::vector<int64_t>& off, int t, int dtype) {
+  return static_cast<char*>(base) + off[(size_t)t] * table_unit_bytes(dtype);
+}
 hipError_t upload_fp8_scales(drs_engine* e);   // fp8_k -> d_tab_scale
 int32_t fail(drs_engine* e, int32_t code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
 int32_t set_device(drs_engine* e);

@@ -632,19 +632,16 @@ int32_t drs_set_table(drs_handle e, int32_t t, const float* h_W, int64_t rows) {
       mul = fp8_pow2(e->fp8_k[(size_t)t]);
       HIP_TRY(e, upload_fp8_scales(e));
     }
-    char* dst = reinterpret_cast<char*>(e->tables) + e->tab_off[t] * table_unit_bytes(dt);
+    char* dst = table_ptr(e->tables, e->tab_off, t, dt);
     float* stage = nullptr;
     HIP_TRY(e, hipMalloc(&stage, sizeof(float) * (size_t)(chunk * D)));
     hipError_t r = hipSuccess;
     for (int64_t i = 0; i < rows && r == hipSuccess; i += chunk) {
       const int64_t m = std::min(chunk, rows - i);
       r = hipMemcpy(stage, h_W + i * D, sizeof(float) * (size_t)(m * D), hipMemcpyHostToDevice);
-      if (r == hipSuccess && dt == DRS_TABLE_FP8_E4M3)
-        r = launch_rows_to_fp8(stage, DRS_TABLE_FP32, reinterpret_cast<uint8_t*>(dst) + i * D, m, (int)D, mul, nullptr);
-      else if (r == hipSuccess)
-        // (rowwise: the kernel places rows i .. i + m - 1 of the table itself -- an int8 chunk may start inside a line)
-        r = table_rowwise(dt) ? launch_convert_rows(stage, DRS_TABLE_FP32, dst, dt, m, (int)D, nullptr, 0, e->i8l.n, i, rows)
-                              : launch_convert_table(stage, DRS_TABLE_FP32, dst + i * table_row_stride(dt, D), dt, m * D, nullptr);
+      // (rowwise: the kernel places rows i .. i + m - 1 of the table itself -- an int8 chunk may start inside a line)
+      const TableSide to{table_rowwise(dt) ? dst : dst + i * table_row_stride(dt, D), dt, e->i8l.n, mul};
+      if (r == hipSuccess) r = launch_convert_rows(TableSide{stage, DRS_TABLE_FP32}, to, RowWindow{i, m, rows}, (int)D, nullptr);
       if (r == hipSuccess) r = hipStreamSynchronize(nullptr);    // (before the next chunk overwrites the staging buffer)
     }
     (void)hipFree(stage);
@@ -659,20 +656,16 @@ int32_t drs_fill_table_uniform(drs_handle e, int32_t t, float lo, float hi, uint
   if (rc) return rc;
   if (t < 0 || t >= e->T) return fail(e, DRS_ERR_BAD_ARG, "bad table id");
   if (e->arenas.size() > 1) { if ((rc = drs_sync(e))) return rc; drop_other_placements(e); }
+  TableSide to{table_ptr(e->tables, e->tab_off, t, e->table_dtype), e->table_dtype, e->i8l.n};
   if (e->table_dtype == DRS_TABLE_FP8_E4M3) {
     // fp8 e4m3: the scale comes from the bounds, max(|lo|, |hi|) -- the samples are not inspected, so k may be one less
     // than the conversion of the same fp32 fill would pick
     if ((rc = drs_sync(e))) return rc;
     e->fp8_k[(size_t)t] = fp8_exponent(std::max(fabsf(lo), fabsf(hi)));
     HIP_TRY(e, upload_fp8_scales(e));
-    HIP_TRY(e, launch_fill_uniform_fp8(reinterpret_cast<uint8_t*>(e->tables) + e->tab_off[t], e->rows[t], e->D, t, lo, hi, seed,
-                                       fp8_pow2(e->fp8_k[(size_t)t]), e->slots[0].stream));
-    HIP_TRY(e, hipStreamSynchronize(e->slots[0].stream));
-    e->table_set[t] = true;
-    return DRS_OK;
+    to.scale = fp8_pow2(e->fp8_k[(size_t)t]);
   }
-  HIP_TRY(e, launch_fill_uniform_dtype(reinterpret_cast<char*>(e->tables) + e->tab_off[t] * table_unit_bytes(e->table_dtype), e->table_dtype,
-                                       e->rows[t], e->D, t, lo, hi, seed, e->slots[0].stream, e->i8l.n));
+  HIP_TRY(e, launch_fill_rows(to, e->rows[t], e->D, t, lo, hi, seed, e->slots[0].stream));
   HIP_TRY(e, hipStreamSynchronize(e->slots[0].stream));
   e->table_set[t] = true;
   return DRS_OK;

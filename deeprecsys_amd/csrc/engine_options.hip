@@ -131,31 +131,22 @@ int32_t convert_tables(drs_engine* e, int dt, int lines) {
   // fp8 e4m3: each table's scale exponent from a device reduction over the source's values (the largest finite |x|), then
   // the quantizing pass; out of fp8, each code's value decode * 2^-k goes through the new type's own rounding or quantizer
   std::vector<int32_t> k_new((size_t)e->T, 0);
-  if (to8 || from8) {
-    for (int t = 0; t < e->T && r == hipSuccess; ++t) {
-      const char* src = reinterpret_cast<const char*>(e->tables) + e->tab_off[t] * table_unit_bytes(from);
-      char* dst = reinterpret_cast<char*>(fresh.p) + off[t] * table_unit_bytes(dt);
-      if (from8) {
-        r = launch_convert_rows(src, from, dst, dt, e->rows[t], e->D, nullptr, 0, to_l.n, 0, -1, fp8_pow2(-e->fp8_k[(size_t)t]));
-        continue;
-      }
+  if (!rowwise)    // (fp32 / fp16 / bf16 arenas share their element offsets: one pass over the whole arena)
+    r = launch_convert_table(e->tables, from, fresh.p, dt, (int64_t)(e->tables_bytes / (size_t)table_unit_bytes(from)), nullptr);
+  for (int t = 0; rowwise && t < e->T && r == hipSuccess; ++t) {
+    const TableSide src{table_ptr(e->tables, e->tab_off, t, from), from, from_l.n, from8 ? fp8_pow2(-e->fp8_k[(size_t)t]) : 1.0f};
+    TableSide dst{table_ptr(fresh.p, off, t, dt), dt, to_l.n};
+    if (to8) {
       uint32_t bits = 0;
       r = hipMemset(e->d_absmax, 0, sizeof(uint32_t));
-      if (r == hipSuccess) r = launch_absmax_rows(src, from, e->rows[t], e->D, e->d_absmax, nullptr);
+      if (r == hipSuccess) r = launch_absmax_rows(src, e->rows[t], e->D, e->d_absmax, nullptr);
       if (r == hipSuccess) r = hipMemcpy(&bits, e->d_absmax, sizeof bits, hipMemcpyDeviceToHost);
       float absmax = 0.0f;
       memcpy(&absmax, &bits, sizeof absmax);
       k_new[(size_t)t] = fp8_exponent(absmax);
-      if (r == hipSuccess)
-        r = launch_rows_to_fp8(src, from, reinterpret_cast<uint8_t*>(dst), e->rows[t], e->D, fp8_pow2(k_new[(size_t)t]), nullptr);
+      dst.scale = fp8_pow2(k_new[(size_t)t]);
     }
-  } else if (!rowwise) {    // (fp32 / fp16 / bf16 arenas share their element offsets: one pass over the whole arena)
-    r = launch_convert_table(e->tables, from, fresh.p, dt, (int64_t)(e->tables_bytes / (size_t)table_unit_bytes(from)), nullptr);
-  } else {
-    for (int t = 0; t < e->T && r == hipSuccess; ++t)
-      r = launch_convert_rows(reinterpret_cast<const char*>(e->tables) + e->tab_off[t] * table_unit_bytes(from), from,
-                              reinterpret_cast<char*>(fresh.p) + off[t] * table_unit_bytes(dt), dt, e->rows[t], e->D, nullptr,
-                              from_l.n, to_l.n);
+    if (r == hipSuccess) r = launch_convert_rows(src, dst, RowWindow{0, e->rows[t], e->rows[t]}, e->D, nullptr);
   }
   if (r == hipSuccess) r = hipStreamSynchronize(nullptr);
   if (r == hipSuccess && rowwise) r = hipMemcpy(e->d_tab_off, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice);

@@ -486,536 +486,4 @@ hipError_t launch_sls(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hipS
   }
 }
 
-// ---------------------------------------------------------------------------
-// device-side table fill, bit-identical to oracle/drs_oracle.c fill_value()
-__device__ __forceinline__ float fill_value(int64_t i, int32_t t, float lo, float span, uint64_t seed) {
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)i + ((uint64_t)(uint32_t)t << 40) + 1ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  const float u = (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
-  return __fmaf_rn(u, span, lo);
-}
-__global__ void fill_uniform_kernel(float* W, int64_t n, int32_t t, float lo, float hi,
-                                    uint64_t seed) {
-  const float span = hi - lo;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    W[i] = fill_value(i, t, lo, span, seed);
-  }
-}
-
-// "table_dtype": an fp32 value as it is stored in a table of element type dt (fp16 / bf16: the hardware's
-// round-to-nearest-even conversions, v_cvt_f16_f32 / v_cvt_pk_bf16_f32 -- NaN stays NaN, overflow gives +-inf, fp16
-// subnormals are kept), and back (exact)
-__device__ __forceinline__ void store_elem(void* W, int dt, int64_t i, float x) {
-  if (dt == DRS_TABLE_FP16) static_cast<_Float16*>(W)[i] = (_Float16)x;
-  else if (dt == DRS_TABLE_BF16) static_cast<__bf16*>(W)[i] = (__bf16)x;
-  else static_cast<float*>(W)[i] = x;
-}
-__device__ __forceinline__ float load_elem(const void* W, int dt, int64_t i) {
-  if (dt == DRS_TABLE_FP16) return F16::up1(static_cast<const uint16_t*>(W)[i]);
-  if (dt == DRS_TABLE_BF16) return BF16::up1(static_cast<const uint16_t*>(W)[i]);
-  return static_cast<const float*>(W)[i];
-}
-// n elements of type sdt -> type ddt (the arena conversion of "table_dtype", drs_set_table's staged rows)
-__global__ void convert_table_kernel(const void* src, int sdt, void* dst, int ddt, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    store_elem(dst, ddt, i, load_elem(src, sdt, i));
-}
-// fill_uniform_kernel's fp32 value, rounded to the table's element type
-__global__ void fill_uniform_round_kernel(void* W, int dt, int64_t n, int32_t t, float lo, float hi, uint64_t seed) {
-  const float span = hi - lo;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    store_elem(W, dt, i, fill_value(i, t, lo, span, seed));
-  }
-}
-
-// ---------------------------------------------------------------------------
-// "table_dtype" 8, 8-bit rowwise tables (layout: struct I8).  Quantizing a row, FBGEMM's embedding_bag_byte_prepack in
-// IEEE fp32 without contraction: mn = min, mx = max, range = mx - mn, scale = range / 255, bias = mn,
-// inv = 255 / (range + 1e-8), q = rint((x - mn) * inv).  One wave per row, any D; the row is read twice (the second
-// time from the cache).  Rows holding inf or NaN are outside the contract: the clamp keeps every code a byte.  A finite
-// row with mx - mn = inf (+3e38 beside -3e38) is inside it: scale = inf, inv = 0 and every code 0 (fminf(fmaxf(NaN, 0), 255)
-// is 0 for the element whose x - mn is inf) -- embedding_bag_byte_prepack's bytes; the row decodes to inf * 0 = NaN and
-// the gather keeps that NaN to the bags that name it (I8::addw).
-struct SrcElems {      // row r of a table of element type dt at src (D elements per row)
-  const void* src;
-  int dt;
-  __device__ __forceinline__ float operator()(int64_t r, int D, int c) const { return load_elem(src, dt, r * D + c); }
-};
-struct SrcFill {       // fill_uniform_kernel's values of table t
-  int32_t t;
-  float lo, span;
-  uint64_t seed;
-  __device__ __forceinline__ float operator()(int64_t r, int D, int c) const { return fill_value(r * D + c, t, lo, span, seed); }
-};
-// Where the int8 rows of a launch go, or come from: `base` is the TABLE's first byte, the launch's row r is the table's row
-// first + r (drs_set_table stages a table in chunks) of `total`, n = I8Lines::n of the layout (0: plain).
-struct I8Rows {
-  uint8_t* base;
-  int64_t first, total;
-  int32_t n;
-  __device__ __forceinline__ uint8_t* row(int64_t r, int64_t S) const { return base + i8_row_offset(first + r, S, n); }
-  // line-packed layout: the bytes of its line behind row r that belong to no row -- the line's last 128 - n S bytes after
-  // its last slot, and the unused slots too after the table's last row
-  __device__ __forceinline__ int tail(int64_t r, int64_t S) const {
-    if (!n) return 0;
-    const int slot = (int)((first + r) % n);
-    return slot == n - 1 || first + r == total - 1 ? 128 - (slot + 1) * (int)S : 0;
-  }
-};
-struct SrcI8 {         // each int8 rowwise row's value, fmaf(scale, q, 0.0f + bias)
-  I8Rows rows;
-  __device__ __forceinline__ float operator()(int64_t r, int D, int c) const {
-    const uint8_t* row = rows.row(r, I8::padded(D) + 8);
-    const float2 sb = I8::row_sb(row, D);
-    return I8::row1(sb.x, sb.y, I8::code(row, c), 0.0f);
-  }
-};
-// int4 rowwise rows (layout: struct I4), as I8Rows: `base` is the TABLE's first byte, the launch's row r its row first + r of
-// `total`, n = I8Lines::n of the layout ("table_int4_lines"; 0: plain)
-struct I4Rows {
-  uint8_t* base;
-  int64_t first, total;
-  int32_t n;
-  __device__ __forceinline__ uint8_t* row(int64_t r, int D) const { return base + i8_row_offset(first + r, I4::padded(D) + 4, n); }
-  // the bytes of its line behind row r that belong to no row (I8Rows::tail; a multiple of 4 here)
-  __device__ __forceinline__ int tail(int64_t r, int D) const { return I8Rows{base, first, total, n}.tail(r, I4::padded(D) + 4); }
-};
-struct SrcI4 {         // each int4 rowwise row's value
-  I4Rows rows;
-  __device__ __forceinline__ float operator()(int64_t r, int D, int c) const {
-    const uint8_t* row = rows.row(r, D);
-    const float2 sb = I4::row_sb(row, D);
-    return I4::row1(sb.x, sb.y, I4::code(row, c), 0.0f);
-  }
-};
-template <class Src>
-__device__ __forceinline__ void quantize_rows8(Src src, I8Rows dst, int64_t rows, int D) {
-  const int lane = threadIdx.x & 63;
-  const int D8 = I8::padded(D);
-  const int64_t S = D8 + 8;
-  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
-    float mn = INFINITY, mx = -INFINITY;
-    for (int c = lane; c < D; c += 64) {
-      const float x = src(r, D, c);
-      mn = fminf(mn, x);
-      mx = fmaxf(mx, x);
-    }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-      mn = fminf(mn, __shfl_xor(mn, m));
-      mx = fmaxf(mx, __shfl_xor(mx, m));
-    }
-    const float range = __fsub_rn(mx, mn);
-    const float inv = __fdiv_rn(255.0f, __fadd_rn(range, 1e-8f));
-    uint8_t* row = dst.row(r, S);
-    for (int c = lane; c < D8; c += 64) {
-      const float q = c < D ? rintf(__fmul_rn(__fsub_rn(src(r, D, c), mn), inv)) : 0.f;
-      row[c] = (uint8_t)fminf(fmaxf(q, 0.f), 255.f);
-    }
-    if (lane == 0) *reinterpret_cast<float2*>(row + D8) = make_float2(__fdiv_rn(range, 255.0f), mn);
-    for (int c = lane * 8, z = dst.tail(r, S); c < z; c += 64 * 8) *reinterpret_cast<uint2*>(row + S + c) = make_uint2(0u, 0u);
-  }
-}
-template <class Src>
-__global__ __launch_bounds__(256) void quantize_rows_kernel(Src src, I8Rows dst, int64_t rows, int D) {
-  quantize_rows8(src, dst, rows, D);
-}
-// int4 rowwise rows -> int8 rowwise rows ("table_dtype" 9 -> 8): each row's value, quantized again
-__global__ __launch_bounds__(256) void rows4_to_rows8_kernel(SrcI4 src, I8Rows dst, int64_t rows, int D) {
-  quantize_rows8(src, dst, rows, D);
-}
-// int8 rows -> elements of type dt: each row's value fmaf(scale, q, 0.0f + bias) (the one-row bag), rounded to dt
-__global__ __launch_bounds__(256) void dequantize_rows_kernel(I8Rows src, void* dst, int dt, int64_t rows, int D) {
-  const int lane = threadIdx.x & 63;
-  const int D8 = I8::padded(D);
-  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
-    const uint8_t* row = src.row(r, D8 + 8);
-    const float2 sb = *reinterpret_cast<const float2*>(row + D8);
-    for (int c = lane; c < D; c += 64) store_elem(dst, dt, r * D + c, I8::row1(sb.x, sb.y, (float)row[c], 0.0f));
-  }
-}
-// int8 rows from one layout to the other ("table_int8_lines" set on an int8 arena): the rows' bytes as they are
-__global__ __launch_bounds__(256) void relayout_rows_kernel(I8Rows src, I8Rows dst, int64_t rows, int D) {
-  const int lane = threadIdx.x & 63;
-  const int64_t S = I8::padded(D) + 8;
-  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
-    const uint8_t* from = src.row(r, S);
-    uint8_t* to = dst.row(r, S);
-    for (int c = lane * 8; c < S; c += 64 * 8) *reinterpret_cast<uint2*>(to + c) = *reinterpret_cast<const uint2*>(from + c);
-    for (int c = lane * 8, z = dst.tail(r, S); c < z; c += 64 * 8) *reinterpret_cast<uint2*>(to + S + c) = make_uint2(0u, 0u);
-  }
-}
-
-// ---------------------------------------------------------------------------
-// "table_dtype" 9, 4-bit rowwise tables (layout: struct I4).  Quantizing a row, torch's embedding_bag_4bit_prepack in IEEE
-// fp32 without contraction: bias = fp16(min), scale = fp16((max - (float)bias) / 15), a zero scale becomes 1,
-// inv = 1 / (float)scale (infinite: scale = inv = 1), q = clamp(rint((x - (float)bias) * inv), 0, 15).  One wave per row,
-// any even D; the row is read twice (the second time from the cache).  Rows holding inf or NaN, or values beyond fp16's
-// range, are outside the contract: the clamp keeps every code a nibble.  A finite row with (max - bias) / 15 >= 65520 --
-// one element of 1e6 -- takes the scale +inf, inv = 0 and every code 0, embedding_bag_4bit_prepack's bytes: it decodes to
-// inf * 0 = NaN in every column, and the gather keeps that NaN to the bags that name it (I4::addw).
-template <class Src>
-__device__ __forceinline__ void pack4_rows(Src src, I4Rows dst, int64_t rows, int D) {
-  const int lane = threadIdx.x & 63;
-  const int P = I4::padded(D);
-  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
-    float mn = INFINITY, mx = -INFINITY;
-    for (int c = lane; c < D; c += 64) {
-      const float x = src(r, D, c);
-      mn = fminf(mn, x);
-      mx = fmaxf(mx, x);
-    }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-      mn = fminf(mn, __shfl_xor(mn, m));
-      mx = fmaxf(mx, __shfl_xor(mx, m));
-    }
-    const _Float16 bias_h = (_Float16)mn;
-    const float bias = (float)bias_h;
-    _Float16 scale_h = (_Float16)__fdiv_rn(__fsub_rn(mx, bias), 15.0f);
-    if (scale_h == (_Float16)0.0f) scale_h = (_Float16)1.0f;
-    float inv = __fdiv_rn(1.0f, (float)scale_h);
-    if (isinf(inv)) { scale_h = (_Float16)1.0f; inv = 1.0f; }
-    uint8_t* row = dst.row(r, D);
-    for (int j = lane; j < P; j += 64) {          // byte j: columns 2 j (low nibble) and 2 j + 1
-      uint32_t b = 0;
-      if (2 * j < D) {
-        const float q0 = rintf(__fmul_rn(__fsub_rn(src(r, D, 2 * j), bias), inv));
-        const float q1 = rintf(__fmul_rn(__fsub_rn(src(r, D, 2 * j + 1), bias), inv));
-        b = (uint32_t)fminf(fmaxf(q0, 0.f), 15.f) | ((uint32_t)fminf(fmaxf(q1, 0.f), 15.f) << 4);
-      }
-      row[j] = (uint8_t)b;
-    }
-    if (lane == 0)
-      *reinterpret_cast<uint32_t*>(row + P) = (uint32_t)__builtin_bit_cast(uint16_t, scale_h) | ((uint32_t)__builtin_bit_cast(uint16_t, bias_h) << 16);
-    for (int c = lane * 4, z = dst.tail(r, D); c < z; c += 64 * 4) *reinterpret_cast<uint32_t*>(row + P + 4 + c) = 0u;
-  }
-}
-template <class Src>
-__global__ __launch_bounds__(256) void pack4_rows_kernel(Src src, I4Rows dst, int64_t rows, int D) {
-  pack4_rows(src, dst, rows, D);
-}
-// int4 rows -> elements of type dt: each row's value fmaf(scale, q, 0.0f + bias) (the one-row bag), rounded to dt
-__global__ __launch_bounds__(256) void unpack4_rows_kernel(SrcI4 src, void* dst, int dt, int64_t rows, int D) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4)
-    for (int c = lane; c < D; c += 64) store_elem(dst, dt, r * D + c, src(r, D, c));
-}
-// int4 rows from one layout to the other ("table_int4_lines" set on an int4 arena): the rows' bytes as they are
-__global__ __launch_bounds__(256) void relayout4_rows_kernel(I4Rows src, I4Rows dst, int64_t rows, int D) {
-  const int lane = threadIdx.x & 63;
-  const int S = I4::padded(D) + 4;
-  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
-    const uint8_t* from = src.row(r, D);
-    uint8_t* to = dst.row(r, D);
-    for (int c = lane * 4; c < S; c += 64 * 4) *reinterpret_cast<uint32_t*>(to + c) = *reinterpret_cast<const uint32_t*>(from + c);
-    for (int c = lane * 4, z = dst.tail(r, D); c < z; c += 64 * 4) *reinterpret_cast<uint32_t*>(to + S + c) = 0u;
-  }
-}
-static unsigned row_grid(int64_t rows) {
-  const int64_t want = (rows + 3) / 4;
-  return (unsigned)(want < 16384 ? want : 16384);
-}
-
-// ---------------------------------------------------------------------------
-// "table_dtype" 4, fp8 e4m3 tables (layout: struct F8).  e4m3_rne: an fp32 value as its OCP e4m3 code, torch's
-// float8_e4m3fn conversion in integer arithmetic, bit for bit: round to nearest even, the subnormal codes (multiples of
-// 2^-9 below 2^-6) through the add of 2^14 whose ulp they are, 0x7F (NaN) with the sign bit for NaN, +-inf and everything
-// that rounds beyond 448 -- which no finite element does after the table's scale.
-__device__ __forceinline__ uint8_t e4m3_rne(float x) {
-  uint32_t b = __float_as_uint(x);
-  const uint32_t sign = b & 0x80000000u;
-  b ^= sign;
-  uint32_t q;
-  if (b >= 0x43F00000u) {                           // >= 480, +-inf, NaN
-    q = 0x7Fu;
-  } else if (b < (121u << 23)) {                    // below 2^-6
-    q = __float_as_uint(__fadd_rn(__uint_as_float(b), __uint_as_float(141u << 23))) - (141u << 23);
-  } else {
-    const uint32_t odd = (b >> 20) & 1u;
-    b += ((uint32_t)(7 - 127) << 23) + 0x7FFFFu + odd;
-    q = b >> 20;
-  }
-  return (uint8_t)(q | (sign >> 24));
-}
-struct SrcF8 {         // each fp8 code's value, decode(code) * 2^-k of its table
-  const uint8_t* codes;
-  float scale;
-  __device__ __forceinline__ float operator()(int64_t r, int D, int c) const { return __fmul_rn(F8::up1(codes[r * D + c]), scale); }
-};
-// the largest |x| over the source's finite values, as its bits: one atomicMax per wave into *out (zeroed by the caller)
-template <class Src>
-__global__ __launch_bounds__(256) void absmax_rows_kernel(Src src, int64_t rows, int D, uint32_t* out) {
-  const int64_t n = rows * D;
-  uint32_t m = 0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = i / D;
-    const uint32_t b = __float_as_uint(src(r, D, (int)(i - r * D))) & 0x7fffffffu;
-    m = b < 0x7f800000u && b > m ? b : m;
-  }
-#pragma unroll
-  for (int k = 1; k < 64; k <<= 1) {
-    const uint32_t o = (uint32_t)__shfl_xor((int)m, k);
-    m = o > m ? o : m;
-  }
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
-}
-// rows x D source values -> codes: dst[r * D + c] = e4m3_rne(x * mul), mul = 2^k
-template <class Src>
-__global__ __launch_bounds__(256) void to_fp8_rows_kernel(Src src, uint8_t* dst, int64_t rows, int D, float mul) {
-  const int64_t n = rows * D;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = i / D;
-    dst[i] = e4m3_rne(__fmul_rn(src(r, D, (int)(i - r * D)), mul));
-  }
-}
-// fp8 rows -> int8 / int4 rowwise rows ("table_dtype" 4 -> 8, 4 -> 9): each code's value, through that type's quantizer
-__global__ __launch_bounds__(256) void fp8_to_rows8_kernel(SrcF8 src, I8Rows dst, int64_t rows, int D) {
-  quantize_rows8(src, dst, rows, D);
-}
-__global__ __launch_bounds__(256) void fp8_to_rows4_kernel(SrcF8 src, I4Rows dst, int64_t rows, int D) {
-  pack4_rows(src, dst, rows, D);
-}
-// fp8 rows -> elements of type dt: each code's value, rounded to dt
-__global__ __launch_bounds__(256) void from_fp8_rows_kernel(SrcF8 src, void* dst, int dt, int64_t rows, int D) {
-  const int64_t n = rows * D;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = i / D;
-    store_elem(dst, dt, i, src(r, D, (int)(i - r * D)));
-  }
-}
-static unsigned elem_grid(int64_t n) {
-  const int64_t want = (n + 255) / 256;
-  return (unsigned)(want < 16384 ? want : 16384);
-}
-static bool plain_dtype(int dtype) { return dtype == DRS_TABLE_FP32 || dtype == DRS_TABLE_FP16 || dtype == DRS_TABLE_BF16; }
-
-#ifdef DRS_LAB   // probes of tools/placement_lab.py (libdrs_hip_lab.so: make lab-lib); not in the product library
-// ---------------------------------------------------------------------------
-// Row-read probe of a range of device memory: the access shape of the many-rows-per-bag gather (a wave =
-// 80 random 256-byte rows, 4 per load instruction, all 20 loads of a lane in flight, non-temporal) without
-// index arrays or outputs.  What it is for: DESIGN.md 5 -- the same gather runs up to 9 % faster on some
-// gigabytes of HBM than on others, and the arena builder keeps the gigabytes this probe reads fastest.
-// G lanes per row (16 bytes each): 16 = RMC1's 256-byte rows (a wave = 80 rows), 8 = 128-byte rows (dlrm_rm1.json / RM3:
-// a wave = 160 rows, eight per load instruction), 32 = 512-byte rows; NT: non-temporal loads (a compile-time property).
-template <int G, bool NT, int NLD>
-__global__ __launch_bounds__(64) void probe_rows_kernel(const float4* __restrict__ base, uint32_t rows, uint32_t seed,
-                                                        float4* __restrict__ sink, uint32_t windows, uint32_t stride_rows, int sorted) {
-  // windows == 0: the wave's 80 rows anywhere in [0, rows).  windows > 0: wave w reads inside window w % windows
-  // (window k = rows [k * stride_rows, k * stride_rows + rows)), like a bag of one table; sorted: ascending, one row per
-  // eightieth of the window (what np.unique leaves of a bag's indices)
-  constexpr int NG = 64 / G;                       // rows per load instruction
-  constexpr uint32_t RW = NLD * NG;                 // rows per wave
-  const int lane = threadIdx.x, g = lane / G, gl = lane % G;
-  const uint64_t w0 = windows ? (uint64_t)(blockIdx.x % windows) * stride_rows : 0;
-  uint32_t r[NLD];
-#pragma unroll
-  for (int u = 0; u < NLD; ++u) {
-    uint32_t z = (blockIdx.x * RW + (uint32_t)(NG * u + g)) * 0x9E3779B1u + seed;
-    z = (z ^ (z >> 16)) * 0x85EBCA6Bu;
-    z = (z ^ (z >> 13)) * 0xC2B2AE35u;
-    z ^= z >> 16;
-    if (sorted) {
-      const uint32_t lo = (uint32_t)(((uint64_t)(NG * u + g) * rows) / RW), hi = (uint32_t)(((uint64_t)(NG * u + g + 1) * rows) / RW);
-      r[u] = lo + (uint32_t)(((uint64_t)z * (hi > lo ? hi - lo : 1)) >> 32);
-    } else {
-      r[u] = (uint32_t)(((uint64_t)z * rows) >> 32);
-    }
-  }
-  float4 v[NLD];
-#pragma unroll
-  for (int u = 0; u < NLD; ++u) {
-    if constexpr (NT) v[u] = ld_nt(base + (w0 + r[u]) * G + gl);
-    else v[u] = base[(w0 + r[u]) * G + gl];
-  }
-  float4 acc = vzero4();
-#pragma unroll
-  for (int u = 0; u < NLD; ++u) vadd(acc, v[u]);
-  if (acc.x == 1.2345e-30f) sink[lane] = acc;      // (keeps the loads alive; never true for table data)
-}
-
-// time `reps` launches of `waves` waves over [base, base + bytes); GB/s of row bytes in *gbs
-hipError_t probe_rows(const void* base, size_t bytes, int waves, int reps, float* sink, hipStream_t s, double* gbs,
-                      int windows, int sorted, int row_bytes, int nt, int loads) {
-  *gbs = 0;
-  if (row_bytes != 128 && row_bytes != 256 && row_bytes != 512) return hipErrorInvalidValue;
-  uint64_t rows = bytes / (uint64_t)row_bytes, stride = 0;
-  if (windows > 0) { stride = rows / (uint64_t)windows; rows = stride; }
-  if (loads != 10 && loads != 20) return hipErrorInvalidValue;
-  const int G = row_bytes / 16, rw = loads * (64 / G);
-  if (rows < (uint64_t)rw || rows > 0xffffffffull) return hipErrorInvalidValue;
-  auto launch = [&](uint32_t seed) {
-#define DRS_PROBE(G_, NT_)                                                                                                               \
-  do {                                                                                                                                     \
-    if (loads == 10) hipLaunchKernelGGL((probe_rows_kernel<G_, NT_, 10>), dim3((unsigned)waves), dim3(64), 0, s, static_cast<const float4*>(base), \
-                                        (uint32_t)rows, seed, reinterpret_cast<float4*>(sink), (uint32_t)windows, (uint32_t)stride, sorted); \
-    else hipLaunchKernelGGL((probe_rows_kernel<G_, NT_, 20>), dim3((unsigned)waves), dim3(64), 0, s, static_cast<const float4*>(base),       \
-                            (uint32_t)rows, seed, reinterpret_cast<float4*>(sink), (uint32_t)windows, (uint32_t)stride, sorted);            \
-  } while (0)
-    if (G == 8) { if (nt) DRS_PROBE(8, true); else DRS_PROBE(8, false); }
-    else if (G == 16) { if (nt) DRS_PROBE(16, true); else DRS_PROBE(16, false); }
-    else { if (nt) DRS_PROBE(32, true); else DRS_PROBE(32, false); }
-#undef DRS_PROBE
-  };
-  hipEvent_t e0, e1;
-  hipError_t r = hipEventCreate(&e0);
-  if (r != hipSuccess) return r;
-  r = hipEventCreate(&e1);
-  if (r != hipSuccess) { (void)hipEventDestroy(e0); return r; }
-  launch(1u);
-  r = hipEventRecord(e0, s);
-  for (int i = 0; i < reps && r == hipSuccess; ++i) {
-    launch(0x51ED27u * (uint32_t)(i + 2));
-    r = hipGetLastError();
-  }
-  if (r == hipSuccess) r = hipEventRecord(e1, s);
-  if (r == hipSuccess) r = hipEventSynchronize(e1);
-  float ms = 0.f;
-  if (r == hipSuccess) r = hipEventElapsedTime(&ms, e0, e1);
-  if (r == hipSuccess && ms > 0.f) *gbs = (double)waves * (double)rw * (double)row_bytes * reps / (ms * 1e-3) / 1e9;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return r;
-}
-
-// Latency probe: workgroup k walks `steps` DEPENDENT 16-byte loads through random 256-byte rows of chunk k
-// ([base + k * chunk_bytes, + chunk_bytes)); out[k] = device-clock ticks (100 MHz) for the walk.  One lane per
-// chunk, all chunks at once: the walks do not disturb each other, and a launch is steps x ~1 us long.
-__global__ __launch_bounds__(64) void probe_latency_kernel(const float4* __restrict__ base, uint64_t chunk_rows, uint32_t rows,
-                                                           int steps, uint32_t seed, uint64_t* __restrict__ out) {
-  if (threadIdx.x != 0) return;
-  const float4* b = base + (uint64_t)blockIdx.x * chunk_rows * 16;
-  uint32_t z = seed + blockIdx.x * 0x9E3779B1u;
-  float sink = 0.f;
-  const uint64_t t0 = wall_clock64();
-  for (int i = 0; i < steps; ++i) {
-    z = (z ^ (z >> 16)) * 0x85EBCA6Bu;
-    z = (z ^ (z >> 13)) * 0xC2B2AE35u;
-    z ^= z >> 16;
-    const uint32_t r = (uint32_t)(((uint64_t)z * rows) >> 32);
-    const float4 v = ld_nt(b + (uint64_t)r * 16 + (z & 15));
-    z += __float_as_uint(v.x) | 1u;                  // the next address depends on the loaded value
-    sink += v.y;
-  }
-  const uint64_t t1 = wall_clock64();
-  out[blockIdx.x] = t1 - t0 + (sink == 1.2345e-30f ? 1 : 0);
-}
-
-hipError_t probe_latency(const void* base, size_t chunk_bytes, int n_chunks, int steps, uint64_t* d_ticks, hipStream_t s) {
-  const uint64_t rows = chunk_bytes / 256;
-  if (rows < 1 || rows > 0xffffffffull || n_chunks < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(probe_latency_kernel, dim3((unsigned)n_chunks), dim3(64), 0, s, static_cast<const float4*>(base), rows,
-                     (uint32_t)rows, steps, 12345u, d_ticks);
-  return hipGetLastError();
-}
-
-#endif  // DRS_LAB
-
-hipError_t launch_fill_uniform(float* W, int64_t n, int32_t t, float lo, float hi, uint64_t seed,
-                               hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  const int64_t want = (n + 255) / 256;
-  const unsigned grid = (unsigned)(want < 8192 ? want : 8192);
-  hipLaunchKernelGGL(fill_uniform_kernel, dim3(grid), dim3(256), 0, s, W, n, t, lo, hi, seed);
-  return hipGetLastError();
-}
-
-hipError_t launch_fill_uniform_dtype(void* W, int dtype, int64_t rows, int D, int32_t t, float lo, float hi, uint64_t seed,
-                                     hipStream_t s, int32_t n_lines) {
-  const int64_t n = rows * D;
-  if (dtype == DRS_TABLE_FP32) return launch_fill_uniform(static_cast<float*>(W), n, t, lo, hi, seed, s);
-  if (n <= 0) return hipSuccess;
-  if (dtype == DRS_TABLE_INT4_ROWWISE) {
-    if (D & 1) return hipErrorInvalidValue;   // (internal guard: the engine refuses table_dtype 9 on odd D before any launch)
-    hipLaunchKernelGGL(pack4_rows_kernel<SrcFill>, dim3(row_grid(rows)), dim3(256), 0, s, SrcFill{t, lo, hi - lo, seed},
-                       I4Rows{static_cast<uint8_t*>(W), 0, rows, n_lines}, rows, D);
-    return hipGetLastError();
-  }
-  if (dtype == DRS_TABLE_INT8_ROWWISE) {
-    hipLaunchKernelGGL(quantize_rows_kernel<SrcFill>, dim3(row_grid(rows)), dim3(256), 0, s, SrcFill{t, lo, hi - lo, seed},
-                       I8Rows{static_cast<uint8_t*>(W), 0, rows, n_lines}, rows, D);
-    return hipGetLastError();
-  }
-  const int64_t want = (n + 255) / 256;
-  const unsigned grid = (unsigned)(want < 8192 ? want : 8192);
-  hipLaunchKernelGGL(fill_uniform_round_kernel, dim3(grid), dim3(256), 0, s, W, dtype, n, t, lo, hi, seed);
-  return hipGetLastError();
-}
-
-hipError_t launch_absmax_rows(const void* src, int src_dtype, int64_t rows, int D, uint32_t* d_bits, hipStream_t s) {
-  if (rows <= 0) return hipSuccess;
-  if (!plain_dtype(src_dtype)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(absmax_rows_kernel<SrcElems>, dim3(elem_grid(rows * D)), dim3(256), 0, s, SrcElems{src, src_dtype}, rows, D, d_bits);
-  return hipGetLastError();
-}
-
-hipError_t launch_rows_to_fp8(const void* src, int src_dtype, uint8_t* dst, int64_t rows, int D, float mul, hipStream_t s) {
-  if (rows <= 0) return hipSuccess;
-  if (!plain_dtype(src_dtype)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(to_fp8_rows_kernel<SrcElems>, dim3(elem_grid(rows * D)), dim3(256), 0, s, SrcElems{src, src_dtype}, dst, rows, D, mul);
-  return hipGetLastError();
-}
-
-hipError_t launch_fill_uniform_fp8(uint8_t* dst, int64_t rows, int D, int32_t t, float lo, float hi, uint64_t seed, float mul, hipStream_t s) {
-  if (rows <= 0) return hipSuccess;
-  hipLaunchKernelGGL(to_fp8_rows_kernel<SrcFill>, dim3(elem_grid(rows * D)), dim3(256), 0, s, SrcFill{t, lo, hi - lo, seed}, dst, rows, D, mul);
-  return hipGetLastError();
-}
-
-hipError_t launch_convert_rows(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t rows, int D, hipStream_t s,
-                               int32_t n_src, int32_t n_dst, int64_t first, int64_t total, float src_scale) {
-  if (rows <= 0) return hipSuccess;
-  if (total < 0) total = first + rows;
-  if (src_dtype == DRS_TABLE_FP8_E4M3) {   // (whole tables only: first == 0)
-    const SrcF8 from8{static_cast<const uint8_t*>(src), src_scale};
-    const dim3 grid(row_grid(rows)), block(256);
-    if (first != 0 || dst_dtype == DRS_TABLE_FP8_E4M3 || (dst_dtype == DRS_TABLE_INT4_ROWWISE && (D & 1))) return hipErrorInvalidValue;
-    if (dst_dtype == DRS_TABLE_INT8_ROWWISE)
-      hipLaunchKernelGGL(fp8_to_rows8_kernel, grid, block, 0, s, from8, I8Rows{static_cast<uint8_t*>(dst), 0, total, n_dst}, rows, D);
-    else if (dst_dtype == DRS_TABLE_INT4_ROWWISE)
-      hipLaunchKernelGGL(fp8_to_rows4_kernel, grid, block, 0, s, from8, I4Rows{static_cast<uint8_t*>(dst), 0, total, n_dst}, rows, D);
-    else
-      hipLaunchKernelGGL(from_fp8_rows_kernel, dim3(elem_grid(rows * D)), block, 0, s, from8, dst, dst_dtype, rows, D);
-    return hipGetLastError();
-  }
-  if (dst_dtype == DRS_TABLE_FP8_E4M3) return hipErrorInvalidValue;   // (launch_rows_to_fp8: it needs the table's scale first)
-  const I8Rows from{static_cast<uint8_t*>(const_cast<void*>(src)), first, total, n_src}, to{static_cast<uint8_t*>(dst), first, total, n_dst};
-  const bool si8 = src_dtype == DRS_TABLE_INT8_ROWWISE, di8 = dst_dtype == DRS_TABLE_INT8_ROWWISE;
-  const bool si4 = src_dtype == DRS_TABLE_INT4_ROWWISE, di4 = dst_dtype == DRS_TABLE_INT4_ROWWISE;
-  if (si4 || di4) {
-    // (internal guard, unreachable through the engine: convert_tables refuses odd D)
-    if (D & 1) return hipErrorInvalidValue;
-    const dim3 grid(row_grid(rows)), block(256);
-    const SrcI4 from4{I4Rows{from.base, first, total, n_src}};
-    const I4Rows to4{to.base, first, total, n_dst};
-    if (si4 && di4) hipLaunchKernelGGL(relayout4_rows_kernel, grid, block, 0, s, from4.rows, to4, rows, D);
-    else if (si4 && di8) hipLaunchKernelGGL(rows4_to_rows8_kernel, grid, block, 0, s, from4, to, rows, D);
-    else if (si4) hipLaunchKernelGGL(unpack4_rows_kernel, grid, block, 0, s, from4, dst, dst_dtype, rows, D);
-    else if (si8) hipLaunchKernelGGL(pack4_rows_kernel<SrcI8>, grid, block, 0, s, SrcI8{from}, to4, rows, D);
-    else hipLaunchKernelGGL(pack4_rows_kernel<SrcElems>, grid, block, 0, s, SrcElems{src, src_dtype}, to4, rows, D);
-    return hipGetLastError();
-  }
-  if (di8 && !si8)
-    hipLaunchKernelGGL(quantize_rows_kernel<SrcElems>, dim3(row_grid(rows)), dim3(256), 0, s, SrcElems{src, src_dtype}, to, rows, D);
-  else if (si8 && !di8)
-    hipLaunchKernelGGL(dequantize_rows_kernel, dim3(row_grid(rows)), dim3(256), 0, s, from, dst, dst_dtype, rows, D);
-  else if (si8 && di8)
-    hipLaunchKernelGGL(relayout_rows_kernel, dim3(row_grid(rows)), dim3(256), 0, s, from, to, rows, D);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-
-hipError_t launch_convert_table(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  const int64_t want = (n + 255) / 256;
-  const unsigned grid = (unsigned)(want < 16384 ? want : 16384);
-  hipLaunchKernelGGL(convert_table_kernel, dim3(grid), dim3(256), 0, s, src, src_dtype, dst, dst_dtype, n);
-  return hipGetLastError();
-}
-
 }  // namespace drs

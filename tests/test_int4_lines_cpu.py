@@ -4,7 +4,6 @@ line), the multiply-and-shift quotient the gather kernels take for r / n, and a 
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ from deeprecsys_amd import dlrm_s_hip
 from deeprecsys_amd.utils.utils import FLAG_CHOICES, cli
 from tests import helpers as H
 from tests.test_bf16_mlp_cpu import _Recorder
+from tests.test_table_convert_cpu import listing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEY = "table_int4_lines"
@@ -205,25 +205,18 @@ def test_documents_name_the_key():
 
 # ---- 8. compile check -------------------------------------------------------------------------------------------------
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
-def test_line_packed_int4_kernels_exist_and_use_no_scratch(tmp_path):
-    """sls.hip compiled with the Makefile's flags: an I4L instance of each of the five gather families exists, none uses
-    scratch, and the kernel that moves int4 rows between the two layouts exists."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    src = os.path.join(ROOT, "deeprecsys_amd", "csrc")
-    out = str(tmp_path / "sls.s")
-    flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function", "-Wno-inline-asm"]
-    r = subprocess.run([hipcc] + flags + ["--offload-device-only", "-S", "-o", out, os.path.join(src, "sls.hip")],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    asm = open(out).read()
+def test_line_packed_int4_kernels_exist_and_use_no_scratch():
+    """sls.hip compiled with the Makefile's flags: an I4L instance of each of the five gather families exists and none
+    uses scratch.  (The kernel that moves rows between the two layouts: table_convert.hip,
+    tests/test_table_convert_cpu.py.)"""
+    asm = listing("sls.hip")
     found = {}
     for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", asm, re.S):
         name, body = m.group(1), m.group(2)
-        kind = re.search(r"(sls_kernel|sls_one_kernel|sls_flat_kernel|sls_flatc_kernel|sls_any_kernel|relayout4_rows_kernel)", name)
-        if not kind or (kind.group(1).startswith("sls_") and "3I4LE" not in name):
+        kind = re.search(r"(sls_kernel|sls_one_kernel|sls_flat_kernel|sls_flatc_kernel|sls_any_kernel)", name)
+        if not kind or "3I4LE" not in name:
             continue
         found[kind.group(1)] = found.get(kind.group(1), 0) + 1
         assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)) == 0, name
     for kind in ("sls_kernel", "sls_one_kernel", "sls_flat_kernel", "sls_flatc_kernel", "sls_any_kernel"):
         assert found.get(kind, 0) > 0, (kind, found)
-    assert found.get("relayout4_rows_kernel") == 1, found

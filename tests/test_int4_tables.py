@@ -294,6 +294,32 @@ def test_line_packed_int8_rows_convert_to_int4(D):
         eng.close()
 
 
+@pytest.mark.parametrize("D", [12, 32])
+def test_line_packed_int4_rows_convert_to_line_packed_int8(D):
+    """9 -> 8 with BOTH sides line-packed (table_int4_lines 1 and table_int8_lines 1; D 12: ten int4 rows and five int8
+    rows to a line, D 32: six and three): every int4 row's value, quantized as byte prepack quantizes it.  Tables of 37
+    and 5 rows: the last line of each is partly filled on either side."""
+    rng = np.random.RandomState(60 + D)
+    rows, B = [37, 5], 37
+    tables = [_special_rows(rng.uniform(-1, 1, (r, D)).astype(np.float32)) for r in rows]
+    ix = [(np.arange(B) % r).astype(np.int64) for r in rows]                  # every row of either table
+    n4, n8 = 128 // _stride(D), 128 // _stride8(D)
+    eng = _engine(rows, D, 1, B, N.TABLE_FP32, slots=1, staged=1)
+    try:
+        eng.set_option("table_int4_lines", 1)
+        eng.set_option("table_int8_lines", 1)
+        eng.set_option("table_dtype", I4)
+        _load(eng, tables, D)
+        assert eng.get_option("table_bytes") == sum(((r + n4 - 1) // n4 * 128 + 255) // 256 * 256 for r in rows)
+        eng.set_option("table_dtype", I8)
+        assert eng.get_option("table_bytes") == sum(((r + n8 - 1) // n8 * 128 + 255) // 256 * 256 for r in rows)
+        e = np.concatenate([dequant8(dequant(W))[ix[t]] for t, W in enumerate(tables)], axis=1)
+        for k, got in enumerate(_one_row_bags(eng, rows, D, B, ix)):
+            assert _same(got, e), k
+    finally:
+        eng.close()
+
+
 def test_rows_wider_than_a_wave_take_the_generic_form():
     """D 258 (even, no multiple of 4, above 256): sls_any_kernel<i4> walks the row in two passes of 64 x 4 columns;
     ragged bags with empty ones, bit-identical to embedding_bag_4bit_rowwise_offsets under either sls_exact."""

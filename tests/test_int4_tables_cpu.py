@@ -5,7 +5,6 @@ here)."""
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ from deeprecsys_amd import _native as N
 from deeprecsys_amd import dlrm_s_hip
 from deeprecsys_amd.utils.utils import cli
 from tests import helpers as H
+from tests.test_table_convert_cpu import listing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -154,33 +154,22 @@ def test_options_doc_names_the_value():
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
-def test_int4_kernels_exist_and_do_not_spill(tmp_path):
+def test_int4_kernels_exist_and_do_not_spill():
     """sls.hip compiled with the Makefile's flags: an int4 instance of each of the five gather families exists; every one
-    of them, and each int4 table kernel (quantize, write out, int4 -> int8), uses no scratch, and nothing spills a VGPR.
-    The RMC1 form reads its 20 rows per lane with non-temporal 2-byte loads of the codes, each beside a non-temporal
-    dword load of the row's fp16 scale and bias."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    src = os.path.join(ROOT, "deeprecsys_amd", "csrc")
-    out = str(tmp_path / "sls.s")
-    flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function", "-Wno-inline-asm"]
-    r = subprocess.run([hipcc] + flags + ["--offload-device-only", "-S", "-o", out, os.path.join(src, "sls.hip")],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    asm = open(out).read()
+    of them uses no scratch, and nothing spills a VGPR.  The RMC1 form reads its 20 rows per lane with non-temporal 2-byte
+    loads of the codes, each beside a non-temporal dword load of the row's fp16 scale and bias.  (The kernels that write
+    int4 tables -- quantize, write out, int4 -> int8: table_convert.hip, tests/test_table_convert_cpu.py.)"""
+    asm = listing("sls.hip")
     found = {}
     for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", asm, re.S):
         name, body = m.group(1), m.group(2)
-        kind = re.search(r"(sls_kernel|sls_one_kernel|sls_flat_kernel|sls_flatc_kernel|sls_any_kernel|unpack4_rows_kernel|"
-                         r"pack4_rows_kernel|rows4_to_rows8_kernel)", name)
-        if not kind or (kind.group(1).startswith("sls_") and "2I4E" not in name):
+        kind = re.search(r"(sls_kernel|sls_one_kernel|sls_flat_kernel|sls_flatc_kernel|sls_any_kernel)", name)
+        if not kind or "2I4E" not in name:
             continue
         found[kind.group(1)] = found.get(kind.group(1), 0) + 1
         assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)) == 0, name
     for kind in ("sls_kernel", "sls_one_kernel", "sls_flat_kernel", "sls_flatc_kernel", "sls_any_kernel"):
         assert found.get(kind, 0) > 0, (kind, found)
-    # quantizing from fp32 / fp16 / bf16 elements, from the fill's values and from int8 rows; one kernel each way out
-    assert found.get("pack4_rows_kernel") == 3 and found.get("unpack4_rows_kernel") == 1, found
-    assert found.get("rows4_to_rows8_kernel") == 1, found
     assert set(re.findall(r"\.vgpr_spill_count:\s+(\d+)", asm)) == {"0"}
     body = re.search(r"^(_ZN3drs12_GLOBAL__N_116sls_flatc_kernelILi16ELi20ELb1ENS0_2I4EEEvNS_7SlsArgsEi):(.*?)^\.Lfunc_end",
                      asm, re.S | re.M).group(2)

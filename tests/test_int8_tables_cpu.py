@@ -4,7 +4,6 @@ the ISA of the int8 gather kernels (hipcc cross-compiles here)."""
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ from deeprecsys_amd import _native as N
 from deeprecsys_amd import dlrm_s_hip
 from deeprecsys_amd.utils.utils import cli
 from tests import helpers as H
+from tests.test_table_convert_cpu import listing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -99,31 +99,22 @@ def test_quantization_formula_matches_embedding_bag_byte_prepack(D):
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
-def test_int8_gather_kernels_exist_and_do_not_spill(tmp_path):
+def test_int8_gather_kernels_exist_and_do_not_spill():
     """sls.hip compiled with the Makefile's flags: every int8 instantiation of the five gather families exists, uses no
     scratch and spills no VGPR; the RMC1 form reads its 20 rows per lane with non-temporal dword loads of the codes, each
     beside a non-temporal 8-byte load of the row's scale and bias, all issued before the first sum, and converts the codes
-    with v_cvt_f32_ubyte0..3."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    src = os.path.join(ROOT, "deeprecsys_amd", "csrc")
-    out = str(tmp_path / "sls.s")
-    flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function", "-Wno-inline-asm"]
-    r = subprocess.run([hipcc] + flags + ["--offload-device-only", "-S", "-o", out, os.path.join(src, "sls.hip")],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    asm = open(out).read()
+    with v_cvt_f32_ubyte0..3.  (The kernels that write int8 tables: table_convert.hip, tests/test_table_convert_cpu.py.)"""
+    asm = listing("sls.hip")
     found = {}
     for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", asm, re.S):
         name, body = m.group(1), m.group(2)
-        kind = re.search(r"(sls_kernel|sls_one_kernel|sls_flat_kernel|sls_flatc_kernel|sls_any_kernel|quantize_rows_kernel|"
-                         r"dequantize_rows_kernel)", name)
-        if not kind or ("2I8E" not in name and "quantize" not in kind.group(1)):
+        kind = re.search(r"(sls_kernel|sls_one_kernel|sls_flat_kernel|sls_flatc_kernel|sls_any_kernel)", name)
+        if not kind or "2I8E" not in name:
             continue
         found[kind.group(1)] = found.get(kind.group(1), 0) + 1
         assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)) == 0, name
     for kind in ("sls_kernel", "sls_one_kernel", "sls_flat_kernel", "sls_flatc_kernel", "sls_any_kernel"):
         assert found.get(kind, 0) > 0, (kind, found)
-    assert found.get("quantize_rows_kernel") == 2 and found.get("dequantize_rows_kernel") == 1, found
     assert set(re.findall(r"\.vgpr_spill_count:\s+(\d+)", asm)) == {"0"}
     body = re.search(r"^(_ZN3drs12_GLOBAL__N_116sls_flatc_kernelILi16ELi20ELb1ENS0_2I8EEEvNS_7SlsArgsEi):(.*?)^\.Lfunc_end",
                      asm, re.S | re.M).group(2)

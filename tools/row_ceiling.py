@@ -1,6 +1,6 @@
 """GPU-box lab: what can random fixed-size rows reach on this HBM?
 
-The synthetic row-read probe (sls.hip probe_rows_kernel, lab build: make -C deeprecsys_amd/csrc lab-lib) over the
+The synthetic row-read probe (sls_probe.hip probe_rows_kernel, lab build: make -C deeprecsys_amd/csrc lab-lib) over the
 model's own table arena: every wave issues 10 or 20 loads of 16 bytes per lane, 128- / 256- / 512-byte rows
 (8 / 16 / 32 lanes per row), non-temporal or plain, rows anywhere in the arena or inside one table per wave
 (`windows` = T, like a bag), no index arrays, no outputs -- the gather's access shape with nothing else in the way.
