@@ -100,6 +100,12 @@ FP8_SYMBOLS = [
     ("drs_table_fp8_exponent", C.c_int32, [C.c_void_p, C.c_int32, _i32p]),
 ]
 
+# single table rows, written and read back in the stored type (include/drs_rows.h) -- the HIP build alone, as above
+ROW_SYMBOLS = [
+    ("drs_update_rows", C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _i64p, _f32p]),
+    ("drs_get_rows", C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _i64p, _f32p]),
+]
+
 
 class ModelCfg(C.Structure):
     _fields_ = [
@@ -146,7 +152,7 @@ def lib():
         if not backend.startswith(b"hip:"):
             raise ImportError("%s identifies itself as %r: deeprecsys_amd binds the HIP build only "
                               "(the CPU restatement of the ABI is test infrastructure)" % (LIB_PATH, backend))
-        for name, res, args in WEIGHT_SYMBOLS + FP8_SYMBOLS:     # (the HIP build alone exports these)
+        for name, res, args in WEIGHT_SYMBOLS + FP8_SYMBOLS + ROW_SYMBOLS:     # (the HIP build alone exports these)
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -244,6 +250,27 @@ class Engine(object):
         k = C.c_int32(0)
         self._check(lib().drs_table_fp8_exponent(self._h, int(t), C.byref(k)), "drs_table_fp8_exponent")
         return int(k.value)
+
+    def update_rows(self, t, ids, values):
+        """Rows `ids` (int64 [n]) of table t become `values` (fp32 [n, D]), stored as set_table would store them in the
+        tables' current type and layout (fp8: under the table's existing scale).  A repeated id takes its last row.  Drains
+        the engine first."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        values = _f32(values)
+        if ids.ndim != 1 or values.shape != (ids.size, self.D):
+            raise ValueError("ids [n] and values [n, %d]: got %r and %r" % (self.D, ids.shape, values.shape))
+        self._check(lib().drs_update_rows(self._h, int(t), ids.size, ids.ctypes.data_as(_i64p), values.ctypes.data_as(_f32p)),
+                    "drs_update_rows")
+
+    def get_rows(self, t, ids):
+        """-> fp32 [n, D]: what each of rows `ids` (int64 [n], any order, repeats allowed) of table t serves as a one-row bag."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        if ids.ndim != 1:
+            raise ValueError("ids [n]: got %r" % (ids.shape,))
+        out = np.empty((ids.size, self.D), dtype=np.float32)
+        self._check(lib().drs_get_rows(self._h, int(t), ids.size, ids.ctypes.data_as(_i64p), out.ctypes.data_as(_f32p)),
+                    "drs_get_rows")
+        return out
 
     def set_fc(self, mlp, layer, W, b):
         W, b = _f32(W), _f32(b)

@@ -383,5 +383,9 @@ hipError_t launch_fill_rows(const TableSide& dst, int64_t rows, int D, int32_t t
 hipError_t launch_absmax_rows(const TableSide& src, int64_t rows, int D, uint32_t* d_bits, hipStream_t stream);
 // n elements of type src_dtype -> dst_dtype, fp32 / fp16 / bf16 only: a whole arena in one pass
 hipError_t launch_convert_table(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, hipStream_t stream);
+// Single rows (table_rows.hip): `rows` rows of S bytes between a packed buffer (row r at r * S) and rows d_ids[r] of the table
+// whose first byte is `table` (lines_n: I8Lines::n of a line-packed rowwise table, else 0) -- into the table (distinct ids)
+// or out of it.  Only the rows' own S bytes are touched.
+hipError_t launch_move_rows(void* buf, void* table, const int64_t* d_ids, int64_t rows, int64_t S, int32_t lines_n, bool to_table, hipStream_t stream);
 
 }  // namespace drs

@@ -22,7 +22,8 @@
 // Translation units (round 6: one 3 000-line file before): engine_create.hip (device set-up, launch-form choice,
 // drs_create / drs_destroy, tables and weights), engine_arena.hip (where the table arena lives), engine_inputs.hip
 // (staging and the per-call input path), engine_dispatch.hip (a launch set: enqueue, wait, the operator-level entry
-// points), engine_options.hip (the option table, profiling read-outs).  engine_host.h: the worker pool and the
+// points), engine_options.hip (the option table, profiling read-outs), engine_rows.hip (single table rows: drs_update_rows /
+// drs_get_rows).  engine_host.h: the worker pool and the
 // launcher thread of the per-call input path.
 #pragma once
 #include <immintrin.h>

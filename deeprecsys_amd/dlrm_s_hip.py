@@ -324,6 +324,15 @@ class _HipNet(object):
                                     weights=None if lS_w is None else lS_w[j])
         self._n_staged = len(lS_l)
 
+    def update_embedding_rows(self, t, ids, values):
+        """Rows `ids` of embedding table t take `values` ([n, m_spa] fp32) in place, stored in the tables' current type
+        (FBGEMM's emb_inplace_update; Engine.update_rows): queries enqueued before the call see the old rows."""
+        self.engine.update_rows(t, ids, values)
+
+    def embedding_rows(self, t, ids):
+        """-> [n, m_spa] fp32: rows `ids` of embedding table t as the engine serves them (Engine.get_rows)."""
+        return self.engine.get_rows(t, ids)
+
     def tune_table_placement(self, candidates=12, sets=128, spacer_gb=None, policies=(1, 0), max_extra_gb=48, sharers=1):
         """Where the tables live in HBM, and with which cache policy their rows are read, moves the many-rows-per-bag
         gather by up to 9 % -- a property of the PHYSICAL memory (it follows the memory through address changes;

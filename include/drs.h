@@ -405,9 +405,11 @@ const char* drs_comm_last_error(void);
  * The declarations above are the ABI that every implementation restates (the CPU restatement under oracle/ among
  * them) and that DRS_ABI_VERSION counts.  drs_weights.h adds the per-sample-weight entry points, which libdrs_hip.so
  * alone exports; nothing above changed for them, so the version stays what it is.  drs_fp8.h likewise adds the
- * read-back of an fp8 table's scale exponent ("table_dtype" 4).                                                    */
+ * read-back of an fp8 table's scale exponent ("table_dtype" 4), drs_rows.h the update and the read-back of single
+ * table rows in whatever type the table is stored.                                                                  */
 #include "drs_weights.h"
 #include "drs_fp8.h"
+#include "drs_rows.h"
 
 #ifdef __cplusplus
 }
