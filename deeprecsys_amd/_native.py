@@ -106,6 +106,14 @@ ROW_SYMBOLS = [
     ("drs_get_rows", C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, _i64p, _f32p]),
 ]
 
+# launch sets whose per-query arrays are device arrays (include/drs_device_inputs.h) -- the HIP build alone, as above
+DEVICE_INPUT_SYMBOLS = [
+    ("drs_run_queues_device_multi_async", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _i32p, C.POINTER(C.c_void_p),
+                                                      C.POINTER(C.c_void_p), _i64p, _i64p, C.POINTER(C.c_void_p), _i64p, _i32p]),
+    ("drs_run_queues_device_async", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                                C.c_int64, C.c_void_p, C.c_int64, C.c_int32]),
+]
+
 
 class ModelCfg(C.Structure):
     _fields_ = [
@@ -152,7 +160,7 @@ def lib():
         if not backend.startswith(b"hip:"):
             raise ImportError("%s identifies itself as %r: deeprecsys_amd binds the HIP build only "
                               "(the CPU restatement of the ABI is test infrastructure)" % (LIB_PATH, backend))
-        for name, res, args in WEIGHT_SYMBOLS + FP8_SYMBOLS + ROW_SYMBOLS:     # (the HIP build alone exports these)
+        for name, res, args in WEIGHT_SYMBOLS + FP8_SYMBOLS + ROW_SYMBOLS + DEVICE_INPUT_SYMBOLS:     # (the HIP build alone exports these)
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -197,6 +205,7 @@ class Engine(object):
         self.T = int(self._rows.size)
         self.D = int(sparse_dim)
         self.max_batch = int(max_batch)
+        self.max_lookups = int(max_lookups)
         # width of a query's dense rows (drs_create's shape algebra): DLRM / W&D / MT-WnD feed ln_bot[0]
         self.m_den = int(self._ln_bot[0]) if kind in (MODEL_DLRM, MODEL_WND, MODEL_MTWND) else 0
         self.num_slots = int(num_slots)
@@ -444,6 +453,31 @@ class Engine(object):
                                                      ids_stride.ctypes.data_as(_i64p), n_idx.ctypes.data_as(_i64p),
                                                      lp, len_stride.ctypes.data_as(_i64p)),
                     "drs_run_queues_multi_async")
+
+    def run_queues_device_multi_async(self, queries, slot=0):
+        """run_queues_multi_async for arrays that live in DEVICE memory (include/drs_device_inputs.h): `queries` is a list
+        of (bs, dense_ptr, ids_ptr, ids_row_stride, n_idx_per_table, len_ptr, len_row_stride, fixed_len) -- device
+        addresses as integers (0 / None: no dense rows), strides in elements, fixed_len >= 0 the promise that every bag
+        holds that many indices or -1.  One kernel launch converts and checks the arrays; wait(slot, sum(bs)) returns the
+        outputs back to back.  The arrays must be complete now and stay untouched until wait() has returned."""
+        n = len(queries)
+        bsa = np.empty(n, dtype=np.int32)
+        ids_stride = np.empty(n, dtype=np.int64)
+        len_stride = np.empty(n, dtype=np.int64)
+        n_idx = np.empty(n, dtype=np.int64)
+        fixed = np.empty(n, dtype=np.int32)
+        dp = (C.c_void_p * max(n, 1))()
+        ip = (C.c_void_p * max(n, 1))()
+        lp = (C.c_void_p * max(n, 1))()
+        for i, (bs, dense_ptr, ids_ptr, ids_rs, ni, len_ptr, len_rs, fl) in enumerate(queries):
+            bsa[i], ids_stride[i], n_idx[i], len_stride[i], fixed[i] = bs, ids_rs, ni, len_rs, fl
+            dp[i] = dense_ptr or None
+            ip[i] = ids_ptr or None
+            lp[i] = len_ptr or None
+        self._check(lib().drs_run_queues_device_multi_async(self._h, slot, n, bsa.ctypes.data_as(_i32p), dp, ip,
+                                                            ids_stride.ctypes.data_as(_i64p), n_idx.ctypes.data_as(_i64p),
+                                                            lp, len_stride.ctypes.data_as(_i64p), fixed.ctypes.data_as(_i32p)),
+                    "drs_run_queues_device_multi_async")
 
     def fetch_interaction(self, bs, slot=0):
         R = np.empty((bs, self.num_int), dtype=np.float32)

@@ -388,4 +388,38 @@ hipError_t launch_convert_table(const void* src, int src_dtype, void* dst, int d
 // or out of it.  Only the rows' own S bytes are touched.
 hipError_t launch_move_rows(void* buf, void* table, const int64_t* d_ids, int64_t rows, int64_t S, int32_t lines_n, bool to_table, hipStream_t stream);
 
+// The per-call input pass on the device (input_pass.hip; include/drs_device_inputs.h): what convert_table does on the host
+// for a launch set whose arrays are device arrays -- ONE launch narrows every query's int64 indices into its int32 index
+// rows, turns its lengths into prefix sums and copies its dense rows.  A query's workgroups are numbered lengths first
+// (one per table), then nb_idx per table of kInPassIdx indices each, then nb_dense of kInPassDense floats each; query i
+// owns workgroups [wg0[i], wg0[i + 1]).
+constexpr int kInPassThreads = 256;
+constexpr int kInPassIdx = 2048;      // indices per narrowing workgroup: four 16-byte loads (two int64 each) per lane
+constexpr int kInPassDense = 4096;    // floats per dense-row workgroup: four float4 per lane
+constexpr uint32_t kErrIndex = 1u, kErrMlpEarly = 2u, kErrLengths = 4u;   // bits of a slot's device error word
+struct InQuery {
+  const int64_t* ids;         // [T] rows of n_idx, ids_stride elements apart (8-byte aligned, no more)
+  const int32_t* len;         // [T] rows of bs, len_stride elements apart
+  const float* dense;         // [bs * m_den], or null
+  int64_t ids_stride, len_stride;
+  int32_t* idx;               // -> Batch::idx [T][cap]
+  int32_t* off;               // -> Batch::off [T][max_batch + 1]
+  float* dst_dense;           // -> Batch::dense
+  int32_t bs, n_idx;
+  int32_t fixed_len;          // >= 0: every length must equal it | -1
+  int32_t store_off;          // the gather will read this query's prefix sums (ragged bags, or "sls_uniform" 0)
+  int32_t nb_idx, nb_dense;
+};
+struct InPassArgs {
+  int32_t n_q, T, m_den, max_batch;
+  int64_t cap;
+  const int64_t* rows;        // [T] rows of every table (device)
+  uint32_t* err;              // the slot's device error word
+  int32_t wg0[DRS_MAX_COALESCE + 1];
+  InQuery q[DRS_MAX_COALESCE];
+};
+// fills nb_idx / nb_dense / wg0 from the rest and returns the grid (0: nothing to do)
+int64_t plan_input_pass(InPassArgs& a);
+hipError_t launch_input_pass(const InPassArgs& a, int64_t grid, hipStream_t stream);
+
 }  // namespace drs

@@ -23,7 +23,8 @@
 // drs_create / drs_destroy, tables and weights), engine_arena.hip (where the table arena lives), engine_inputs.hip
 // (staging and the per-call input path), engine_dispatch.hip (a launch set: enqueue, wait, the operator-level entry
 // points), engine_options.hip (the option table, profiling read-outs), engine_rows.hip (single table rows: drs_update_rows /
-// drs_get_rows).  engine_host.h: the worker pool and the
+// drs_get_rows), engine_device_inputs.hip (launch sets whose per-query arrays are device arrays: the refusals the host can
+// make and the input-pass launch).  engine_host.h: the worker pool and the
 // launcher thread of the per-call input path.
 #pragma once
 #include <immintrin.h>
@@ -109,7 +110,7 @@ struct Slot {
   float* H2 = nullptr;       // NCF: concat(mf, mlp_out)
   float* H3 = nullptr;       // MT-WnD: output of the shared top MLP (input of every task head)
   float* d_out = nullptr;    // [max_batch*n_out] device outputs (copy path only)
-  uint32_t* d_err = nullptr; // device error word (bit0: index out of range)
+  uint32_t* d_err = nullptr; // device error word (kErrIndex: index out of range | kErrMlpEarly | kErrLengths: the device input pass's length ENFORCEs)
   uint32_t* d_counter = nullptr;  // arrival counter of the completion hand-off
   float* xbuf = nullptr;          // stream4_kernel's column-split form: exchange buffer [xrows, xcols] of the split layer's outputs ...
   uint32_t* xcnt = nullptr;       // ... and one arrival ticket per 16-row slab (zero between launches)
@@ -351,6 +352,7 @@ int32_t wait_slot(drs_engine* e, Slot& s, float* h_out, int64_t h_cap = -1);
 int32_t check_handle(drs_engine* e, bool hot = false);
 // engine_inputs.hip
 int32_t finish_inputs(drs_engine* e, Slot& s, int mode, int32_t bs, size_t used, bool need_off);
+int32_t multi_blocks(drs_engine* e, Slot& s, bool host_side);
 
 }  // namespace eng
 }  // namespace drs

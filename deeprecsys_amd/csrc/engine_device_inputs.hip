@@ -1,0 +1,144 @@
+// libdrs_hip.so, host side: launch sets whose per-query arrays are DEVICE arrays (include/drs_device_inputs.h).  The host
+// refuses what it can see (shapes, NULLs, pointers that are not device memory or run past their allocation), one launch of
+// the input pass (input_pass.hip) converts and checks the arrays into the slot's per-query HBM blocks on the stream the
+// host form puts its DMA copy on, and the set is then enqueued exactly like a host set (enqueue_forward on Slot::mq).
+#include "engine.h"
+#include "input_extent.h"
+
+namespace {
+
+// nullptr when [p, p + bytes) is plain device memory of the engine's device inside one allocation, else what is wrong
+const char* device_range_fault(const drs_engine* e, const void* p, size_t bytes) {
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof at);
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return "is not memory the HIP runtime knows";
+  }
+  if (at.type != hipMemoryTypeDevice || at.isManaged) return "is not plain device memory (host, pinned and managed memory are refused)";
+  if (at.device != e->device) return "lives on another device";
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+    (void)hipGetLastError();
+    return "has no allocation the HIP runtime knows";
+  }
+  if (!extent_inside(reinterpret_cast<uintptr_t>(p), bytes, reinterpret_cast<uintptr_t>(base), size)) return "runs past the end of its allocation";
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t drs_run_queues_device_multi_async(drs_handle e, int32_t slot, int32_t n, const int32_t* bs,
+                                          const float* const* d_dense, const int64_t* const* d_ids,
+                                          const int64_t* ids_row_stride, const int64_t* n_idx_per_table,
+                                          const int32_t* const* d_lengths, const int64_t* len_row_stride,
+                                          const int32_t* fixed_len) {
+  int32_t rc = check_handle(e);
+  if (rc) return rc;
+  if (slot < 0 || slot >= e->n_slots) return fail(e, DRS_ERR_BAD_ARG, "slot %d of %d", slot, e->n_slots);
+  if (n < 1 || n > DRS_MAX_COALESCE) return fail(e, DRS_ERR_BAD_ARG, "1..%d queries per launch", DRS_MAX_COALESCE);
+  if (!bs || !d_dense || !d_ids || !ids_row_stride || !n_idx_per_table || !d_lengths || !len_row_stride)
+    return fail(e, DRS_ERR_BAD_ARG, "bad per-query array tables");
+  const int T = e->T;
+  // everything the host can see, before anything is enqueued (a slot in flight is not even waited for)
+  int64_t Mv = 0;
+  for (int i = 0; i < n; ++i) {
+    const int32_t fl = fixed_len ? fixed_len[i] : -1;
+    const int64_t ni = n_idx_per_table[i];
+    if (bs[i] < 0 || bs[i] > e->max_batch) return fail(e, DRS_ERR_BAD_ARG, "query %d: n_samples=%d exceeds max_batch=%d", i, bs[i], e->max_batch);
+    if (ni < 0 || ni > e->cap) return fail(e, DRS_ERR_BAD_ARG, "query %d: %lld indices per table exceed staging capacity %lld", i, (long long)ni, (long long)e->cap);
+    if (fl < -1) return fail(e, DRS_ERR_BAD_ARG, "query %d: fixed_len=%d", i, fl);
+    if (ids_row_stride[i] < 0 || len_row_stride[i] < 0) return fail(e, DRS_ERR_BAD_ARG, "query %d: negative row stride", i);
+    if (bs[i] > 0 && (!d_ids[i] || !d_lengths[i])) return fail(e, DRS_ERR_BAD_ARG, "query %d: null ids / lengths", i);
+    if (bs[i] > 0 && e->m_den > 0 && !d_dense[i]) return fail(e, DRS_ERR_BAD_ARG, "query %d: null dense input", i);
+    Mv += ((int64_t)bs[i] + 63) / 64 * 64;
+  }
+  if (Mv > e->max_rows) return fail(e, DRS_ERR_BAD_ARG, "%lld coalesced rows exceed the slot capacity %lld", (long long)Mv, (long long)e->max_rows);
+  for (int i = 0; i < n; ++i) {
+    const int32_t fl = fixed_len ? fixed_len[i] : -1;
+    const int64_t ni = n_idx_per_table[i];
+    if (fl >= 0 && ni != (int64_t)bs[i] * fl)
+      return fail(e, DRS_ERR_LENGTHS_SUM, "query %d: %lld indices per table, but %d bags of the promised length %d", i, (long long)ni, bs[i], fl);
+    if (bs[i] == 0 && ni != 0)
+      return fail(e, DRS_ERR_LENGTHS_SUM, "query %d: sum(lengths)=0 != len(indices)=%lld", i, (long long)ni);
+  }
+  // the pointer check: three pointers per query, each with the extent the pass will read
+  // (an empty query's pointers are checked too where it has any: what they are is refused even when nothing is read)
+  for (int i = 0; i < n; ++i) {
+    const int64_t ni = n_idx_per_table[i];
+    uint64_t ids_bytes, len_bytes, dense_bytes;
+    if (!input_extent_bytes(T, ids_row_stride[i], ni, sizeof(int64_t), &ids_bytes) ||
+        !input_extent_bytes(T, len_row_stride[i], bs[i], sizeof(int32_t), &len_bytes) ||
+        !input_extent_bytes(1, 0, (int64_t)bs[i] * (e->m_den > 0 ? e->m_den : 0), sizeof(float), &dense_bytes))
+      return fail(e, DRS_ERR_BAD_ARG, "query %d: a row stride beyond any allocation", i);
+    const char* why;
+    if ((reinterpret_cast<uintptr_t>(d_ids[i]) & 7) || (reinterpret_cast<uintptr_t>(d_lengths[i]) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_dense[i]) & 3))
+      return fail(e, DRS_ERR_BAD_ARG, "query %d: a pointer is not aligned to its element type", i);
+    if (d_ids[i] && (why = device_range_fault(e, d_ids[i], ids_bytes))) return fail(e, DRS_ERR_BAD_ARG, "query %d: d_ids %s", i, why);
+    if (d_lengths[i] && (why = device_range_fault(e, d_lengths[i], len_bytes))) return fail(e, DRS_ERR_BAD_ARG, "query %d: d_lengths %s", i, why);
+    if (e->m_den > 0 && d_dense[i] && (why = device_range_fault(e, d_dense[i], dense_bytes)))
+      return fail(e, DRS_ERR_BAD_ARG, "query %d: d_dense %s", i, why);
+  }
+  Slot& s = e->slots[slot];
+  if (s.busy && (rc = wait_slot(e, s, nullptr))) return rc;
+  if ((rc = multi_blocks(e, s, false))) return rc;
+  if (!e->stream_h2d) HIP_TRY(e, hipStreamCreateWithFlags(&e->stream_h2d, hipStreamNonBlocking));
+
+  InPassArgs a;
+  memset(&a, 0, sizeof a);
+  a.T = T; a.m_den = e->m_den; a.max_batch = e->max_batch; a.cap = e->cap;
+  a.rows = e->d_tab_rows; a.err = s.d_err;
+  const Batch* bts[DRS_MAX_COALESCE];
+  for (int i = 0; i < n; ++i) {
+    Batch& b = s.mq[i];
+    const int32_t fl = fixed_len ? fixed_len[i] : -1;
+    b.n_samples = bs[i];
+    b.staged = true;
+    b.weighted = false;
+    b.uniform_len = bs[i] > 0 ? fl : -1;
+    for (int t = 0; t < T; ++t) b.h_off[(size_t)t * (e->max_batch + 1) + (size_t)bs[i]] = (int32_t)n_idx_per_table[i];   // (all the byte accounting reads)
+    bts[i] = &b;
+    if (bs[i] == 0) continue;
+    InQuery& q = a.q[a.n_q++];
+    q.ids = d_ids[i]; q.len = d_lengths[i]; q.dense = e->m_den > 0 ? d_dense[i] : nullptr;
+    q.ids_stride = ids_row_stride[i]; q.len_stride = len_row_stride[i];
+    q.idx = b.idx; q.off = b.off; q.dst_dense = b.dense;
+    q.bs = bs[i]; q.n_idx = (int32_t)n_idx_per_table[i];
+    q.fixed_len = fl;
+    q.store_off = !e->sls_uniform || fl < 0;     // (enqueue_forward's predicate for handing the kernels uniform_len = -1)
+  }
+  const int64_t grid = plan_input_pass(a);
+  if (grid > 0) {
+    HIP_TRY(e, launch_input_pass(a, grid, e->stream_h2d));
+    HIP_TRY(e, hipEventRecord(s.ev_in, e->stream_h2d));
+    const hipStream_t ms = job_stream(e, s, Mv), gs = job_gather_stream(e, s, Mv);
+    HIP_TRY(e, hipStreamWaitEvent(gs, s.ev_in, 0));
+    if (ms != gs) HIP_TRY(e, hipStreamWaitEvent(ms, s.ev_in, 0));   // the MLP side reads the dense rows
+  }
+  rc = enqueue_forward(e, s, n, bts, bs);
+  if (rc == DRS_OK && grid > 0 && e->dispatch_log) {
+    // the pass's own entry, in FRONT of the entries enqueue_forward has just noted for the set (it starts the record)
+    char head[64];
+    const int hl = snprintf(head, sizeof head, "input_pass[%lld x %d] ", (long long)grid, kInPassThreads);
+    DispatchLog& lg = s.dlog;
+    if (hl > 0 && lg.len + hl < (int)sizeof(lg.text)) {
+      memmove(lg.text + hl, lg.text, (size_t)lg.len + 1);
+      memcpy(lg.text, head, (size_t)hl);
+      lg.len += hl;
+    }
+  }
+  return rc;
+}
+
+int32_t drs_run_queues_device_async(drs_handle e, int32_t slot, int32_t bs, const float* d_dense, const int64_t* d_ids,
+                                    int64_t ids_row_stride, int64_t n_idx_per_table, const int32_t* d_lengths,
+                                    int64_t len_row_stride, int32_t fixed_len) {
+  return drs_run_queues_device_multi_async(e, slot, 1, &bs, &d_dense, &d_ids, &ids_row_stride, &n_idx_per_table, &d_lengths,
+                                           &len_row_stride, &fixed_len);
+}
+
+}  // extern "C"

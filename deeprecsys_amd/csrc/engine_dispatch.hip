@@ -694,7 +694,9 @@ int32_t wait_slot(drs_engine* e, Slot& s, float* h_out, int64_t h_cap) {
     s.h_out[1] = 0;
     HIP_TRY(e, hipMemsetAsync(s.d_err, 0, sizeof(uint32_t), s.stream));
     HIP_TRY(e, hipStreamSynchronize(s.stream));
-    if (bits & 2u) return fail(e, DRS_ERR_HIP, "mlp_early: the gather's flag never reached the MLP launch");
+    if (bits & kErrMlpEarly) return fail(e, DRS_ERR_HIP, "mlp_early: the gather's flag never reached the MLP launch");
+    if (bits & kErrLengths)    // (the device input pass, input_pass.hip: the device keeps one word, no position or value)
+      return fail(e, DRS_ERR_LENGTHS_SUM, "device inputs: a negative length, sum(lengths) != len(indices), or a length that differs from the promised fixed_len");
     return fail(e, DRS_ERR_INDEX_RANGE, "an embedding index was out of range on the device");
   }
   if (h_out && s.last_bs > 0) {

@@ -169,6 +169,43 @@ int32_t finish_inputs(drs_engine* e, Slot& s, int mode, int32_t bs, size_t used,
   return enqueue_forward(e, s, 1, &bt, &bs);
 }
 
+// The per-query blocks of a slot's launch sets with per-call inputs, allocated on first use: the HBM blocks (s.d_multi,
+// viewed as s.mq) and, for the host form alone (host_side), their pinned twins -- the device form
+// (engine_device_inputs.hip) never needs the pinned half.  What THIS call allocated is all there or all gone (a failed
+// second allocation must not leave a half-built slot behind: the next call would index device pointers derived from
+// null -- ADVICE r3); blocks an earlier call of the other form made stay.
+int32_t multi_blocks(drs_engine* e, Slot& s, bool host_side) {
+  const bool need_d = !s.d_multi, need_h = host_side && !s.h_multi;
+  if (!need_d && !need_h) return DRS_OK;
+  const size_t dense_bytes = sizeof(float) * (size_t)e->max_batch * (e->m_den > 0 ? e->m_den : 1);
+  const size_t idx_bytes = sizeof(int32_t) * (size_t)e->T * e->cap;
+  const size_t off_bytes = sizeof(int32_t) * (size_t)e->T * (e->max_batch + 1);
+  const size_t block = (size_t)round_up((int64_t)(dense_bytes + idx_bytes + off_bytes), 256);
+  char* h = nullptr;
+  char* d = nullptr;
+  hipError_t r = hipSuccess;
+  if (need_h) r = hipHostMalloc(reinterpret_cast<void**>(&h), block * DRS_MAX_COALESCE, hipHostMallocDefault);
+  if (r == hipSuccess && need_d) r = hipMalloc(reinterpret_cast<void**>(&d), block * DRS_MAX_COALESCE);
+  if (r != hipSuccess) {
+    if (h) (void)hipHostFree(h);
+    return fail(e, r == hipErrorOutOfMemory ? DRS_ERR_OOM : DRS_ERR_HIP, "per-call input blocks of a launch set: %s", hipGetErrorString(r));
+  }
+  s.multi_block = block;
+  if (need_h) s.h_multi = h;
+  if (need_d) {
+    s.d_multi = d;
+    s.mq.assign(DRS_MAX_COALESCE, Batch());
+    for (int i = 0; i < DRS_MAX_COALESCE; ++i) {
+      char* b = s.d_multi + (size_t)i * s.multi_block;
+      s.mq[i].dense = reinterpret_cast<float*>(b);
+      s.mq[i].idx = reinterpret_cast<int32_t*>(b + dense_bytes);
+      s.mq[i].off = reinterpret_cast<int32_t*>(b + dense_bytes + idx_bytes);
+      s.mq[i].h_off.assign((size_t)e->T * (e->max_batch + 1), 0);
+    }
+  }
+  return DRS_OK;
+}
+
 
 }  // namespace eng
 }  // namespace drs
@@ -387,26 +424,7 @@ int32_t drs_run_queues_multi_async(drs_handle e, int32_t slot, int32_t n, const 
   const size_t dense_bytes = sizeof(float) * (size_t)e->max_batch * (e->m_den > 0 ? e->m_den : 1);
   const size_t idx_bytes = sizeof(int32_t) * (size_t)e->T * e->cap;
   const size_t off_bytes = sizeof(int32_t) * (size_t)e->T * (e->max_batch + 1);
-  if (s.mq.empty()) {
-    // first use: both allocations or neither (a failed second one must not leave a half-built slot behind:
-    // the next call would index device pointers derived from null -- ADVICE r3)
-    s.multi_block = (size_t)round_up((int64_t)(dense_bytes + idx_bytes + off_bytes), 256);
-    hipError_t r1 = hipHostMalloc(reinterpret_cast<void**>(&s.h_multi), s.multi_block * DRS_MAX_COALESCE, hipHostMallocDefault);
-    hipError_t r2 = r1 == hipSuccess ? hipMalloc(reinterpret_cast<void**>(&s.d_multi), s.multi_block * DRS_MAX_COALESCE) : r1;
-    if (r2 != hipSuccess) {
-      if (r1 == hipSuccess) (void)hipHostFree(s.h_multi);
-      s.h_multi = nullptr; s.d_multi = nullptr; s.multi_block = 0;
-      return fail(e, r2 == hipErrorOutOfMemory ? DRS_ERR_OOM : DRS_ERR_HIP, "per-call input blocks of a launch set: %s", hipGetErrorString(r2));
-    }
-    s.mq.assign(DRS_MAX_COALESCE, Batch());
-    for (int i = 0; i < DRS_MAX_COALESCE; ++i) {
-      char* d = s.d_multi + (size_t)i * s.multi_block;
-      s.mq[i].dense = reinterpret_cast<float*>(d);
-      s.mq[i].idx = reinterpret_cast<int32_t*>(d + dense_bytes);
-      s.mq[i].off = reinterpret_cast<int32_t*>(d + dense_bytes + idx_bytes);
-      s.mq[i].h_off.assign((size_t)e->T * (e->max_batch + 1), 0);
-    }
-  }
+  if ((rc = multi_blocks(e, s, true))) return rc;
   if (!e->stream_h2d) HIP_TRY(e, hipStreamCreateWithFlags(&e->stream_h2d, hipStreamNonBlocking));
   // host pass: ONE fork-join over the tables (and dense rows) of every query of the set
   for (int i = 0; i < n; ++i) {

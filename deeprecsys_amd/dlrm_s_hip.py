@@ -117,6 +117,48 @@ def sls_weights(args, lS_i):
     return [[(rs.randint(0, 1 << 24, size=len(i)) * np.float32(2.0 ** -24)).astype(np.float32) for i in per] for per in lS_i]
 
 
+def device_request(request, T, m_den, device, i=0):
+    """One request of run_queued_device_multi -- (ids, lengths, fc, batch_size[, fixed_len]), torch tensors on GPU `device`
+    -- as the tuple Engine.run_queues_device_multi_async takes.  Checks everything the tensors themselves show (dtype,
+    shape, layout, then the device) and raises ValueError naming the argument; touches no engine.  m_den == 0: fc is
+    ignored, as the models without dense input ignore it."""
+    import torch
+    if len(request) not in (4, 5):
+        raise ValueError("request %d: (ids, lengths, fc, batch_size[, fixed_len])" % i)
+    ids, lengths, fc, bs = request[:4]
+    fixed_len = int(request[4]) if len(request) == 5 else -1
+    bs = int(bs)
+    if m_den == 0:
+        fc = None
+
+    def check(name, t, dtype, rows, cols):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("request %d: %s must be a torch tensor, got %s" % (i, name, type(t).__name__))
+        if t.dtype != dtype:
+            raise ValueError("request %d: %s must be %s, got %s" % (i, name, dtype, t.dtype))
+        if t.dim() != 2 or (rows is not None and t.shape[0] != rows) or (cols is not None and t.shape[1] != cols):
+            raise ValueError("request %d: %s must be [%s, %s], got %r" % (i, name, "bs" if rows is None else rows,
+                                                                           "n" if cols is None else cols, tuple(t.shape)))
+        if t.shape[1] > 1 and t.stride(1) != 1:
+            raise ValueError("request %d: the last dimension of %s must be contiguous (stride %d)" % (i, name, t.stride(1)))
+        if t.shape[0] > 1 and t.stride(0) < 0:
+            raise ValueError("request %d: %s has a negative row stride" % (i, name))
+
+    if bs < 0:
+        raise ValueError("request %d: batch_size %d" % (i, bs))
+    check("ids", ids, torch.int64, T, None)
+    check("lengths", lengths, torch.int32, T, bs)
+    if fc is not None:
+        check("fc", fc, torch.float32, bs, m_den)
+        if bs > 1 and fc.stride(0) != m_den:
+            raise ValueError("request %d: the rows of fc must be contiguous (row stride %d, width %d)" % (i, fc.stride(0), m_den))
+    for name, t in (("ids", ids), ("lengths", lengths), ("fc", fc)):
+        if t is not None and (t.device.type != "cuda" or t.device.index != device):
+            raise ValueError("request %d: %s lives on %s, the engine on cuda:%d" % (i, name, t.device, device))
+    return (bs, 0 if fc is None else fc.data_ptr(), ids.data_ptr(), ids.stride(0) if T > 1 else ids.shape[1], ids.shape[1],
+            lengths.data_ptr(), lengths.stride(0) if T > 1 else bs, fixed_len)
+
+
 def _init_table(n, m):
     # models/dlrm_s_caffe2.py:297-299
     return np.random.uniform(low=-np.sqrt(1 / n), high=np.sqrt(1 / n), size=(n, m)).astype(np.float32)
@@ -313,6 +355,32 @@ class _HipNet(object):
         self.engine.run_queues_multi_async(qs, slot=slot)
         sizes = [q[3] for q in qs]
         out = self.engine.wait(slot, sum(sizes))
+        outs = np.split(out, np.cumsum(sizes)[:-1], axis=0)
+        self._out = outs[-1]
+        return outs
+
+    def run_queued_device_multi(self, requests, slot=0):
+        """run_queued_multi for requests whose arrays are torch tensors on the engine's GPU
+        (drs_run_queues_device_multi_async): a request is (ids, lengths, fc, batch_size[, fixed_len]) with ids [T, n]
+        int64, lengths [T, bs] int32, fc [bs, m_den] float32 or None -- last dimension contiguous, row strides as the
+        tensors have them, so slices of wider tensors go down as they are.  fixed_len >= 0 promises that every bag holds
+        that many indices (default -1: the lengths are read).  No byte crosses the bus: one kernel launch narrows, scans
+        and checks the arrays.  Returns the list of [bs_i, n_out] outputs (numpy, as run_queued_multi)."""
+        import torch
+        eng = self.engine
+        qs = [device_request(r, eng.T, eng.m_den, eng.device, i) for i, r in enumerate(requests)]
+        # (torch gives an empty tensor a null data_ptr; the library takes no null ids with bs > 0, even where none is read)
+        spare = None
+        for k, q in enumerate(qs):
+            if q[0] > 0 and q[2] == 0:
+                if spare is None:
+                    spare = torch.zeros((eng.T, 1), dtype=torch.int64, device="cuda:%d" % eng.device)
+                qs[k] = q[:2] + (spare.data_ptr(), 1) + q[4:]
+        # the engine cannot order itself behind the work that produced the tensors: once per call, torch's stream
+        torch.cuda.current_stream(eng.device).synchronize()
+        eng.run_queues_device_multi_async(qs, slot=slot)
+        sizes = [q[0] for q in qs]
+        out = eng.wait(slot, sum(sizes))
         outs = np.split(out, np.cumsum(sizes)[:-1], axis=0)
         self._out = outs[-1]
         return outs
@@ -802,6 +870,10 @@ class _Wrapper(object):
     def run_queues_multi(self, requests, slot=0):
         """Several queued requests, each in run_queues' argument order, as one launch set."""
         return self.net.run_queued_multi(requests, slot=slot)
+
+    def run_queues_device_multi(self, requests, slot=0):
+        """run_queues_multi for requests whose arrays are torch tensors on the engine's GPU (_HipNet.run_queued_device_multi)."""
+        return self.net.run_queued_device_multi(requests, slot=slot)
 
 
 class DLRM_Wrapper(_Wrapper):

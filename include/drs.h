@@ -406,10 +406,13 @@ const char* drs_comm_last_error(void);
  * them) and that DRS_ABI_VERSION counts.  drs_weights.h adds the per-sample-weight entry points, which libdrs_hip.so
  * alone exports; nothing above changed for them, so the version stays what it is.  drs_fp8.h likewise adds the
  * read-back of an fp8 table's scale exponent ("table_dtype" 4), drs_rows.h the update and the read-back of single
- * table rows in whatever type the table is stored.                                                                  */
+ * table rows in whatever type the table is stored.  drs_device_inputs.h adds the form of the per-call input path whose
+ * dense rows, indices and lengths are DEVICE arrays: narrowed, prefix-summed and ENFORCE-checked by one kernel launch per
+ * set instead of on the host.                                                                                         */
 #include "drs_weights.h"
 #include "drs_fp8.h"
 #include "drs_rows.h"
+#include "drs_device_inputs.h"
 
 #ifdef __cplusplus
 }
