@@ -11,8 +11,9 @@
 //   weights  one arena: all biases back to back (layer order, padded to 4 floats), then per
 //            layer W [N, K] dense row-major (as fed by the reference)
 //   batches  per staged batch: dense [max_batch, m_den] f32 | idx [T, cap] i32 |
-//            off [T, max_batch+1] i32 (exclusive prefix sums of the lengths); wgt [T, cap] f32 once the batch has
-//            carried per-sample weights (drs_stage_batch_weights)
+//            off [T, max_batch+1] i32 (exclusive prefix sums of the lengths) -- input_block.h's BlockLayout, which every
+//            size and stride below is read from; wgt [T, cap] f32 once the batch has carried per-sample weights
+//            (drs_stage_batch_weights)
 //   slots    per in-flight launch set (up to DRS_MAX_COALESCE coalesced queries): interaction buffer(s),
 //            layer scratch, device output buffer, [flag | err | out] in host-mapped pinned
 //            memory, and a host-mapped pinned input block for per-call inputs
@@ -25,7 +26,8 @@
 // points), engine_options.hip (the option table, profiling read-outs), engine_rows.hip (single table rows: drs_update_rows /
 // drs_get_rows), engine_device_inputs.hip (launch sets whose per-query arrays are device arrays: the refusals the host can
 // make and the input-pass launch).  engine_host.h: the worker pool and the
-// launcher thread of the per-call input path.
+// launcher thread of the per-call input path.  input_block.h: the per-call input block's layout, the host pass that
+// fills one and the copies that move it (plain C++: a host program can build it alone).
 #pragma once
 #include <immintrin.h>
 #include <sched.h>
@@ -41,6 +43,7 @@
 #include <vector>
 
 #include "drs_internal.h"
+#include "input_block.h"
 
 #include <condition_variable>
 #include <functional>
@@ -83,9 +86,15 @@ struct Batch {
   bool weighted = false;       // ... and whether the staged batch carries them (drs_stage_batch drops them)
   int32_t n_samples = 0;
   int32_t uniform_len = -1;    // all bags of all tables have this length, else -1
-  std::vector<int32_t> h_off;  // [T][max_batch+1] host copy (gather_bytes, validation)
+  std::vector<int32_t> h_off;  // [T][off_stride] host copy (gather_bytes, validation): BlockLayout::h_off_at
   bool staged = false;
 };
+// a batch whose inputs are the block at `base` (a device address): zc, dc and every mq[i]
+inline void view_as(Batch& b, const BlockLayout& L, void* base) {
+  const BlockView v = view_block(L, base);
+  b.dense = v.dense; b.idx = v.idx; b.off = v.off;
+  b.h_off.assign(L.off_elems(), 0);
+}
 
 struct Slot {
   bool split_last = false;        // the set in flight read its dense columns in place ("gemm_split"): s.T holds none
@@ -143,9 +152,8 @@ struct Slot {
   // DRS_MAX_COALESCE blocks [dense | idx | off] back to back in ONE pinned allocation and their
   // twins in ONE HBM allocation, so that a set's inputs cross the bus in one DMA copy
   char* h_multi = nullptr;
-  char* d_multi = nullptr;
-  size_t multi_block = 0;    // bytes from one block to the next
-  std::vector<Batch> mq;     // block i viewed as a batch (device pointers into d_multi)
+  char* d_multi = nullptr;   // (BlockLayout::padded bytes from one block to the next)
+  std::vector<Batch> mq;    // block i viewed as a batch (device pointers into d_multi)
   int32_t launch_rc = 0;     // status of the launches the launcher thread made for the job in flight
   std::string launch_err;
   DispatchLog dlog = {{0}, 0};   // what the launch functions chose for the set last enqueued here (drs_last_dispatch)
@@ -242,6 +250,7 @@ struct drs_engine {
   int32_t m_den = 0, w0 = 0;     // dense input width, dense_out width
   int32_t num_int = 0, n_out = 0;
   int64_t ldT = 0, ldR = 0, ldH = 0, cap = 0;
+  BlockLayout blk;               // a batch's / per-call input block's [dense | idx | off] (set in drs_create before the slots are built)
   int64_t max_rows = 0;          // virtual rows of a slot's activation buffers
   std::vector<Batch> batches;
   std::vector<Slot> slots;
@@ -353,6 +362,13 @@ int32_t check_handle(drs_engine* e, bool hot = false);
 // engine_inputs.hip
 int32_t finish_inputs(drs_engine* e, Slot& s, int mode, int32_t bs, size_t used, bool need_off);
 int32_t multi_blocks(drs_engine* e, Slot& s, bool host_side);
+// what the host and the device form of a per-call launch set refuse alike (i: the query, -1: a query alone) ...
+inline int64_t padded_rows(int32_t bs) { return ((int64_t)bs + 63) / 64 * 64; }
+int32_t check_bs(drs_engine* e, int i, int32_t bs);
+int32_t check_dense(drs_engine* e, int i, const float* dense, int32_t bs);
+int32_t check_set_rows(drs_engine* e, int64_t Mv);
+// ... and how both order the set behind what fills its blocks on stream_h2d
+int32_t order_behind_inputs(drs_engine* e, Slot& s, int64_t Mv);
 
 }  // namespace eng
 }  // namespace drs

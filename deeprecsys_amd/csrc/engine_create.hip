@@ -83,9 +83,9 @@ hipError_t build_bf16_twin(Layer& L) {
 int32_t alloc_batch(drs_engine* e, Batch& b) {
   if (e->m_den > 0)
     HIP_TRY(e, hipMalloc(&b.dense, sizeof(float) * (size_t)e->max_batch * e->m_den));
-  HIP_TRY(e, hipMalloc(&b.idx, sizeof(int32_t) * (size_t)e->T * e->cap));
-  HIP_TRY(e, hipMalloc(&b.off, sizeof(int32_t) * (size_t)e->T * (e->max_batch + 1)));
-  b.h_off.assign((size_t)e->T * (e->max_batch + 1), 0);
+  HIP_TRY(e, hipMalloc(&b.idx, e->blk.idx_bytes));
+  HIP_TRY(e, hipMalloc(&b.off, e->blk.off_bytes));
+  b.h_off.assign(e->blk.off_elems(), 0);
   return DRS_OK;
 }
 
@@ -414,6 +414,7 @@ int32_t drs_create(const drs_model_cfg* cfg, int32_t device_id, drs_handle* out)
   CREATE_TRY(upload_fp8_scales(e));
 
   e->cap = (int64_t)e->max_batch * e->max_lookups;
+  e->blk = BlockLayout(e->max_batch, e->m_den, T, e->cap);
   e->max_rows = (int64_t)DRS_MAX_COALESCE * ((e->max_batch + 63) / 64 * 64);
   e->ldT = e->kind == DRS_MODEL_NCF ? 4 * D : e->w0 + (int64_t)T * D;   // (DIN: w0 == 0)
   e->ldR = round_up(e->num_int, 4);
@@ -478,26 +479,16 @@ int32_t drs_create(const drs_model_cfg* cfg, int32_t device_id, drs_handle* out)
     for (auto& ev : s.ev_k) CREATE_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventDisableSystemFence));
     if (alloc_batch(e, s.scratch)) return bail(DRS_ERR_OOM, e->err.c_str());
     s.scratch.n_samples = 0;
-    s.h_stage_bytes = sizeof(float) * (size_t)e->max_batch * (e->m_den > 0 ? e->m_den : 1) +
-                      sizeof(int32_t) * (size_t)T * e->cap +
-                      sizeof(int32_t) * (size_t)T * (e->max_batch + 1);
+    s.h_stage_bytes = e->blk.bytes;
     CREATE_TRY(hipHostMalloc(&s.h_stage, s.h_stage_bytes, hipHostMallocMapped));
     {
       // device view of the same block, laid out like a staged batch: [dense | idx | off]
       char* dm = nullptr;
       CREATE_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&dm), s.h_stage, 0));
-      const size_t dense_bytes = sizeof(float) * (size_t)e->max_batch * (e->m_den > 0 ? e->m_den : 1);
-      const size_t idx_bytes = sizeof(int32_t) * (size_t)T * e->cap;
-      s.zc.dense = reinterpret_cast<float*>(dm);
-      s.zc.idx = reinterpret_cast<int32_t*>(dm + dense_bytes);
-      s.zc.off = reinterpret_cast<int32_t*>(dm + dense_bytes + idx_bytes);
-      s.zc.h_off.assign((size_t)T * (e->max_batch + 1), 0);
+      view_as(s.zc, e->blk, dm);
       // the same layout once more in HBM: target of the one-copy input path
       CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&s.d_stage), s.h_stage_bytes));
-      s.dc.dense = reinterpret_cast<float*>(s.d_stage);
-      s.dc.idx = reinterpret_cast<int32_t*>(s.d_stage + dense_bytes);
-      s.dc.off = reinterpret_cast<int32_t*>(s.d_stage + dense_bytes + idx_bytes);
-      s.dc.h_off.assign((size_t)T * (e->max_batch + 1), 0);
+      view_as(s.dc, e->blk, s.d_stage);
     }
   }
   CREATE_TRY(hipStreamCreateWithFlags(&e->stream_g, hipStreamNonBlocking));

@@ -48,15 +48,15 @@ int32_t drs_run_queues_device_multi_async(drs_handle e, int32_t slot, int32_t n,
   for (int i = 0; i < n; ++i) {
     const int32_t fl = fixed_len ? fixed_len[i] : -1;
     const int64_t ni = n_idx_per_table[i];
-    if (bs[i] < 0 || bs[i] > e->max_batch) return fail(e, DRS_ERR_BAD_ARG, "query %d: n_samples=%d exceeds max_batch=%d", i, bs[i], e->max_batch);
+    if ((rc = check_bs(e, i, bs[i]))) return rc;
     if (ni < 0 || ni > e->cap) return fail(e, DRS_ERR_BAD_ARG, "query %d: %lld indices per table exceed staging capacity %lld", i, (long long)ni, (long long)e->cap);
     if (fl < -1) return fail(e, DRS_ERR_BAD_ARG, "query %d: fixed_len=%d", i, fl);
     if (ids_row_stride[i] < 0 || len_row_stride[i] < 0) return fail(e, DRS_ERR_BAD_ARG, "query %d: negative row stride", i);
     if (bs[i] > 0 && (!d_ids[i] || !d_lengths[i])) return fail(e, DRS_ERR_BAD_ARG, "query %d: null ids / lengths", i);
-    if (bs[i] > 0 && e->m_den > 0 && !d_dense[i]) return fail(e, DRS_ERR_BAD_ARG, "query %d: null dense input", i);
-    Mv += ((int64_t)bs[i] + 63) / 64 * 64;
+    if ((rc = check_dense(e, i, d_dense[i], bs[i]))) return rc;
+    Mv += padded_rows(bs[i]);
   }
-  if (Mv > e->max_rows) return fail(e, DRS_ERR_BAD_ARG, "%lld coalesced rows exceed the slot capacity %lld", (long long)Mv, (long long)e->max_rows);
+  if ((rc = check_set_rows(e, Mv))) return rc;
   for (int i = 0; i < n; ++i) {
     const int32_t fl = fixed_len ? fixed_len[i] : -1;
     const int64_t ni = n_idx_per_table[i];
@@ -100,7 +100,7 @@ int32_t drs_run_queues_device_multi_async(drs_handle e, int32_t slot, int32_t n,
     b.staged = true;
     b.weighted = false;
     b.uniform_len = bs[i] > 0 ? fl : -1;
-    for (int t = 0; t < T; ++t) b.h_off[(size_t)t * (e->max_batch + 1) + (size_t)bs[i]] = (int32_t)n_idx_per_table[i];   // (all the byte accounting reads)
+    for (int t = 0; t < T; ++t) b.h_off[e->blk.h_off_at(t, bs[i])] = (int32_t)n_idx_per_table[i];   // (all the byte accounting reads)
     bts[i] = &b;
     if (bs[i] == 0) continue;
     InQuery& q = a.q[a.n_q++];
@@ -114,10 +114,7 @@ int32_t drs_run_queues_device_multi_async(drs_handle e, int32_t slot, int32_t n,
   const int64_t grid = plan_input_pass(a);
   if (grid > 0) {
     HIP_TRY(e, launch_input_pass(a, grid, e->stream_h2d));
-    HIP_TRY(e, hipEventRecord(s.ev_in, e->stream_h2d));
-    const hipStream_t ms = job_stream(e, s, Mv), gs = job_gather_stream(e, s, Mv);
-    HIP_TRY(e, hipStreamWaitEvent(gs, s.ev_in, 0));
-    if (ms != gs) HIP_TRY(e, hipStreamWaitEvent(ms, s.ev_in, 0));   // the MLP side reads the dense rows
+    if ((rc = order_behind_inputs(e, s, Mv))) return rc;
   }
   rc = enqueue_forward(e, s, n, bts, bs);
   if (rc == DRS_OK && grid > 0 && e->dispatch_log) {

@@ -311,7 +311,7 @@ static int32_t launch_gather(SetCtx& x) {
     a.wgt[i] = x.qb[i]->weighted ? x.qb[i]->wgt : nullptr;   // (staged batches only: the per-call input paths carry no weights)
     a.uniform_len[i] = e->sls_uniform ? x.qb[i]->uniform_len : -1;
   }
-  a.idx_stride = e->cap; a.off_stride = e->max_batch + 1;
+  a.idx_stride = e->blk.cap; a.off_stride = (int64_t)e->blk.off_stride();
   a.out = s.T; a.ld_out = e->ldT; a.col0 = e->kind == DRS_MODEL_NCF ? 0 : e->w0;
   a.T = e->T; a.D = e->D; a.err = reinterpret_cast<int32_t*>(s.d_err);
   a.ts = prof ? s.d_ts : nullptr;
@@ -333,7 +333,7 @@ static int32_t launch_gather(SetCtx& x) {
     int64_t bytes = 0;
     for (int i = 0; i < q.n_q; ++i)
       for (int t = 0; t < e->T; ++t)
-        bytes += (int64_t)x.qb[i]->h_off[(size_t)t * (e->max_batch + 1) + q.bs[i]] * (table_row_bytes(e->table_dtype, e->D) + 4 + (x.qb[i]->weighted ? 4 : 0)) +
+        bytes += (int64_t)x.qb[i]->h_off[e->blk.h_off_at(t, q.bs[i])] * (table_row_bytes(e->table_dtype, e->D) + 4 + (x.qb[i]->weighted ? 4 : 0)) +
                  (int64_t)q.bs[i] * (4 + (int64_t)e->D * 4);
     // (the fused DIN launch writes the 4 D floats of the top MLP's input row per sample instead
     // of T pooled vectors)

@@ -1,5 +1,6 @@
-// The two helper threads of the per-call input path (engine_inputs.hip): the conversion worker pool and the
-// launcher thread.  Included at the end of engine.h: drs_engine owns one of each through unique_ptr.
+// The two helper threads of the per-call input path (engine_inputs.hip): the conversion worker pool, which runs the work
+// items of the host pass (input_block.h's convert_table per table, the dense rows), and the launcher thread, which makes a
+// converted query's HIP calls.  Included at the end of engine.h: drs_engine owns one of each through unique_ptr.
 #pragma once
 
 namespace drs {

@@ -629,7 +629,7 @@ int32_t drs_gather_bytes(drs_handle e, int32_t batch_id, int32_t bs, int64_t* by
   if (bs < 0 || bs > b.n_samples) return fail(e, DRS_ERR_BAD_ARG, "bs out of range");
   int64_t total = 0;
   for (int t = 0; t < e->T; ++t) {
-    const int64_t n = b.h_off[(size_t)t * (e->max_batch + 1) + bs];
+    const int64_t n = b.h_off[e->blk.h_off_at(t, bs)];
     // (a batch that carries weights reads 4 more bytes per looked-up row)
     total += n * (table_row_bytes(e->table_dtype, e->D) + 4 + (b.weighted ? 4 : 0)) + (int64_t)bs * (4 + (int64_t)e->D * 4);
   }
