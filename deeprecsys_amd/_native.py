@@ -114,6 +114,13 @@ DEVICE_INPUT_SYMBOLS = [
                                                 C.c_int64, C.c_void_p, C.c_int64, C.c_int32]),
 ]
 
+# ... and whose results stay on the device, ordered on a stream of the caller's (include/drs_device_outputs.h) -- the HIP build alone
+DEVICE_OUTPUT_SYMBOLS = [
+    ("drs_run_queues_device_io_multi_async", C.c_int32, DEVICE_INPUT_SYMBOLS[0][2] + [C.POINTER(C.c_void_p), _i64p, C.c_void_p,
+                                                                                     C.c_int32]),
+    ("drs_run_queues_device_io_async", C.c_int32, DEVICE_INPUT_SYMBOLS[1][2] + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
+]
+
 
 class ModelCfg(C.Structure):
     _fields_ = [
@@ -160,7 +167,7 @@ def lib():
         if not backend.startswith(b"hip:"):
             raise ImportError("%s identifies itself as %r: deeprecsys_amd binds the HIP build only "
                               "(the CPU restatement of the ABI is test infrastructure)" % (LIB_PATH, backend))
-        for name, res, args in WEIGHT_SYMBOLS + FP8_SYMBOLS + ROW_SYMBOLS + DEVICE_INPUT_SYMBOLS:     # (the HIP build alone exports these)
+        for name, res, args in WEIGHT_SYMBOLS + FP8_SYMBOLS + ROW_SYMBOLS + DEVICE_INPUT_SYMBOLS + DEVICE_OUTPUT_SYMBOLS:     # (the HIP build alone exports these)
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -460,6 +467,12 @@ class Engine(object):
         addresses as integers (0 / None: no dense rows), strides in elements, fixed_len >= 0 the promise that every bag
         holds that many indices or -1.  One kernel launch converts and checks the arrays; wait(slot, sum(bs)) returns the
         outputs back to back.  The arrays must be complete now and stay untouched until wait() has returned."""
+        self._check(lib().drs_run_queues_device_multi_async(self._h, slot, *self._device_set(queries)[0]),
+                    "drs_run_queues_device_multi_async")
+
+    @staticmethod
+    def _device_set(queries):
+        """the tuples of run_queues_device_multi_async -> (the call's arguments from n on, the arrays they point into)"""
         n = len(queries)
         bsa = np.empty(n, dtype=np.int32)
         ids_stride = np.empty(n, dtype=np.int64)
@@ -474,10 +487,29 @@ class Engine(object):
             dp[i] = dense_ptr or None
             ip[i] = ids_ptr or None
             lp[i] = len_ptr or None
-        self._check(lib().drs_run_queues_device_multi_async(self._h, slot, n, bsa.ctypes.data_as(_i32p), dp, ip,
-                                                            ids_stride.ctypes.data_as(_i64p), n_idx.ctypes.data_as(_i64p),
-                                                            lp, len_stride.ctypes.data_as(_i64p), fixed.ctypes.data_as(_i32p)),
-                    "drs_run_queues_device_multi_async")
+        keep = (bsa, ids_stride, n_idx, len_stride, fixed)
+        return [n, bsa.ctypes.data_as(_i32p), dp, ip, ids_stride.ctypes.data_as(_i64p), n_idx.ctypes.data_as(_i64p), lp,
+                len_stride.ctypes.data_as(_i64p), fixed.ctypes.data_as(_i32p)], keep
+
+    def run_queues_device_io_multi_async(self, queries, outs, stream=None, slot=0):
+        """run_queues_device_multi_async whose results stay in DEVICE memory (include/drs_device_outputs.h): `outs` is a list
+        of (ptr, row_stride), one per query -- query i's [bs, n_out] fp32 scores go to the device address ptr, rows
+        row_stride floats apart (0 / None: no output, an empty query's).  stream None: `ordered` 0 -- the inputs are complete
+        now and the outputs are when wait(slot) has returned.  stream an integer hipStream_t handle (0 is the null stream):
+        `ordered` 1 -- the set runs behind what is enqueued on that stream, and what is enqueued there after this call sees
+        the outputs; nothing waits on the host.  Inputs and outputs must stay alive and untouched until wait(slot)."""
+        if len(outs) != len(queries):
+            raise ValueError("%d queries, %d outputs" % (len(queries), len(outs)))
+        args, keep = self._device_set(queries)
+        n = len(outs)
+        op = (C.c_void_p * max(n, 1))()
+        out_stride = np.empty(n, dtype=np.int64)
+        for i, (ptr, rs) in enumerate(outs):
+            op[i] = ptr or None
+            out_stride[i] = rs
+        self._check(lib().drs_run_queues_device_io_multi_async(self._h, slot, *(args + [
+            op, out_stride.ctypes.data_as(_i64p), None if stream is None else (int(stream) or None), 0 if stream is None else 1])),
+            "drs_run_queues_device_io_multi_async")
 
     def fetch_interaction(self, bs, slot=0):
         R = np.empty((bs, self.num_int), dtype=np.float32)

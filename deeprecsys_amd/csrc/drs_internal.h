@@ -422,4 +422,10 @@ struct InPassArgs {
 int64_t plan_input_pass(InPassArgs& a);
 hipError_t launch_input_pass(const InPassArgs& a, int64_t grid, hipStream_t stream);
 
+// The output pass on the device (output_pass.hip; include/drs_device_outputs.h), its mirror: ONE launch moves every query's
+// scores from the slot's device buffer to the caller's device arrays.  OutPassArgs, its planner and the owner lookup are
+// plain C++ (output_plan.h).
+struct OutPassArgs;
+hipError_t launch_output_pass(const OutPassArgs& a, int64_t grid, hipStream_t stream);
+
 }  // namespace drs

@@ -25,7 +25,8 @@
 // (staging and the per-call input path), engine_dispatch.hip (a launch set: enqueue, wait, the operator-level entry
 // points), engine_options.hip (the option table, profiling read-outs), engine_rows.hip (single table rows: drs_update_rows /
 // drs_get_rows), engine_device_inputs.hip (launch sets whose per-query arrays are device arrays: the refusals the host can
-// make and the input-pass launch).  engine_host.h: the worker pool and the
+// make and the input-pass launch), engine_device_outputs.hip (the same sets with their results left in device arrays of the
+// caller's: the output-pass launch and the event edges to the caller's stream).  engine_host.h: the worker pool and the
 // launcher thread of the per-call input path.  input_block.h: the per-call input block's layout, the host pass that
 // fills one and the copies that move it (plain C++: a host program can build it alone).
 #pragma once
@@ -111,6 +112,10 @@ struct Slot {
   hipEvent_t ev_dma = nullptr;           // "out_dma": last kernel done -> the copy stream may take the outputs
   bool on_dma = false;                   // ... the job in flight hands over through the copy stream
   hipEvent_t ev_in = nullptr;            // pipelined mode: per-call inputs copied -> the gather may start
+  // device outputs (engine_device_outputs.hip): the caller's stream has reached the call -> the input pass may start; the
+  // output pass has finished -> the caller's stream may go on, and wait_slot may hand the slot (and its d_out) to the next set
+  hipEvent_t ev_caller = nullptr, ev_out = nullptr;
+  bool out_pass = false;                 // ... the set in flight has an output pass behind its last kernel (enqueue_forward resets it)
   Batch zc;                              // per-call inputs read in place from host-mapped pinned memory
   float* T = nullptr;        // [max_batch, ldT]  concat buffer: dense_out | emb_0 | ...
   float* R = nullptr;        // [max_batch, ldR]  dot-interaction output (dot only)
@@ -369,6 +374,27 @@ int32_t check_dense(drs_engine* e, int i, const float* dense, int32_t bs);
 int32_t check_set_rows(drs_engine* e, int64_t Mv);
 // ... and how both order the set behind what fills its blocks on stream_h2d
 int32_t order_behind_inputs(drs_engine* e, Slot& s, int64_t Mv);
+// engine_device_inputs.hip: a launch set whose per-query arrays are device arrays, shared by drs_run_queues_device_multi_async
+// and the device-output form (engine_device_outputs.hip) -- everything the host can refuse (nothing enqueued, a slot in
+// flight not even waited for) ...
+struct DeviceSet {
+  int32_t n;
+  const int32_t* bs;
+  const float* const* d_dense;
+  const int64_t* const* d_ids;
+  const int64_t* ids_row_stride;
+  const int64_t* n_idx_per_table;
+  const int32_t* const* d_lengths;
+  const int64_t* len_row_stride;
+  const int32_t* fixed_len;
+};
+int32_t check_device_set(drs_engine* e, int32_t slot, const DeviceSet& d, int64_t* Mv);
+// ... and the set itself: the input pass, the launches, the dispatch log's head.  behind != nullptr: the input pass is first
+// ordered behind everything enqueued on *behind so far (an event of the slot's recorded there; a set of no samples
+// launches nothing and adds no edge)
+int32_t enqueue_device_set(drs_engine* e, int32_t slot, const DeviceSet& d, int64_t Mv, const hipStream_t* behind);
+// nullptr when [p, p + bytes) is plain device memory of the engine's device inside one allocation, else what is wrong
+const char* device_range_fault(const drs_engine* e, const void* p, size_t bytes);
 
 }  // namespace eng
 }  // namespace drs

@@ -477,6 +477,10 @@ int32_t drs_create(const drs_model_cfg* cfg, int32_t device_id, drs_handle* out)
     CREATE_TRY(hipEventCreateWithFlags(&s.ev_dma, hipEventDisableTiming | hipEventDisableSystemFence));
     CREATE_TRY(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming | hipEventDisableSystemFence));
     for (auto& ev : s.ev_k) CREATE_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventDisableSystemFence));
+    // the two edges to a caller's stream (device outputs): what the caller runs on either side, copies included, is not
+    // the engine's to know, so these keep the default fence
+    CREATE_TRY(hipEventCreateWithFlags(&s.ev_caller, hipEventDisableTiming));
+    CREATE_TRY(hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
     if (alloc_batch(e, s.scratch)) return bail(DRS_ERR_OOM, e->err.c_str());
     s.scratch.n_samples = 0;
     s.h_stage_bytes = e->blk.bytes;
@@ -542,6 +546,8 @@ int32_t drs_destroy(drs_handle e) {
     if (s.ev_sls) (void)hipEventDestroy(s.ev_sls);
     if (s.ev_dma) (void)hipEventDestroy(s.ev_dma);
     if (s.ev_in) (void)hipEventDestroy(s.ev_in);
+    if (s.ev_caller) (void)hipEventDestroy(s.ev_caller);
+    if (s.ev_out) (void)hipEventDestroy(s.ev_out);
     for (auto& ev : s.ev_k) if (ev) (void)hipEventDestroy(ev);
     if (s.T) (void)hipFree(s.T);
     if (s.R) (void)hipFree(s.R);

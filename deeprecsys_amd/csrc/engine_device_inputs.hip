@@ -2,12 +2,14 @@
 // refuses what it can see (shapes, NULLs, pointers that are not device memory or run past their allocation), one launch of
 // the input pass (input_pass.hip) converts and checks the arrays into the slot's per-query HBM blocks on the stream the
 // host form puts its DMA copy on, and the set is then enqueued exactly like a host set (enqueue_forward on Slot::mq).
+// The two steps are functions of their own (check_device_set, enqueue_device_set): the form that also leaves its results
+// on the device (engine_device_outputs.hip) puts its own refusals between them and its output pass behind them.
 #include "engine.h"
 #include "input_extent.h"
 
-namespace {
+namespace drs {
+namespace eng {
 
-// nullptr when [p, p + bytes) is plain device memory of the engine's device inside one allocation, else what is wrong
 const char* device_range_fault(const drs_engine* e, const void* p, size_t bytes) {
   hipPointerAttribute_t at;
   memset(&at, 0, sizeof at);
@@ -27,15 +29,14 @@ const char* device_range_fault(const drs_engine* e, const void* p, size_t bytes)
   return nullptr;
 }
 
-}  // namespace
-
-extern "C" {
-
-int32_t drs_run_queues_device_multi_async(drs_handle e, int32_t slot, int32_t n, const int32_t* bs,
-                                          const float* const* d_dense, const int64_t* const* d_ids,
-                                          const int64_t* ids_row_stride, const int64_t* n_idx_per_table,
-                                          const int32_t* const* d_lengths, const int64_t* len_row_stride,
-                                          const int32_t* fixed_len) {
+int32_t check_device_set(drs_engine* e, int32_t slot, const DeviceSet& d, int64_t* Mv_out) {
+  const int32_t n = d.n;
+  const int32_t* bs = d.bs;
+  const float* const* d_dense = d.d_dense;
+  const int64_t* const* d_ids = d.d_ids;
+  const int32_t* const* d_lengths = d.d_lengths;
+  const int64_t *ids_row_stride = d.ids_row_stride, *n_idx_per_table = d.n_idx_per_table, *len_row_stride = d.len_row_stride;
+  const int32_t* fixed_len = d.fixed_len;
   int32_t rc = check_handle(e);
   if (rc) return rc;
   if (slot < 0 || slot >= e->n_slots) return fail(e, DRS_ERR_BAD_ARG, "slot %d of %d", slot, e->n_slots);
@@ -83,6 +84,15 @@ int32_t drs_run_queues_device_multi_async(drs_handle e, int32_t slot, int32_t n,
     if (e->m_den > 0 && d_dense[i] && (why = device_range_fault(e, d_dense[i], dense_bytes)))
       return fail(e, DRS_ERR_BAD_ARG, "query %d: d_dense %s", i, why);
   }
+  *Mv_out = Mv;
+  return DRS_OK;
+}
+
+int32_t enqueue_device_set(drs_engine* e, int32_t slot, const DeviceSet& d, int64_t Mv, const hipStream_t* behind) {
+  const int32_t n = d.n;
+  const int32_t *bs = d.bs, *fixed_len = d.fixed_len;
+  const int T = e->T;
+  int32_t rc;
   Slot& s = e->slots[slot];
   if (s.busy && (rc = wait_slot(e, s, nullptr))) return rc;
   if ((rc = multi_blocks(e, s, false))) return rc;
@@ -100,19 +110,24 @@ int32_t drs_run_queues_device_multi_async(drs_handle e, int32_t slot, int32_t n,
     b.staged = true;
     b.weighted = false;
     b.uniform_len = bs[i] > 0 ? fl : -1;
-    for (int t = 0; t < T; ++t) b.h_off[e->blk.h_off_at(t, bs[i])] = (int32_t)n_idx_per_table[i];   // (all the byte accounting reads)
+    for (int t = 0; t < T; ++t) b.h_off[e->blk.h_off_at(t, bs[i])] = (int32_t)d.n_idx_per_table[i];   // (all the byte accounting reads)
     bts[i] = &b;
     if (bs[i] == 0) continue;
     InQuery& q = a.q[a.n_q++];
-    q.ids = d_ids[i]; q.len = d_lengths[i]; q.dense = e->m_den > 0 ? d_dense[i] : nullptr;
-    q.ids_stride = ids_row_stride[i]; q.len_stride = len_row_stride[i];
+    q.ids = d.d_ids[i]; q.len = d.d_lengths[i]; q.dense = e->m_den > 0 ? d.d_dense[i] : nullptr;
+    q.ids_stride = d.ids_row_stride[i]; q.len_stride = d.len_row_stride[i];
     q.idx = b.idx; q.off = b.off; q.dst_dense = b.dense;
-    q.bs = bs[i]; q.n_idx = (int32_t)n_idx_per_table[i];
+    q.bs = bs[i]; q.n_idx = (int32_t)d.n_idx_per_table[i];
     q.fixed_len = fl;
     q.store_off = !e->sls_uniform || fl < 0;     // (enqueue_forward's predicate for handing the kernels uniform_len = -1)
   }
   const int64_t grid = plan_input_pass(a);
   if (grid > 0) {
+    if (behind) {
+      // the engine's streams are non-blocking: the edge from the caller's stream (the null stream too) is an event
+      HIP_TRY(e, hipEventRecord(s.ev_caller, *behind));
+      HIP_TRY(e, hipStreamWaitEvent(e->stream_h2d, s.ev_caller, 0));
+    }
     HIP_TRY(e, launch_input_pass(a, grid, e->stream_h2d));
     if ((rc = order_behind_inputs(e, s, Mv))) return rc;
   }
@@ -129,6 +144,22 @@ int32_t drs_run_queues_device_multi_async(drs_handle e, int32_t slot, int32_t n,
     }
   }
   return rc;
+}
+
+}  // namespace eng
+}  // namespace drs
+
+extern "C" {
+
+int32_t drs_run_queues_device_multi_async(drs_handle e, int32_t slot, int32_t n, const int32_t* bs,
+                                          const float* const* d_dense, const int64_t* const* d_ids,
+                                          const int64_t* ids_row_stride, const int64_t* n_idx_per_table,
+                                          const int32_t* const* d_lengths, const int64_t* len_row_stride,
+                                          const int32_t* fixed_len) {
+  const DeviceSet d = {n, bs, d_dense, d_ids, ids_row_stride, n_idx_per_table, d_lengths, len_row_stride, fixed_len};
+  int64_t Mv = 0;
+  const int32_t rc = check_device_set(e, slot, d, &Mv);
+  return rc ? rc : enqueue_device_set(e, slot, d, Mv, nullptr);
 }
 
 int32_t drs_run_queues_device_async(drs_handle e, int32_t slot, int32_t bs, const float* d_dense, const int64_t* d_ids,

@@ -591,6 +591,7 @@ int32_t enqueue_forward(drs_engine* e, Slot& s, int n, const Batch* const* bts, 
   s.last_bs = x.c;
   s.busy = true;
   s.polled = false;
+  s.out_pass = false;            // (engine_device_outputs.hip sets it behind this call, for its own sets alone)
   if (x.c == 0) return DRS_OK;
   // Pipelined mode, small launch set (a single query: 256 rows = 16 MLP workgroups on a 256-CU
   // chip): its latency-bound MLP launch goes on the SLOT's own stream, so the MLP launches of
@@ -661,6 +662,12 @@ int32_t wait_slot(drs_engine* e, Slot& s, float* h_out, int64_t h_cap) {
     std::atomic_thread_fence(std::memory_order_acquire);
   } else {
     HIP_TRY(e, hipStreamSynchronize(s.stream));
+  }
+  if (s.out_pass) {
+    // device outputs: the flag above is published by the set's last MLP kernel, BEFORE the output pass behind it reads
+    // s.d_out and the error word -- and the next set on this slot may launch on another stream (job_stream goes by Mv)
+    s.out_pass = false;
+    HIP_TRY(e, hipEventSynchronize(s.ev_out));
   }
   s.busy = false;
   if (s.ev_pending) {

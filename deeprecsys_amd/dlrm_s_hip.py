@@ -159,6 +159,27 @@ def device_request(request, T, m_den, device, i=0):
             lengths.data_ptr(), lengths.stride(0) if T > 1 else bs, fixed_len)
 
 
+def device_out(t, bs, n_out, device, i=0):
+    """One output of run_queued_device_io_multi -- a torch fp32 tensor [bs, n_out] on GPU `device`, last dimension contiguous,
+    rows any non-negative stride apart (a column block of a wider tensor goes down as it is) -- as the (ptr, row_stride)
+    Engine.run_queues_device_io_multi_async takes.  Checks what the tensor itself shows (dtype, shape, layout, then the
+    device) and raises ValueError naming the argument; touches no engine."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("out %d: must be a torch tensor, got %s" % (i, type(t).__name__))
+    if t.dtype != torch.float32:
+        raise ValueError("out %d: must be %s, got %s" % (i, torch.float32, t.dtype))
+    if t.dim() != 2 or t.shape[0] != bs or t.shape[1] != n_out:
+        raise ValueError("out %d: must be [%d, %d], got %r" % (i, bs, n_out, tuple(t.shape)))
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        raise ValueError("out %d: the last dimension must be contiguous (stride %d)" % (i, t.stride(1)))
+    if t.shape[0] > 1 and t.stride(0) < 0:
+        raise ValueError("out %d: a negative row stride" % i)
+    if t.device.type != "cuda" or t.device.index != device:
+        raise ValueError("out %d: lives on %s, the engine on cuda:%d" % (i, t.device, device))
+    return (t.data_ptr() if bs > 0 else 0, t.stride(0) if bs > 1 else n_out)
+
+
 def _init_table(n, m):
     # models/dlrm_s_caffe2.py:297-299
     return np.random.uniform(low=-np.sqrt(1 / n), high=np.sqrt(1 / n), size=(n, m)).astype(np.float32)
@@ -368,14 +389,7 @@ class _HipNet(object):
         and checks the arrays.  Returns the list of [bs_i, n_out] outputs (numpy, as run_queued_multi)."""
         import torch
         eng = self.engine
-        qs = [device_request(r, eng.T, eng.m_den, eng.device, i) for i, r in enumerate(requests)]
-        # (torch gives an empty tensor a null data_ptr; the library takes no null ids with bs > 0, even where none is read)
-        spare = None
-        for k, q in enumerate(qs):
-            if q[0] > 0 and q[2] == 0:
-                if spare is None:
-                    spare = torch.zeros((eng.T, 1), dtype=torch.int64, device="cuda:%d" % eng.device)
-                qs[k] = q[:2] + (spare.data_ptr(), 1) + q[4:]
+        qs, spare = self._device_queries(requests)
         # the engine cannot order itself behind the work that produced the tensors: once per call, torch's stream
         torch.cuda.current_stream(eng.device).synchronize()
         eng.run_queues_device_multi_async(qs, slot=slot)
@@ -384,6 +398,56 @@ class _HipNet(object):
         outs = np.split(out, np.cumsum(sizes)[:-1], axis=0)
         self._out = outs[-1]
         return outs
+
+    def _device_queries(self, requests):
+        """requests of torch tensors -> (the tuples Engine.run_queues_device_multi_async takes, a tensor to keep alive or None)"""
+        import torch
+        eng = self.engine
+        qs = [device_request(r, eng.T, eng.m_den, eng.device, i) for i, r in enumerate(requests)]
+        # (torch gives an empty tensor a null data_ptr; the library takes no null ids with bs > 0, even where none is read)
+        spare = None
+        for k, q in enumerate(qs):
+            if q[0] > 0 and q[2] == 0:
+                if spare is None:
+                    spare = torch.zeros((eng.T, 1), dtype=torch.int64, device="cuda:%d" % eng.device)
+                qs[k] = q[:2] + (spare.data_ptr(), 1) + q[4:]
+        return qs, spare
+
+    def run_queued_device_io_multi(self, requests, out=None, stream=None, slot=0):
+        """run_queued_device_multi whose results stay on the GPU (drs_run_queues_device_io_multi_async, `ordered` 1): returns
+        at once the list of [bs_i, n_out] float32 torch tensors the scores go to -- `out`, one tensor per request (column
+        blocks of wider tensors are fine), or freshly allocated ones.  The set runs behind what is enqueued on `stream` (a
+        torch.cuda.Stream or a raw handle; default: torch's current stream of the engine's GPU) and work enqueued there
+        after this call sees the scores; nothing synchronises on the host.  A set that failed on the device holds NaN in
+        every element.  The request and output tensors are kept referenced until the next wait on the slot -- torch's
+        caching allocator does not know the engine's streams -- so call finish_device(slot) (the set's completion and its
+        status) before tensors handed in here are overwritten by anything not ordered on `stream`."""
+        import torch
+        eng = self.engine
+        n_out, device = eng.n_out, eng.device
+        if out is not None and len(out) != len(requests):
+            raise ValueError("%d requests, %d output tensors" % (len(requests), len(out)))
+        qs, spare = self._device_queries(requests)
+        if out is None:
+            out = [torch.empty((q[0], n_out), dtype=torch.float32, device="cuda:%d" % device) for q in qs]
+        outs_arg = [device_out(t, q[0], n_out, device, i) for i, (t, q) in enumerate(zip(out, qs))]
+        if stream is None:
+            stream = torch.cuda.current_stream(device)
+        handle = stream.cuda_stream if isinstance(stream, torch.cuda.Stream) else int(stream)
+        eng.run_queues_device_io_multi_async(qs, outs_arg, stream=handle, slot=slot)     # (waits first for a set still on the slot)
+        refs = getattr(self, "_device_refs", None)
+        if refs is None:
+            refs = self._device_refs = {}
+        refs[slot] = (list(requests), list(out), spare)
+        return list(out)
+
+    def finish_device(self, slot=0):
+        """The completion of the set run_queued_device_io_multi put on `slot`: returns once its outputs are written, drops the
+        references held for it, and raises DrsError for a set that failed on the device (its outputs are NaN)."""
+        try:
+            self.engine.wait(slot)
+        finally:
+            getattr(self, "_device_refs", {}).pop(slot, None)
 
     def stage_batches(self, lX, lS_l, lS_i, lS_w=None):
         """lS_w: per-index weights of every input set (sls_weights), or None."""
@@ -874,6 +938,14 @@ class _Wrapper(object):
     def run_queues_device_multi(self, requests, slot=0):
         """run_queues_multi for requests whose arrays are torch tensors on the engine's GPU (_HipNet.run_queued_device_multi)."""
         return self.net.run_queued_device_multi(requests, slot=slot)
+
+    def run_queues_device_io_multi(self, requests, out=None, stream=None, slot=0):
+        """run_queues_device_multi whose results stay on the GPU, ordered on a torch stream: returns the list of [bs_i, n_out]
+        device tensors at once (_HipNet.run_queued_device_io_multi); finish_device(slot) is the set's completion."""
+        return self.net.run_queued_device_io_multi(requests, out=out, stream=stream, slot=slot)
+
+    def finish_device(self, slot=0):
+        return self.net.finish_device(slot=slot)
 
 
 class DLRM_Wrapper(_Wrapper):
