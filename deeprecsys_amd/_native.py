@@ -121,6 +121,14 @@ DEVICE_OUTPUT_SYMBOLS = [
     ("drs_run_queues_device_io_async", C.c_int32, DEVICE_INPUT_SYMBOLS[1][2] + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
 ]
 
+# ... and both forms with per-sample weights as device arrays (include/drs_device_weights.h) -- the HIP build alone
+DEVICE_WEIGHT_SYMBOLS = [
+    ("drs_run_queues_device_weighted_multi_async", C.c_int32, DEVICE_INPUT_SYMBOLS[0][2] + [
+        C.POINTER(C.c_void_p), _i64p, _i32p, C.POINTER(C.c_void_p), _i64p, C.c_void_p, C.c_int32]),
+]
+# the codes of a weight array's element type (wgt_dtype: the DRS_TABLE_* codes of the three float types)
+WEIGHT_FP32, WEIGHT_FP16, WEIGHT_BF16 = 0, 1, 2
+
 
 class ModelCfg(C.Structure):
     _fields_ = [
@@ -167,7 +175,8 @@ def lib():
         if not backend.startswith(b"hip:"):
             raise ImportError("%s identifies itself as %r: deeprecsys_amd binds the HIP build only "
                               "(the CPU restatement of the ABI is test infrastructure)" % (LIB_PATH, backend))
-        for name, res, args in WEIGHT_SYMBOLS + FP8_SYMBOLS + ROW_SYMBOLS + DEVICE_INPUT_SYMBOLS + DEVICE_OUTPUT_SYMBOLS:     # (the HIP build alone exports these)
+        for name, res, args in (WEIGHT_SYMBOLS + FP8_SYMBOLS + ROW_SYMBOLS + DEVICE_INPUT_SYMBOLS + DEVICE_OUTPUT_SYMBOLS +
+                                DEVICE_WEIGHT_SYMBOLS):     # (the HIP build alone exports these)
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -461,14 +470,41 @@ class Engine(object):
                                                      lp, len_stride.ctypes.data_as(_i64p)),
                     "drs_run_queues_multi_async")
 
-    def run_queues_device_multi_async(self, queries, slot=0):
+    def run_queues_device_multi_async(self, queries, slot=0, weights=None):
         """run_queues_multi_async for arrays that live in DEVICE memory (include/drs_device_inputs.h): `queries` is a list
         of (bs, dense_ptr, ids_ptr, ids_row_stride, n_idx_per_table, len_ptr, len_row_stride, fixed_len) -- device
         addresses as integers (0 / None: no dense rows), strides in elements, fixed_len >= 0 the promise that every bag
         holds that many indices or -1.  One kernel launch converts and checks the arrays; wait(slot, sum(bs)) returns the
-        outputs back to back.  The arrays must be complete now and stay untouched until wait() has returned."""
+        outputs back to back.  The arrays must be complete now and stay untouched until wait() has returned.
+        weights: None, or one entry per query (include/drs_device_weights.h) -- (ptr, row_stride, dtype): the query's
+        per-sample weights [T, n_idx_per_table] at that device address, rows row_stride elements apart, dtype WEIGHT_FP32 /
+        WEIGHT_FP16 / WEIGHT_BF16; or None: the query is unweighted."""
+        if weights is not None:
+            args, keep = self._device_set(queries)
+            wargs, wkeep = self._device_weights(len(queries), weights)
+            self._check(lib().drs_run_queues_device_weighted_multi_async(self._h, slot, *(args + wargs + [None, None, None, 0])),
+                        "drs_run_queues_device_weighted_multi_async")
+            del keep, wkeep
+            return
         self._check(lib().drs_run_queues_device_multi_async(self._h, slot, *self._device_set(queries)[0]),
                     "drs_run_queues_device_multi_async")
+
+    @staticmethod
+    def _device_weights(n, weights):
+        """the `weights` of run_queues_device_multi_async -> (d_weights, wgt_row_stride, wgt_dtype of the call, the arrays
+        they point into)"""
+        if len(weights) != n:
+            raise ValueError("%d queries, %d weight entries" % (n, len(weights)))
+        wp = (C.c_void_p * max(n, 1))()
+        stride = np.zeros(max(n, 1), dtype=np.int64)
+        dtype = np.zeros(max(n, 1), dtype=np.int32)
+        for i, w in enumerate(weights):
+            if w is None:
+                continue
+            ptr, rs, dt = w
+            wp[i] = ptr or None
+            stride[i], dtype[i] = rs, dt
+        return [wp, stride.ctypes.data_as(_i64p), dtype.ctypes.data_as(_i32p)], (stride, dtype)
 
     @staticmethod
     def _device_set(queries):
@@ -491,13 +527,14 @@ class Engine(object):
         return [n, bsa.ctypes.data_as(_i32p), dp, ip, ids_stride.ctypes.data_as(_i64p), n_idx.ctypes.data_as(_i64p), lp,
                 len_stride.ctypes.data_as(_i64p), fixed.ctypes.data_as(_i32p)], keep
 
-    def run_queues_device_io_multi_async(self, queries, outs, stream=None, slot=0):
+    def run_queues_device_io_multi_async(self, queries, outs, stream=None, slot=0, weights=None):
         """run_queues_device_multi_async whose results stay in DEVICE memory (include/drs_device_outputs.h): `outs` is a list
         of (ptr, row_stride), one per query -- query i's [bs, n_out] fp32 scores go to the device address ptr, rows
         row_stride floats apart (0 / None: no output, an empty query's).  stream None: `ordered` 0 -- the inputs are complete
         now and the outputs are when wait(slot) has returned.  stream an integer hipStream_t handle (0 is the null stream):
         `ordered` 1 -- the set runs behind what is enqueued on that stream, and what is enqueued there after this call sees
-        the outputs; nothing waits on the host.  Inputs and outputs must stay alive and untouched until wait(slot)."""
+        the outputs; nothing waits on the host.  Inputs and outputs must stay alive and untouched until wait(slot).
+        weights: as in run_queues_device_multi_async."""
         if len(outs) != len(queries):
             raise ValueError("%d queries, %d outputs" % (len(queries), len(outs)))
         args, keep = self._device_set(queries)
@@ -507,6 +544,13 @@ class Engine(object):
         for i, (ptr, rs) in enumerate(outs):
             op[i] = ptr or None
             out_stride[i] = rs
+        if weights is not None:
+            wargs, wkeep = self._device_weights(len(queries), weights)
+            self._check(lib().drs_run_queues_device_weighted_multi_async(self._h, slot, *(args + wargs + [
+                op, out_stride.ctypes.data_as(_i64p), None if stream is None else (int(stream) or None), 0 if stream is None else 1])),
+                "drs_run_queues_device_weighted_multi_async")
+            del wkeep
+            return
         self._check(lib().drs_run_queues_device_io_multi_async(self._h, slot, *(args + [
             op, out_stride.ctypes.data_as(_i64p), None if stream is None else (int(stream) or None), 0 if stream is None else 1])),
             "drs_run_queues_device_io_multi_async")

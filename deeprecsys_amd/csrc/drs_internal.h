@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/drs.h"
+#include "weight_plan.h"
 
 namespace drs {
 
@@ -421,6 +422,25 @@ struct InPassArgs {
 // fills nb_idx / nb_dense / wg0 from the rest and returns the grid (0: nothing to do)
 int64_t plan_input_pass(InPassArgs& a);
 hipError_t launch_input_pass(const InPassArgs& a, int64_t grid, hipStream_t stream);
+
+// The same pass for a set in which at least one query carries per-sample weights (include/drs_device_weights.h): a second
+// instance of the kernel with a fourth kind of work item, kInPassWgt weights of one (query, table) row copied or widened into
+// the query's [T, cap] fp32 weight block.  A query's weight workgroups are numbered behind its dense ones (weight_plan.h),
+// so the other three kinds keep their numbers.  A set without weights launches input_pass_kernel as before.
+struct InWgt {
+  const void* src;            // [T] rows of n_idx weights of `dtype`, `stride` elements apart (aligned to the element, no more); null: unweighted
+  int64_t stride;
+  float* dst;                 // -> Batch::wgt [T][cap]
+  int32_t dtype;              // DRS_TABLE_FP32 | DRS_TABLE_FP16 | DRS_TABLE_BF16
+  int32_t nb_wgt;
+};
+struct InPassWgtArgs {
+  InPassArgs in;
+  InWgt w[DRS_MAX_COALESCE];  // entry i belongs to in.q[i]
+};
+// fills nb_idx / nb_dense / nb_wgt / wg0 from the rest and returns the grid (0: nothing to do; -1: beyond 32-bit block numbers)
+int64_t plan_input_pass_weighted(InPassWgtArgs& a);
+hipError_t launch_input_pass_weighted(const InPassWgtArgs& a, int64_t grid, hipStream_t stream);
 
 // The output pass on the device (output_pass.hip; include/drs_device_outputs.h), its mirror: ONE launch moves every query's
 // scores from the slot's device buffer to the caller's device arrays.  OutPassArgs, its planner and the owner lookup are

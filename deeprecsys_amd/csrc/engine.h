@@ -28,7 +28,8 @@
 // make and the input-pass launch), engine_device_outputs.hip (the same sets with their results left in device arrays of the
 // caller's: the output-pass launch and the event edges to the caller's stream).  engine_host.h: the worker pool and the
 // launcher thread of the per-call input path.  input_block.h: the per-call input block's layout, the host pass that
-// fills one and the copies that move it (plain C++: a host program can build it alone).
+// fills one and the copies that move it (plain C++: a host program can build it alone).  weight_plan.h: the plan of the
+// per-sample weights a device set may carry (include/drs_device_weights.h), plain C++ likewise.
 #pragma once
 #include <immintrin.h>
 #include <sched.h>
@@ -159,6 +160,10 @@ struct Slot {
   char* h_multi = nullptr;
   char* d_multi = nullptr;   // (BlockLayout::padded bytes from one block to the next)
   std::vector<Batch> mq;    // block i viewed as a batch (device pointers into d_multi)
+  // per-sample weights of a device set (drs_run_queues_device_weighted_multi_async): DRS_MAX_COALESCE blocks of [T, cap]
+  // fp32 in ONE allocation, made when the slot first sees a weighted set and kept until drs_destroy; mq[i].wgt points at
+  // block i while mq[i].weighted, which every path that fills mq sets or clears
+  float* d_wgt = nullptr;
   int32_t launch_rc = 0;     // status of the launches the launcher thread made for the job in flight
   std::string launch_err;
   DispatchLog dlog = {{0}, 0};   // what the launch functions chose for the set last enqueued here (drs_last_dispatch)
@@ -387,6 +392,14 @@ struct DeviceSet {
   const int32_t* const* d_lengths;
   const int64_t* len_row_stride;
   const int32_t* fixed_len;
+  // per-sample weights (include/drs_device_weights.h), read only where `weights_call`: d_weights and wgt_row_stride tables
+  // of n entries (null tables are refused); a null d_weights[i]: query i is unweighted; a null wgt_dtype: fp32 throughout
+  const void* const* d_weights;
+  const int64_t* wgt_row_stride;
+  const int32_t* wgt_dtype;
+  bool weights_call;          // the call is drs_run_queues_device_weighted_multi_async (false: the calls that carry none)
+  const void* weights_of(int i) const { return weights_call ? d_weights[i] : nullptr; }
+  int32_t weight_type(int i) const { return wgt_dtype ? wgt_dtype[i] : (int32_t)DRS_TABLE_FP32; }
 };
 int32_t check_device_set(drs_engine* e, int32_t slot, const DeviceSet& d, int64_t* Mv);
 // ... and the set itself: the input pass, the launches, the dispatch log's head.  behind != nullptr: the input pass is first

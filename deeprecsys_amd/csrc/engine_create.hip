@@ -537,6 +537,7 @@ int32_t drs_destroy(drs_handle e) {
     DTR("slot");
     if (s.h_multi) (void)hipHostFree(s.h_multi);
     if (s.d_multi) (void)hipFree(s.d_multi);
+    if (s.d_wgt) (void)hipFree(s.d_wgt);
     s.mq.clear();
     DTR("multi freed");
     if (s.own_stream) { (void)hipStreamSynchronize(s.own_stream); (void)hipStreamDestroy(s.own_stream); }

@@ -6,6 +6,7 @@
 // on the device (engine_device_outputs.hip) puts its own refusals between them and its output pass behind them.
 #include "engine.h"
 #include "input_extent.h"
+#include "weight_plan.h"
 
 namespace drs {
 namespace eng {
@@ -84,7 +85,43 @@ int32_t check_device_set(drs_engine* e, int32_t slot, const DeviceSet& d, int64_
     if (e->m_den > 0 && d_dense[i] && (why = device_range_fault(e, d_dense[i], dense_bytes)))
       return fail(e, DRS_ERR_BAD_ARG, "query %d: d_dense %s", i, why);
   }
+  // per-sample weights (include/drs_device_weights.h): one more array per weighted query, checked like the others
+  if (d.weights_call) {
+    if (!d.d_weights || !d.wgt_row_stride) return fail(e, DRS_ERR_BAD_ARG, "bad per-query weight tables");
+    for (int i = 0; i < n; ++i) {
+      const void* w = d.d_weights[i];
+      if (!w) continue;
+      if (e->kind == DRS_MODEL_DIN || e->kind == DRS_MODEL_DIEN)
+        return fail(e, DRS_ERR_UNSUPPORTED, "drs_run_queues_device_weighted_multi_async: DIN and DIEN pool their bags by the plain sum only");
+      if (e->sls_pool)
+        return fail(e, DRS_ERR_UNSUPPORTED, "drs_run_queues_device_weighted_multi_async: \"sls_pool\" 1 has no weighted form (there is no weighted mean)");
+      const int32_t ty = d.weight_type(i);
+      if (ty != DRS_TABLE_FP32 && ty != DRS_TABLE_FP16 && ty != DRS_TABLE_BF16)
+        return fail(e, DRS_ERR_BAD_ARG, "query %d: wgt_dtype=%d: 0 (fp32), 1 (fp16) or 2 (bf16)", i, ty);
+      const int64_t elem = ty == DRS_TABLE_FP32 ? 4 : 2;
+      if (d.wgt_row_stride[i] < 0) return fail(e, DRS_ERR_BAD_ARG, "query %d: negative weight row stride", i);
+      uint64_t wgt_bytes;
+      if (!weight_extent_bytes(T, d.wgt_row_stride[i], n_idx_per_table[i], elem, &wgt_bytes))
+        return fail(e, DRS_ERR_BAD_ARG, "query %d: a weight row stride beyond any allocation", i);
+      if (reinterpret_cast<uintptr_t>(w) & (uintptr_t)(elem - 1))
+        return fail(e, DRS_ERR_BAD_ARG, "query %d: d_weights is not aligned to its element type", i);
+      const char* why = device_range_fault(e, w, wgt_bytes);
+      if (why) return fail(e, DRS_ERR_BAD_ARG, "query %d: d_weights %s", i, why);
+    }
+  }
   *Mv_out = Mv;
+  return DRS_OK;
+}
+
+// the slot's weight blocks, allocated when it first sees a weighted set (an engine that never sees weights allocates nothing)
+static int32_t weight_blocks(drs_engine* e, Slot& s) {
+  if (s.d_wgt) return DRS_OK;
+  const hipError_t r = hipMalloc(reinterpret_cast<void**>(&s.d_wgt), sizeof(float) * e->blk.idx_elems() * DRS_MAX_COALESCE);
+  if (r != hipSuccess) {
+    s.d_wgt = nullptr;
+    (void)hipGetLastError();
+    return fail(e, r == hipErrorOutOfMemory ? DRS_ERR_OOM : DRS_ERR_HIP, "per-sample weight blocks of a launch set: %s", hipGetErrorString(r));
+  }
   return DRS_OK;
 }
 
@@ -96,10 +133,17 @@ int32_t enqueue_device_set(drs_engine* e, int32_t slot, const DeviceSet& d, int6
   Slot& s = e->slots[slot];
   if (s.busy && (rc = wait_slot(e, s, nullptr))) return rc;
   if ((rc = multi_blocks(e, s, false))) return rc;
+  bool any_w = false, pass_w = false;   // a query carries weights: the slot's weight blocks; a non-empty one: the weighted instance of the pass
+  for (int i = 0; i < n; ++i) {
+    any_w |= d.weights_of(i) != nullptr;
+    pass_w |= bs[i] > 0 && d.weights_of(i) != nullptr;
+  }
+  if (any_w && (rc = weight_blocks(e, s))) return rc;
   if (!e->stream_h2d) HIP_TRY(e, hipStreamCreateWithFlags(&e->stream_h2d, hipStreamNonBlocking));
 
-  InPassArgs a;
-  memset(&a, 0, sizeof a);
+  InPassWgtArgs aw;
+  memset(&aw, 0, sizeof aw);
+  InPassArgs& a = aw.in;
   a.T = T; a.m_den = e->m_den; a.max_batch = e->max_batch; a.cap = e->cap;
   a.rows = e->d_tab_rows; a.err = s.d_err;
   const Batch* bts[DRS_MAX_COALESCE];
@@ -108,7 +152,11 @@ int32_t enqueue_device_set(drs_engine* e, int32_t slot, const DeviceSet& d, int6
     const int32_t fl = fixed_len ? fixed_len[i] : -1;
     b.n_samples = bs[i];
     b.staged = true;
-    b.weighted = false;
+    // a query's weights go to block i of the slot's weight storage, laid out like its index rows; enqueue_forward then plans
+    // the set as it plans a set of staged batches of which the same ones carry weights
+    const void* w = d.weights_of(i);
+    b.weighted = w != nullptr;
+    b.wgt = w ? s.d_wgt + (size_t)i * e->blk.idx_elems() : nullptr;
     b.uniform_len = bs[i] > 0 ? fl : -1;
     for (int t = 0; t < T; ++t) b.h_off[e->blk.h_off_at(t, bs[i])] = (int32_t)d.n_idx_per_table[i];   // (all the byte accounting reads)
     bts[i] = &b;
@@ -120,22 +168,28 @@ int32_t enqueue_device_set(drs_engine* e, int32_t slot, const DeviceSet& d, int6
     q.bs = bs[i]; q.n_idx = (int32_t)d.n_idx_per_table[i];
     q.fixed_len = fl;
     q.store_off = !e->sls_uniform || fl < 0;     // (enqueue_forward's predicate for handing the kernels uniform_len = -1)
+    if (w) {
+      InWgt& iw = aw.w[a.n_q - 1];
+      iw.src = w; iw.stride = d.wgt_row_stride[i]; iw.dst = b.wgt; iw.dtype = d.weight_type(i);
+    }
   }
-  const int64_t grid = plan_input_pass(a);
+  const int64_t grid = pass_w ? plan_input_pass_weighted(aw) : plan_input_pass(a);
+  if (grid < 0) return fail(e, DRS_ERR_BAD_ARG, "the set's inputs do not fit one input pass");
   if (grid > 0) {
     if (behind) {
       // the engine's streams are non-blocking: the edge from the caller's stream (the null stream too) is an event
       HIP_TRY(e, hipEventRecord(s.ev_caller, *behind));
       HIP_TRY(e, hipStreamWaitEvent(e->stream_h2d, s.ev_caller, 0));
     }
-    HIP_TRY(e, launch_input_pass(a, grid, e->stream_h2d));
+    if (pass_w) HIP_TRY(e, launch_input_pass_weighted(aw, grid, e->stream_h2d));
+    else HIP_TRY(e, launch_input_pass(a, grid, e->stream_h2d));
     if ((rc = order_behind_inputs(e, s, Mv))) return rc;
   }
   rc = enqueue_forward(e, s, n, bts, bs);
   if (rc == DRS_OK && grid > 0 && e->dispatch_log) {
     // the pass's own entry, in FRONT of the entries enqueue_forward has just noted for the set (it starts the record)
     char head[64];
-    const int hl = snprintf(head, sizeof head, "input_pass[%lld x %d] ", (long long)grid, kInPassThreads);
+    const int hl = snprintf(head, sizeof head, "input_pass[%lld x %d%s] ", (long long)grid, kInPassThreads, pass_w ? ",w" : "");
     DispatchLog& lg = s.dlog;
     if (hl > 0 && lg.len + hl < (int)sizeof(lg.text)) {
       memmove(lg.text + hl, lg.text, (size_t)lg.len + 1);

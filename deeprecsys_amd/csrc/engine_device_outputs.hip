@@ -6,18 +6,16 @@
 #include "engine.h"
 #include "output_plan.h"
 
-extern "C" {
+namespace drs {
+namespace eng {
 
-int32_t drs_run_queues_device_io_multi_async(drs_handle e, int32_t slot, int32_t n, const int32_t* bs,
-                                             const float* const* d_dense, const int64_t* const* d_ids,
-                                             const int64_t* ids_row_stride, const int64_t* n_idx_per_table,
-                                             const int32_t* const* d_lengths, const int64_t* len_row_stride,
-                                             const int32_t* fixed_len, float* const* d_out, const int64_t* out_row_stride,
-                                             void* stream, int32_t ordered) {
-  const DeviceSet d = {n, bs, d_dense, d_ids, ids_row_stride, n_idx_per_table, d_lengths, len_row_stride, fixed_len};
-  int64_t Mv = 0;
-  int32_t rc = check_device_set(e, slot, d, &Mv);
-  if (rc) return rc;
+// the device set `d` (checked: Mv is check_device_set's) with its results left in d_out -- shared by
+// drs_run_queues_device_io_multi_async and the form of it that carries per-sample weights
+static int32_t device_io_set(drs_engine* e, int32_t slot, const DeviceSet& d, int64_t Mv, float* const* d_out,
+                             const int64_t* out_row_stride, void* stream, int32_t ordered) {
+  const int32_t n = d.n;
+  const int32_t* bs = d.bs;
+  int32_t rc;
   // what the host can see of the outputs, before anything is enqueued (a slot in flight is not even waited for)
   if (ordered != 0 && ordered != 1) return fail(e, DRS_ERR_BAD_ARG, "ordered=%d: 0 (complete inputs, drs_wait) or 1 (both ends on the stream)", ordered);
   if (!d_out || !out_row_stride) return fail(e, DRS_ERR_BAD_ARG, "bad per-query output tables");
@@ -58,6 +56,41 @@ int32_t drs_run_queues_device_io_multi_async(drs_handle e, int32_t slot, int32_t
   if (ordered) HIP_TRY(e, hipStreamWaitEvent(caller, s.ev_out, 0));
   if (e->dispatch_log) log_launch(&s.dlog, "output_pass[%lld x %d]", (long long)grid, kOutPassThreads);
   return DRS_OK;
+}
+
+}  // namespace eng
+}  // namespace drs
+
+extern "C" {
+
+int32_t drs_run_queues_device_io_multi_async(drs_handle e, int32_t slot, int32_t n, const int32_t* bs,
+                                             const float* const* d_dense, const int64_t* const* d_ids,
+                                             const int64_t* ids_row_stride, const int64_t* n_idx_per_table,
+                                             const int32_t* const* d_lengths, const int64_t* len_row_stride,
+                                             const int32_t* fixed_len, float* const* d_out, const int64_t* out_row_stride,
+                                             void* stream, int32_t ordered) {
+  const DeviceSet d = {n, bs, d_dense, d_ids, ids_row_stride, n_idx_per_table, d_lengths, len_row_stride, fixed_len};
+  int64_t Mv = 0;
+  const int32_t rc = check_device_set(e, slot, d, &Mv);
+  return rc ? rc : device_io_set(e, slot, d, Mv, d_out, out_row_stride, stream, ordered);
+}
+
+// both forms with per-sample weights (include/drs_device_weights.h): d_out == NULL is the host-output form
+int32_t drs_run_queues_device_weighted_multi_async(drs_handle e, int32_t slot, int32_t n, const int32_t* bs,
+                                                   const float* const* d_dense, const int64_t* const* d_ids,
+                                                   const int64_t* ids_row_stride, const int64_t* n_idx_per_table,
+                                                   const int32_t* const* d_lengths, const int64_t* len_row_stride,
+                                                   const int32_t* fixed_len, const void* const* d_weights,
+                                                   const int64_t* wgt_row_stride, const int32_t* wgt_dtype, float* const* d_out,
+                                                   const int64_t* out_row_stride, void* stream, int32_t ordered) {
+  const DeviceSet d = {n, bs, d_dense, d_ids, ids_row_stride, n_idx_per_table, d_lengths, len_row_stride, fixed_len,
+                       d_weights, wgt_row_stride, wgt_dtype, true};
+  int64_t Mv = 0;
+  const int32_t rc = check_device_set(e, slot, d, &Mv);
+  if (rc) return rc;
+  if (d_out) return device_io_set(e, slot, d, Mv, d_out, out_row_stride, stream, ordered);
+  if (ordered != 0) return fail(e, DRS_ERR_BAD_ARG, "ordered=%d without d_out: the host-output form takes complete inputs (ordered 0)", ordered);
+  return enqueue_device_set(e, slot, d, Mv, nullptr);
 }
 
 int32_t drs_run_queues_device_io_async(drs_handle e, int32_t slot, int32_t bs, const float* d_dense, const int64_t* d_ids,

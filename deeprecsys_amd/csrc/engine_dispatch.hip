@@ -308,7 +308,7 @@ static int32_t launch_gather(SetCtx& x) {
   for (int i = 0; i < q.n_q; ++i) {
     a.idx[i] = x.qb[i]->idx;
     a.off[i] = x.qb[i]->off;
-    a.wgt[i] = x.qb[i]->weighted ? x.qb[i]->wgt : nullptr;   // (staged batches only: the per-call input paths carry no weights)
+    a.wgt[i] = x.qb[i]->weighted ? x.qb[i]->wgt : nullptr;   // (staged batches, and device sets that carry weights: drs_device_weights.h; the host per-call paths carry none)
     a.uniform_len[i] = e->sls_uniform ? x.qb[i]->uniform_len : -1;
   }
   a.idx_stride = e->blk.cap; a.off_stride = (int64_t)e->blk.off_stride();

@@ -365,6 +365,7 @@ int32_t drs_run_queues_multi_async(drs_handle e, int32_t slot, int32_t n, const 
   bool need_off[DRS_MAX_COALESCE];
   for (int i = 0; i < n; ++i) {
     Batch& b = s.mq[i];
+    b.weighted = false;       // (the slot's last set may have been a device set with per-sample weights: the host arrays carry none)
     if ((rc = seal_query(e, b, qs[i], res.data() + (size_t)i * T, i))) {
       for (int k = 0; k < n; ++k) { s.mq[k].staged = false; s.mq[k].n_samples = 0; }
       return rc;

@@ -157,6 +157,102 @@ __device__ __forceinline__ void dense_item(const float* __restrict__ src, float*
   }
 }
 
+// ---- per-sample weights (include/drs_device_weights.h): a set in which a query carries them launches the weighted instance
+// of the pass instead -- the three kinds of item above under the same numbers, and the weights' rows copied or widened to
+// fp32 behind them (weight_plan.h, which drs_internal.h includes: chunks, peels, the numbering)
+static_assert(kInPassWgtQueries == DRS_MAX_COALESCE, "weight_plan.h restates DRS_MAX_COALESCE");
+
+// one stored weight -> fp32, exactly: fp16 through v_cvt_f32_f16, bf16 by its 16-bit shift
+template <int kType>
+__device__ __forceinline__ float widen_weight(uint32_t bits) {
+  if (kType == DRS_TABLE_FP16) return (float)__builtin_bit_cast(_Float16, (unsigned short)bits);
+  if (kType == DRS_TABLE_BF16) return __uint_as_float(bits << 16);
+  return __uint_as_float(bits);
+}
+
+// chunk c of one (query, table) row of per-sample weights, copied (fp32) or widened (fp16, bf16) into the query's fp32
+// weight row.  The source is aligned to its element only (a column slice, an odd row stride): wgt_peel (weight_plan.h)
+// names the elements in front of its first 16-byte line and behind its last whole one -- at most 3 (fp32) or 7 (half) each,
+// moved one per lane by chunk 0 -- and every chunk moves its share of the 16-byte vectors between them: all its loads in
+// flight, then the stores (16-byte ones where the destination row, t * cap floats in and `head` further, allows them).
+// Reads stay inside the row's n elements, writes inside the row's n floats; the weights are data and nothing is checked.
+template <int kType>
+__device__ __forceinline__ void weights_item(const InWgt& w, int64_t cap, int64_t n, int t, int c) {
+  constexpr int kElem = kType == DRS_TABLE_FP32 ? 4 : 2;
+  constexpr int kPer = 16 / kElem;                                   // elements per 16-byte load
+  constexpr int kLoads = kInPassWgt / kPer / kInPassThreads;         // ... and loads per lane: 4 (fp32), 2 (half)
+  static_assert(kLoads * kPer * kInPassThreads == kInPassWgt && kLoads >= 2, "whole 16-byte loads, several per lane");
+  const char* src = static_cast<const char*>(w.src) + (int64_t)t * w.stride * kElem;
+  float* dst = w.dst + (int64_t)t * cap;
+  const WgtPeel p = wgt_peel(reinterpret_cast<uintptr_t>(src), kElem, n);
+  const int tid = (int)threadIdx.x;
+  auto one = [&](int64_t j) {
+    const uint32_t bits = kElem == 4 ? reinterpret_cast<const uint32_t*>(src)[j] : (uint32_t)reinterpret_cast<const uint16_t*>(src)[j];
+    dst[j] = widen_weight<kType>(bits);
+  };
+  if (c == 0) {
+    if (tid < p.head) one(tid);
+    if (tid >= 64 && tid - 64 < p.tail) one(n - p.tail + (tid - 64));
+  }
+  const uint4* s4 = reinterpret_cast<const uint4*>(src + (int64_t)p.head * kElem);
+  float* d = dst + p.head;
+  const bool packed = (reinterpret_cast<uintptr_t>(d) & 15) == 0;
+  const int64_t v0 = wgt_vec0(c, kElem);
+  uint4 v[kLoads];
+#pragma unroll
+  for (int k = 0; k < kLoads; ++k) {
+    const int64_t i = v0 + k * kInPassThreads + tid;
+    v[k] = i < p.nvec ? s4[i] : make_uint4(0, 0, 0, 0);
+  }
+#pragma unroll
+  for (int k = 0; k < kLoads; ++k) {
+    const int64_t i = v0 + k * kInPassThreads + tid;
+    if (i >= p.nvec) continue;
+    float f[kPer];
+    const uint32_t u[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if constexpr (kElem == 4) {
+        f[j] = widen_weight<kType>(u[j]);
+      } else {
+        f[2 * j] = widen_weight<kType>(u[j] & 0xffffu);
+        f[2 * j + 1] = widen_weight<kType>(u[j] >> 16);
+      }
+    }
+    float* o = d + i * kPer;
+    if (packed) {
+#pragma unroll
+      for (int j = 0; j < kPer; j += 4) *reinterpret_cast<float4*>(o + j) = make_float4(f[j], f[j + 1], f[j + 2], f[j + 3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < kPer; ++j) o[j] = f[j];
+    }
+  }
+}
+
+// the weighted instance: input_pass_kernel's three kinds of item under their numbers, and behind a query's dense workgroups
+// nb_wgt per table of kInPassWgt weights each
+__global__ __launch_bounds__(kInPassThreads) void input_pass_weighted_kernel(const InPassWgtArgs aw) {
+  const InPassArgs& a = aw.in;
+  const int wg = (int)blockIdx.x;
+  int qi = 0;
+  for (int i = 1; i < a.n_q; ++i) qi = wg >= a.wg0[i] ? i : qi;
+  const InQuery& q = a.q[qi];
+  int r = wg - a.wg0[qi];
+  if (r < a.T) { lengths_item(a, q, r); return; }
+  r -= a.T;
+  if (r < a.T * q.nb_idx) { narrow_item(a, q, r / q.nb_idx, r % q.nb_idx); return; }
+  r -= a.T * q.nb_idx;
+  if (r < q.nb_dense) { dense_item(q.dense, q.dst_dense, (int64_t)q.bs * a.m_den, r); return; }
+  r -= q.nb_dense;
+  const InWgt& w = aw.w[qi];
+  if (r >= a.T * w.nb_wgt) return;
+  const int t = r / w.nb_wgt, c = r % w.nb_wgt;
+  if (w.dtype == DRS_TABLE_FP32) weights_item<DRS_TABLE_FP32>(w, a.cap, q.n_idx, t, c);
+  else if (w.dtype == DRS_TABLE_FP16) weights_item<DRS_TABLE_FP16>(w, a.cap, q.n_idx, t, c);
+  else weights_item<DRS_TABLE_BF16>(w, a.cap, q.n_idx, t, c);
+}
+
 __global__ __launch_bounds__(kInPassThreads) void input_pass_kernel(const InPassArgs a) {
   const int wg = (int)blockIdx.x;
   int qi = 0;
@@ -188,6 +284,23 @@ int64_t plan_input_pass(InPassArgs& a) {
 hipError_t launch_input_pass(const InPassArgs& a, int64_t grid, hipStream_t stream) {
   if (grid <= 0) return hipSuccess;
   hipLaunchKernelGGL(input_pass_kernel, dim3((unsigned)grid), dim3(kInPassThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+int64_t plan_input_pass_weighted(InPassWgtArgs& aw) {
+  InPassArgs& a = aw.in;
+  (void)plan_input_pass(a);       // nb_idx, nb_dense
+  int32_t nb_idx[DRS_MAX_COALESCE], nb_dense[DRS_MAX_COALESCE], nb_wgt[DRS_MAX_COALESCE];
+  for (int i = 0; i < a.n_q; ++i) {
+    aw.w[i].nb_wgt = aw.w[i].src ? wgt_chunks(a.q[i].n_idx) : 0;
+    nb_idx[i] = a.q[i].nb_idx; nb_dense[i] = a.q[i].nb_dense; nb_wgt[i] = aw.w[i].nb_wgt;
+  }
+  return plan_weighted_grid(a.n_q, a.T, nb_idx, nb_dense, nb_wgt, a.wg0);
+}
+
+hipError_t launch_input_pass_weighted(const InPassWgtArgs& a, int64_t grid, hipStream_t stream) {
+  if (grid <= 0) return hipSuccess;
+  hipLaunchKernelGGL(input_pass_weighted_kernel, dim3((unsigned)grid), dim3(kInPassThreads), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -159,6 +159,31 @@ def device_request(request, T, m_den, device, i=0):
             lengths.data_ptr(), lengths.stride(0) if T > 1 else bs, fixed_len)
 
 
+def device_weights(w, T, n, device, i=0):
+    """The per-sample weights of one request of run_queued_device_multi -- a torch tensor [T, n] of float32, float16 or
+    bfloat16 on GPU `device`, one weight per index of ids, last dimension contiguous, rows any non-negative stride apart (a
+    column slice of a wider tensor goes down as it is) -- as the (ptr, row_stride, dtype) entry
+    Engine.run_queues_device_multi_async takes; None stays None (the request is unweighted).  Checks what the tensor itself
+    shows (dtype, shape, layout, then the device) and raises ValueError naming the argument; touches no engine."""
+    import torch
+    if w is None:
+        return None
+    if not isinstance(w, torch.Tensor):
+        raise ValueError("request %d: weights must be a torch tensor or None, got %s" % (i, type(w).__name__))
+    codes = {torch.float32: N.WEIGHT_FP32, torch.float16: N.WEIGHT_FP16, torch.bfloat16: N.WEIGHT_BF16}
+    if w.dtype not in codes:
+        raise ValueError("request %d: weights must be torch.float32, torch.float16 or torch.bfloat16, got %s" % (i, w.dtype))
+    if w.dim() != 2 or w.shape[0] != T or w.shape[1] != n:
+        raise ValueError("request %d: weights must be [%d, %d] (one per index of ids), got %r" % (i, T, n, tuple(w.shape)))
+    if w.shape[1] > 1 and w.stride(1) != 1:
+        raise ValueError("request %d: the last dimension of weights must be contiguous (stride %d)" % (i, w.stride(1)))
+    if w.shape[0] > 1 and w.stride(0) < 0:
+        raise ValueError("request %d: weights has a negative row stride" % i)
+    if w.device.type != "cuda" or w.device.index != device:
+        raise ValueError("request %d: weights lives on %s, the engine on cuda:%d" % (i, w.device, device))
+    return (w.data_ptr(), w.stride(0) if T > 1 else n, codes[w.dtype])
+
+
 def device_out(t, bs, n_out, device, i=0):
     """One output of run_queued_device_io_multi -- a torch fp32 tensor [bs, n_out] on GPU `device`, last dimension contiguous,
     rows any non-negative stride apart (a column block of a wider tensor goes down as it is) -- as the (ptr, row_stride)
@@ -386,13 +411,16 @@ class _HipNet(object):
         int64, lengths [T, bs] int32, fc [bs, m_den] float32 or None -- last dimension contiguous, row strides as the
         tensors have them, so slices of wider tensors go down as they are.  fixed_len >= 0 promises that every bag holds
         that many indices (default -1: the lengths are read).  No byte crosses the bus: one kernel launch narrows, scans
-        and checks the arrays.  Returns the list of [bs_i, n_out] outputs (numpy, as run_queued_multi)."""
+        and checks the arrays.  Returns the list of [bs_i, n_out] outputs (numpy, as run_queued_multi).
+        A request may carry a sixth element, its per-sample weights (SparseLengthsWeightedSum; device_weights): a [T, n]
+        tensor of float32, float16 or bfloat16 on the same GPU, one weight per index of ids, or None -- the same launch
+        copies or widens them (drs_run_queues_device_weighted_multi_async); requests with and without weights mix."""
         import torch
         eng = self.engine
-        qs, spare = self._device_queries(requests)
+        qs, spare, wts = self._device_queries(requests)
         # the engine cannot order itself behind the work that produced the tensors: once per call, torch's stream
         torch.cuda.current_stream(eng.device).synchronize()
-        eng.run_queues_device_multi_async(qs, slot=slot)
+        eng.run_queues_device_multi_async(qs, slot=slot, weights=wts)
         sizes = [q[0] for q in qs]
         out = eng.wait(slot, sum(sizes))
         outs = np.split(out, np.cumsum(sizes)[:-1], axis=0)
@@ -400,10 +428,18 @@ class _HipNet(object):
         return outs
 
     def _device_queries(self, requests):
-        """requests of torch tensors -> (the tuples Engine.run_queues_device_multi_async takes, a tensor to keep alive or None)"""
+        """requests of torch tensors -> (the tuples Engine.run_queues_device_multi_async takes, a tensor to keep alive or None,
+        its `weights` argument: None unless a request has a sixth element, the per-sample weights or None)"""
         import torch
         eng = self.engine
-        qs = [device_request(r, eng.T, eng.m_den, eng.device, i) for i, r in enumerate(requests)]
+        for i, r in enumerate(requests):
+            if len(r) not in (4, 5, 6):
+                raise ValueError("request %d: (ids, lengths, fc, batch_size[, fixed_len[, weights]])" % i)
+        qs = [device_request(r[:5], eng.T, eng.m_den, eng.device, i) for i, r in enumerate(requests)]
+        wts = None
+        if any(len(r) == 6 for r in requests):
+            wts = [device_weights(r[5], eng.T, q[4], eng.device, i) if len(r) == 6 else None
+                   for i, (r, q) in enumerate(zip(requests, qs))]
         # (torch gives an empty tensor a null data_ptr; the library takes no null ids with bs > 0, even where none is read)
         spare = None
         for k, q in enumerate(qs):
@@ -411,7 +447,7 @@ class _HipNet(object):
                 if spare is None:
                     spare = torch.zeros((eng.T, 1), dtype=torch.int64, device="cuda:%d" % eng.device)
                 qs[k] = q[:2] + (spare.data_ptr(), 1) + q[4:]
-        return qs, spare
+        return qs, spare, wts
 
     def run_queued_device_io_multi(self, requests, out=None, stream=None, slot=0):
         """run_queued_device_multi whose results stay on the GPU (drs_run_queues_device_io_multi_async, `ordered` 1): returns
@@ -427,14 +463,14 @@ class _HipNet(object):
         n_out, device = eng.n_out, eng.device
         if out is not None and len(out) != len(requests):
             raise ValueError("%d requests, %d output tensors" % (len(requests), len(out)))
-        qs, spare = self._device_queries(requests)
+        qs, spare, wts = self._device_queries(requests)
         if out is None:
             out = [torch.empty((q[0], n_out), dtype=torch.float32, device="cuda:%d" % device) for q in qs]
         outs_arg = [device_out(t, q[0], n_out, device, i) for i, (t, q) in enumerate(zip(out, qs))]
         if stream is None:
             stream = torch.cuda.current_stream(device)
         handle = stream.cuda_stream if isinstance(stream, torch.cuda.Stream) else int(stream)
-        eng.run_queues_device_io_multi_async(qs, outs_arg, stream=handle, slot=slot)     # (waits first for a set still on the slot)
+        eng.run_queues_device_io_multi_async(qs, outs_arg, stream=handle, slot=slot, weights=wts)     # (waits first for a set still on the slot)
         refs = getattr(self, "_device_refs", None)
         if refs is None:
             refs = self._device_refs = {}
@@ -936,7 +972,8 @@ class _Wrapper(object):
         return self.net.run_queued_multi(requests, slot=slot)
 
     def run_queues_device_multi(self, requests, slot=0):
-        """run_queues_multi for requests whose arrays are torch tensors on the engine's GPU (_HipNet.run_queued_device_multi)."""
+        """run_queues_multi for requests whose arrays are torch tensors on the engine's GPU (_HipNet.run_queued_device_multi);
+        a request's optional sixth element is its per-sample weights."""
         return self.net.run_queued_device_multi(requests, slot=slot)
 
     def run_queues_device_io_multi(self, requests, out=None, stream=None, slot=0):

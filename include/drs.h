@@ -409,12 +409,14 @@ const char* drs_comm_last_error(void);
  * table rows in whatever type the table is stored.  drs_device_inputs.h adds the form of the per-call input path whose
  * dense rows, indices and lengths are DEVICE arrays: narrowed, prefix-summed and ENFORCE-checked by one kernel launch per
  * set instead of on the host.  drs_device_outputs.h adds the form of THAT call whose results stay on the device as well,
- * optionally ordered on a stream of the caller's at both ends.                                                         */
+ * optionally ordered on a stream of the caller's at both ends.  drs_device_weights.h adds the form of both calls that
+ * carries per-sample weights as device arrays too.                                                                     */
 #include "drs_weights.h"
 #include "drs_fp8.h"
 #include "drs_rows.h"
 #include "drs_device_inputs.h"
 #include "drs_device_outputs.h"
+#include "drs_device_weights.h"
 
 #ifdef __cplusplus
 }

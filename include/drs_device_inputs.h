@@ -15,7 +15,8 @@
  * ELEMENTS apart; d_lengths[i]: [T, bs] int32, rows len_row_stride[i] elements apart.  The pointer tables, strides and
  * counts themselves are HOST arrays.  n in 1..DRS_MAX_COALESCE; drs_wait returns the n results back to back; a query's
  * bits do not depend on what it was coalesced with, and they are the bits drs_run_queues_multi_async gives the same
- * arrays.  All six model kinds; per-sample weights do not travel on this path (nor on the host per-call paths).
+ * arrays.  All six model kinds; per-sample weights travel on this path through drs_device_weights.h's form of this call
+ * (the host per-call paths carry none).
  *
  * fixed_len[i] >= 0 is the caller's PROMISE that every bag of every table of query i holds exactly that many indices:
  * the host cannot look at the lengths, and the launch forms for fixed-length bags are chosen on the host.  fixed_len[i]

@@ -17,8 +17,8 @@
  * then).  drs_stage_batch on the same batch_id drops the weights: the batch is unweighted again.  Non-finite
  * weights are outside the contract, as non-finite table values are.  drs_forward, drs_forward_async and
  * drs_forward_multi_async serve weighted batches, also mixed with unweighted ones in one launch set (an unweighted
- * query keeps its sequential bits there); the per-call input paths below (drs_forward_inputs*, drs_run_queues*)
- * carry no weights.  A launch set with a weighted query takes the ring walk or the any-width form, never the flat or
+ * query keeps its sequential bits there); the host per-call input paths (drs_forward_inputs*, drs_run_queues*)
+ * carry no weights, the device-array ones carry them through drs_device_weights.h.  A launch set with a weighted query takes the ring walk or the any-width form, never the flat or
  * one-lookup forms (dispatch log: a "w" token).  DIN and DIEN: DRS_ERR_UNSUPPORTED; so is a handle under "sls_pool" 1
  * (there is no weighted mean), and "sls_pool" 1 is refused while a staged batch carries weights.  drs_gather_bytes
  * counts 4 more bytes per looked-up row of a weighted batch.  Read-only option "sls_weighted": staged batches that
