@@ -126,6 +126,14 @@ DEVICE_WEIGHT_SYMBOLS = [
     ("drs_run_queues_device_weighted_multi_async", C.c_int32, DEVICE_INPUT_SYMBOLS[0][2] + [
         C.POINTER(C.c_void_p), _i64p, _i32p, C.POINTER(C.c_void_p), _i64p, C.c_void_p, C.c_int32]),
 ]
+# single table rows updated and read back from device arrays (include/drs_device_rows.h) -- the HIP build alone, as above
+DEVICE_ROW_SYMBOLS = [
+    ("drs_update_rows_device", C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                           C.c_int32]),
+    ("drs_get_rows_device", C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
+]
+DEVICE_ROWS_MAX = 1 << 24      # DRS_DEVICE_ROWS_MAX: the most rows one device call names
+
 # the codes of a weight array's element type (wgt_dtype: the DRS_TABLE_* codes of the three float types)
 WEIGHT_FP32, WEIGHT_FP16, WEIGHT_BF16 = 0, 1, 2
 
@@ -176,7 +184,7 @@ def lib():
             raise ImportError("%s identifies itself as %r: deeprecsys_amd binds the HIP build only "
                               "(the CPU restatement of the ABI is test infrastructure)" % (LIB_PATH, backend))
         for name, res, args in (WEIGHT_SYMBOLS + FP8_SYMBOLS + ROW_SYMBOLS + DEVICE_INPUT_SYMBOLS + DEVICE_OUTPUT_SYMBOLS +
-                                DEVICE_WEIGHT_SYMBOLS):     # (the HIP build alone exports these)
+                                DEVICE_WEIGHT_SYMBOLS + DEVICE_ROW_SYMBOLS):     # (the HIP build alone exports these)
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -296,6 +304,22 @@ class Engine(object):
         self._check(lib().drs_get_rows(self._h, int(t), ids.size, ids.ctypes.data_as(_i64p), out.ctypes.data_as(_f32p)),
                     "drs_get_rows")
         return out
+
+    def update_rows_device(self, t, ids_ptr, n, val_ptr, row_stride, dtype, stream=None):
+        """update_rows for ids and values that are DEVICE arrays on the engine's GPU (drs_update_rows_device): ids_ptr -> n
+        contiguous int64, val_ptr -> [n, D] elements of `dtype` (TABLE_FP32, TABLE_FP16 or TABLE_BF16), rows `row_stride`
+        elements apart.  stream None: the arrays are complete (`ordered` 0); a stream handle (0: HIP's null stream): the
+        passes run behind what is enqueued there (`ordered` 1).  Returns when the rows are in the table."""
+        self._check(lib().drs_update_rows_device(self._h, int(t), int(n), C.c_void_p(int(ids_ptr)), C.c_void_p(int(val_ptr)), int(row_stride),
+                                                 int(dtype), C.c_void_p(0 if stream is None else int(stream)), 0 if stream is None else 1),
+                    "drs_update_rows_device")
+
+    def get_rows_device(self, t, ids_ptr, n, out_ptr, row_stride, stream=None):
+        """get_rows into a DEVICE array (drs_get_rows_device): out_ptr -> [n, D] float32, rows `row_stride` floats apart;
+        ids_ptr and stream as update_rows_device.  Returns when out is written."""
+        self._check(lib().drs_get_rows_device(self._h, int(t), int(n), C.c_void_p(int(ids_ptr)), C.c_void_p(int(out_ptr)), int(row_stride),
+                                              C.c_void_p(0 if stream is None else int(stream)), 0 if stream is None else 1),
+                    "drs_get_rows_device")
 
     def set_fc(self, mlp, layer, W, b):
         W, b = _f32(W), _f32(b)

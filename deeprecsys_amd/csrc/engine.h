@@ -24,7 +24,8 @@
 // drs_create / drs_destroy, tables and weights), engine_arena.hip (where the table arena lives), engine_inputs.hip
 // (staging and the per-call input path), engine_dispatch.hip (a launch set: enqueue, wait, the operator-level entry
 // points), engine_options.hip (the option table, profiling read-outs), engine_rows.hip (single table rows: drs_update_rows /
-// drs_get_rows), engine_device_inputs.hip (launch sets whose per-query arrays are device arrays: the refusals the host can
+// drs_get_rows), device_rows.hip (the same two calls for ids and rows in device memory: drs_update_rows_device /
+// drs_get_rows_device, their kernel passes and row_dedup.h's de-duplication table), engine_device_inputs.hip (launch sets whose per-query arrays are device arrays: the refusals the host can
 // make and the input-pass launch), engine_device_outputs.hip (the same sets with their results left in device arrays of the
 // caller's: the output-pass launch and the event edges to the caller's stream).  engine_host.h: the worker pool and the
 // launcher thread of the per-call input path.  input_block.h: the per-call input block's layout, the host pass that

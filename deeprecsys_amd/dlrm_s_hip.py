@@ -205,6 +205,64 @@ def device_out(t, bs, n_out, device, i=0):
     return (t.data_ptr() if bs > 0 else 0, t.stride(0) if bs > 1 else n_out)
 
 
+def on_device(x, device):
+    """is x a torch tensor on GPU `device`?  (what sends update_embedding_rows / embedding_rows down the device route; a
+    module that never imported torch holds no such tensor)"""
+    torch = sys.modules.get("torch")
+    return torch is not None and isinstance(x, torch.Tensor) and x.device.type == "cuda" and x.device.index == device
+
+
+def device_row_ids(ids, device):
+    """The ids of a device row update or read-back -- a torch int64 tensor [n], contiguous, on GPU `device` -- as the (ptr, n)
+    Engine.update_rows_device takes.  Checks what the tensor itself shows and raises ValueError naming the rule; touches no
+    engine."""
+    import torch
+    if not isinstance(ids, torch.Tensor):
+        raise ValueError("ids: must be a torch tensor, got %s" % type(ids).__name__)
+    if ids.dtype != torch.int64:
+        raise ValueError("ids: must be torch.int64, got %s" % ids.dtype)
+    if ids.dim() != 1:
+        raise ValueError("ids: must be [n], got %r" % (tuple(ids.shape),))
+    if not ids.is_contiguous():
+        raise ValueError("ids: must be contiguous (stride %d)" % ids.stride(0))
+    if ids.shape[0] > N.DEVICE_ROWS_MAX:
+        raise ValueError("ids: %d rows, one call names at most %d" % (ids.shape[0], N.DEVICE_ROWS_MAX))
+    if ids.device.type != "cuda" or ids.device.index != device:
+        raise ValueError("ids: lives on %s, the engine on cuda:%d" % (ids.device, device))
+    return ids.data_ptr(), int(ids.shape[0])
+
+
+def device_row_values(v, n, D, device, name="values", dtypes=None):
+    """The rows of a device row update -- a torch tensor [n, D] of float32, float16 or bfloat16 on GPU `device`, last
+    dimension contiguous, rows at least D elements apart (a column block of a wider tensor goes down as it is) -- as the
+    (ptr, row_stride, dtype code) Engine.update_rows_device takes; with dtypes=(torch.float32,) the output of a read-back.
+    Checks what the tensor itself shows (dtype, shape, layout, then the device) and raises ValueError naming the rule;
+    touches no engine."""
+    import torch
+    codes = {torch.float32: N.TABLE_FP32, torch.float16: N.TABLE_FP16, torch.bfloat16: N.TABLE_BF16}
+    allowed = tuple(codes) if dtypes is None else tuple(dtypes)
+    if not isinstance(v, torch.Tensor):
+        raise ValueError("%s: must be a torch tensor, got %s" % (name, type(v).__name__))
+    if v.dtype not in allowed:
+        raise ValueError("%s: must be %s, got %s" % (name, " or ".join(str(d) for d in allowed), v.dtype))
+    if v.dim() != 2 or v.shape[0] != n or v.shape[1] != D:
+        raise ValueError("%s: must be [%d, %d], got %r" % (name, n, D, tuple(v.shape)))
+    if D > 1 and v.stride(1) != 1:
+        raise ValueError("%s: the last dimension must be contiguous (stride %d)" % (name, v.stride(1)))
+    if n > 1 and v.stride(0) < D:
+        raise ValueError("%s: a row stride of %d, below the row width %d (the rows would overlap)" % (name, v.stride(0), D))
+    if v.device.type != "cuda" or v.device.index != device:
+        raise ValueError("%s: lives on %s, the engine on cuda:%d" % (name, v.device, device))
+    return v.data_ptr(), (v.stride(0) if n > 1 else D), codes[v.dtype]
+
+
+def _stream_handle(stream):
+    """None stays None (`ordered` 0); a torch.cuda.Stream or a raw handle becomes the handle (`ordered` 1)"""
+    if stream is None:
+        return None
+    return stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+
+
 def _init_table(n, m):
     # models/dlrm_s_caffe2.py:297-299
     return np.random.uniform(low=-np.sqrt(1 / n), high=np.sqrt(1 / n), size=(n, m)).astype(np.float32)
@@ -492,14 +550,41 @@ class _HipNet(object):
                                     weights=None if lS_w is None else lS_w[j])
         self._n_staged = len(lS_l)
 
-    def update_embedding_rows(self, t, ids, values):
+    def update_embedding_rows(self, t, ids, values, stream=None):
         """Rows `ids` of embedding table t take `values` ([n, m_spa] fp32) in place, stored in the tables' current type
-        (FBGEMM's emb_inplace_update; Engine.update_rows): queries enqueued before the call see the old rows."""
-        self.engine.update_rows(t, ids, values)
+        (FBGEMM's emb_inplace_update; Engine.update_rows): queries enqueued before the call see the old rows.
+        `ids` a torch tensor on the engine's GPU: the device route (drs_update_rows_device) -- ids int64 [n] contiguous,
+        values [n, m_spa] float32, float16 or bfloat16 on the same GPU, last dimension contiguous (device_row_ids,
+        device_row_values); no byte crosses the bus.  stream None: the tensors are complete; a torch.cuda.Stream or a raw
+        handle: the update runs behind what is enqueued there and the caller does not synchronise.  numpy arguments take
+        the host route (`stream` is refused there)."""
+        eng = self.engine
+        if not on_device(ids, eng.device):
+            if stream is not None:
+                raise ValueError("stream: ordering applies to the device route, ids on cuda:%d" % eng.device)
+            return eng.update_rows(t, ids, values)
+        ids_ptr, n = device_row_ids(ids, eng.device)
+        val_ptr, stride, code = device_row_values(values, n, eng.D, eng.device)
+        eng.update_rows_device(t, ids_ptr, n, val_ptr, stride, code, stream=_stream_handle(stream))
 
-    def embedding_rows(self, t, ids):
-        """-> [n, m_spa] fp32: rows `ids` of embedding table t as the engine serves them (Engine.get_rows)."""
-        return self.engine.get_rows(t, ids)
+    def embedding_rows(self, t, ids, out=None, stream=None):
+        """-> [n, m_spa] fp32: rows `ids` of embedding table t as the engine serves them (Engine.get_rows).
+        `ids` a torch tensor on the engine's GPU: the device route (drs_get_rows_device) -- returns a float32 tensor on that
+        GPU, `out` when given ([n, m_spa] float32, last dimension contiguous; a column block of a wider tensor keeps what
+        lies between its rows); stream as in update_embedding_rows.  numpy ids take the host route (`out` and `stream` are
+        refused there)."""
+        eng = self.engine
+        if not on_device(ids, eng.device):
+            if out is not None or stream is not None:
+                raise ValueError("out / stream: the device route only, ids on cuda:%d" % eng.device)
+            return eng.get_rows(t, ids)
+        import torch
+        ids_ptr, n = device_row_ids(ids, eng.device)
+        if out is None:
+            out = torch.empty((n, eng.D), dtype=torch.float32, device="cuda:%d" % eng.device)
+        out_ptr, stride, _ = device_row_values(out, n, eng.D, eng.device, name="out", dtypes=(torch.float32,))
+        eng.get_rows_device(t, ids_ptr, n, out_ptr, stride, stream=_stream_handle(stream))
+        return out
 
     def tune_table_placement(self, candidates=12, sets=128, spacer_gb=None, policies=(1, 0), max_extra_gb=48, sharers=1):
         """Where the tables live in HBM, and with which cache policy their rows are read, moves the many-rows-per-bag

@@ -410,13 +410,15 @@ const char* drs_comm_last_error(void);
  * dense rows, indices and lengths are DEVICE arrays: narrowed, prefix-summed and ENFORCE-checked by one kernel launch per
  * set instead of on the host.  drs_device_outputs.h adds the form of THAT call whose results stay on the device as well,
  * optionally ordered on a stream of the caller's at both ends.  drs_device_weights.h adds the form of both calls that
- * carries per-sample weights as device arrays too.                                                                     */
+ * carries per-sample weights as device arrays too.  drs_device_rows.h adds the update and the read-back of single table
+ * rows whose ids and values are DEVICE arrays, optionally ordered behind a stream of the caller's.                        */
 #include "drs_weights.h"
 #include "drs_fp8.h"
 #include "drs_rows.h"
 #include "drs_device_inputs.h"
 #include "drs_device_outputs.h"
 #include "drs_device_weights.h"
+#include "drs_device_rows.h"
 
 #ifdef __cplusplus
 }
