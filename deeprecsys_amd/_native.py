@@ -133,6 +133,14 @@ DEVICE_ROW_SYMBOLS = [
     ("drs_get_rows_device", C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
 ]
 DEVICE_ROWS_MAX = 1 << 24      # DRS_DEVICE_ROWS_MAX: the most rows one device call names
+# each query's top-k rows by one score column, one launch per set (include/drs_device_topk.h) -- the HIP build alone, as above
+DEVICE_TOPK_SYMBOLS = [
+    ("drs_topk_rows", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+    ("drs_run_queues_device_topk_multi_async", C.c_int32, DEVICE_INPUT_SYMBOLS[0][2] + [
+        C.POINTER(C.c_void_p), _i64p, _i32p, _i32p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_int32]),
+]
+TOPK_MAX = 1024                # DRS_TOPK_MAX: the most rows one query hands back
 
 # the codes of a weight array's element type (wgt_dtype: the DRS_TABLE_* codes of the three float types)
 WEIGHT_FP32, WEIGHT_FP16, WEIGHT_BF16 = 0, 1, 2
@@ -184,7 +192,7 @@ def lib():
             raise ImportError("%s identifies itself as %r: deeprecsys_amd binds the HIP build only "
                               "(the CPU restatement of the ABI is test infrastructure)" % (LIB_PATH, backend))
         for name, res, args in (WEIGHT_SYMBOLS + FP8_SYMBOLS + ROW_SYMBOLS + DEVICE_INPUT_SYMBOLS + DEVICE_OUTPUT_SYMBOLS +
-                                DEVICE_WEIGHT_SYMBOLS + DEVICE_ROW_SYMBOLS):     # (the HIP build alone exports these)
+                                DEVICE_WEIGHT_SYMBOLS + DEVICE_ROW_SYMBOLS + DEVICE_TOPK_SYMBOLS):     # (the HIP build alone exports these)
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -578,6 +586,41 @@ class Engine(object):
         self._check(lib().drs_run_queues_device_io_multi_async(self._h, slot, *(args + [
             op, out_stride.ctypes.data_as(_i64p), None if stream is None else (int(stream) or None), 0 if stream is None else 1])),
             "drs_run_queues_device_io_multi_async")
+
+    def run_queues_device_topk_multi_async(self, queries, k, col, tops, stream=None, slot=0, weights=None):
+        """run_queues_device_io_multi_async that hands back each query's top-k rows instead of every score
+        (include/drs_device_topk.h): `k` one count per query (0..min(bs, TOPK_MAX)), `col` the score column the rows rank by,
+        `tops` a list of (idx_ptr, scores_ptr), one per query -- the device addresses of query i's int32 [k_i] row numbers
+        and float32 [k_i, n_out] score rows (0 / None where k_i is 0).  One kernel launch per set ranks every query; NaN first,
+        equal scores by the lower row.  stream, slot, weights and the lifetime rule: as in run_queues_device_io_multi_async."""
+        if len(k) != len(queries) or len(tops) != len(queries):
+            raise ValueError("%d queries, %d counts, %d outputs" % (len(queries), len(k), len(tops)))
+        args, keep = self._device_set(queries)
+        n = len(queries)
+        ka = np.zeros(max(n, 1), dtype=np.int32)
+        ka[:n] = k
+        ip = (C.c_void_p * max(n, 1))()
+        sp = (C.c_void_p * max(n, 1))()
+        for i, (iptr, sptr) in enumerate(tops):
+            ip[i] = iptr or None
+            sp[i] = sptr or None
+        wkeep = None
+        wargs = [None, None, None]
+        if weights is not None:
+            wargs, wkeep = self._device_weights(n, weights)
+        self._check(lib().drs_run_queues_device_topk_multi_async(self._h, slot, *(args + wargs + [
+            ka.ctypes.data_as(_i32p), int(col), ip, sp, None if stream is None else (int(stream) or None), 0 if stream is None else 1])),
+            "drs_run_queues_device_topk_multi_async")
+        del keep, wkeep
+
+    def topk_rows(self, scores_ptr, rows, n_out, row_stride, col, k, idx_ptr, top_ptr, stream=None):
+        """The top-k pass on a device array of the caller's (drs_topk_rows): scores_ptr -> [rows, n_out] float32, rows
+        `row_stride` floats apart; the k rows that rank first by column `col` go to top_ptr as [k, n_out] float32 and their
+        row numbers to idx_ptr as int32 [k].  Enqueued on `stream` (an integer hipStream_t handle; None / 0: the null stream);
+        returns at once."""
+        self._check(lib().drs_topk_rows(self._h, C.c_void_p(int(scores_ptr or 0)), int(rows), int(n_out), int(row_stride), int(col), int(k),
+                                        C.c_void_p(int(idx_ptr or 0)), C.c_void_p(int(top_ptr or 0)),
+                                        None if not stream else C.c_void_p(int(stream))), "drs_topk_rows")
 
     def fetch_interaction(self, bs, slot=0):
         R = np.empty((bs, self.num_int), dtype=np.float32)

@@ -448,4 +448,9 @@ hipError_t launch_input_pass_weighted(const InPassWgtArgs& a, int64_t grid, hipS
 struct OutPassArgs;
 hipError_t launch_output_pass(const OutPassArgs& a, int64_t grid, hipStream_t stream);
 
+// The top-k pass on the device (topk_pass.hip; include/drs_device_topk.h): ONE launch, workgroup i ranks query i of TopKArgs
+// by one score column and writes its k winners' row numbers and score rows.  TopKArgs and the order are plain C++ (topk_plan.h).
+struct TopKArgs;
+hipError_t launch_topk_pass(const TopKArgs& a, hipStream_t stream);
+
 }  // namespace drs

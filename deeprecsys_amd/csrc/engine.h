@@ -27,7 +27,8 @@
 // drs_get_rows), device_rows.hip (the same two calls for ids and rows in device memory: drs_update_rows_device /
 // drs_get_rows_device, their kernel passes and row_dedup.h's de-duplication table), engine_device_inputs.hip (launch sets whose per-query arrays are device arrays: the refusals the host can
 // make and the input-pass launch), engine_device_outputs.hip (the same sets with their results left in device arrays of the
-// caller's: the output-pass launch and the event edges to the caller's stream).  engine_host.h: the worker pool and the
+// caller's: the output-pass launch and the event edges to the caller's stream), engine_device_topk.hip (the same sets
+// handing back each query's top-k rows: the top-k pass launch, and drs_topk_rows).  engine_host.h: the worker pool and the
 // launcher thread of the per-call input path.  input_block.h: the per-call input block's layout, the host pass that
 // fills one and the copies that move it (plain C++: a host program can build it alone).  weight_plan.h: the plan of the
 // per-sample weights a device set may carry (include/drs_device_weights.h), plain C++ likewise.

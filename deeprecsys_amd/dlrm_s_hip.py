@@ -205,6 +205,29 @@ def device_out(t, bs, n_out, device, i=0):
     return (t.data_ptr() if bs > 0 else 0, t.stride(0) if bs > 1 else n_out)
 
 
+def device_top(pair, k, n_out, device, i=0):
+    """One output of run_queued_device_topk_multi -- (idx, scores): torch tensors on GPU `device`, idx int32 [k] and scores
+    float32 [k, n_out], both contiguous -- as the (idx_ptr, scores_ptr) Engine.run_queues_device_topk_multi_async takes.
+    Checks what the tensors themselves show (dtype, shape, layout, then the device) and raises ValueError naming the
+    argument; touches no engine."""
+    import torch
+    if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+        raise ValueError("out %d: must be a pair (idx, scores)" % i)
+    for name, t, dtype, shape in (("idx", pair[0], torch.int32, (k,)), ("scores", pair[1], torch.float32, (k, n_out))):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("out %d: %s must be a torch tensor, got %s" % (i, name, type(t).__name__))
+        if t.dtype != dtype:
+            raise ValueError("out %d: %s must be %s, got %s" % (i, name, dtype, t.dtype))
+        if tuple(t.shape) != shape:
+            raise ValueError("out %d: %s must be %s, got %r" % (i, name, list(shape), tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("out %d: %s must be contiguous (strides %r)" % (i, name, tuple(t.stride())))
+    for name, t in (("idx", pair[0]), ("scores", pair[1])):
+        if t.device.type != "cuda" or t.device.index != device:
+            raise ValueError("out %d: %s lives on %s, the engine on cuda:%d" % (i, name, t.device, device))
+    return (pair[0].data_ptr() if k > 0 else 0, pair[1].data_ptr() if k > 0 else 0)
+
+
 def on_device(x, device):
     """is x a torch tensor on GPU `device`?  (what sends update_embedding_rows / embedding_rows down the device route; a
     module that never imported torch holds no such tensor)"""
@@ -533,6 +556,42 @@ class _HipNet(object):
         if refs is None:
             refs = self._device_refs = {}
         refs[slot] = (list(requests), list(out), spare)
+        return list(out)
+
+    def run_queued_device_topk_multi(self, requests, k, col=0, out=None, stream=None, slot=0):
+        """run_queued_device_io_multi that hands back each request's best rows instead of every score
+        (drs_run_queues_device_topk_multi_async, `ordered` 1): returns at once a list of (idx, scores) torch tensors, int32
+        [k_i] and float32 [k_i, n_out] with k_i = min(k, bs_i) -- the row numbers within request i of the k_i samples that
+        rank first by score column `col` (NaN first, equal scores by the lower row) and their full score rows -- `out`, one
+        pair per request, or freshly allocated ones.  ONE kernel launch per set ranks every request.  stream, the lifetime of
+        the tensors and finish_device(slot): as in run_queued_device_io_multi; a set that failed on the device holds -1 in
+        every idx and NaN in every score.  A request's sixth element carries its per-sample weights as before."""
+        import torch
+        eng = self.engine
+        n_out, device = eng.n_out, eng.device
+        k = int(k)
+        if k < 0 or k > N.TOPK_MAX:
+            raise ValueError("k: %d outside 0..%d" % (k, N.TOPK_MAX))
+        if not 0 <= int(col) < n_out:
+            raise ValueError("col: %d outside [0, %d)" % (int(col), n_out))
+        if out is not None and len(out) != len(requests):
+            raise ValueError("%d requests, %d output pairs" % (len(requests), len(out)))
+        qs, spare, wts = self._device_queries(requests)
+        ks = [min(k, q[0]) for q in qs]
+        if out is None:
+            dev = "cuda:%d" % device
+            out = [(torch.empty((ki,), dtype=torch.int32, device=dev), torch.empty((ki, n_out), dtype=torch.float32, device=dev))
+                   for ki in ks]
+        tops = [device_top(p, ki, n_out, device, i) for i, (p, ki) in enumerate(zip(out, ks))]
+        if stream is None:
+            stream = torch.cuda.current_stream(device)
+        handle = stream.cuda_stream if isinstance(stream, torch.cuda.Stream) else int(stream)
+        eng.run_queues_device_topk_multi_async(qs, ks, int(col), tops, stream=handle, slot=slot, weights=wts)   # (waits first for a set still on the slot)
+        refs = getattr(self, "_device_refs", None)
+        if refs is None:
+            refs = self._device_refs = {}
+        out = [tuple(p) for p in out]
+        refs[slot] = (list(requests), out, spare)
         return list(out)
 
     def finish_device(self, slot=0):
@@ -1065,6 +1124,12 @@ class _Wrapper(object):
         """run_queues_device_multi whose results stay on the GPU, ordered on a torch stream: returns the list of [bs_i, n_out]
         device tensors at once (_HipNet.run_queued_device_io_multi); finish_device(slot) is the set's completion."""
         return self.net.run_queued_device_io_multi(requests, out=out, stream=stream, slot=slot)
+
+    def run_queues_device_topk_multi(self, requests, k, col=0, out=None, stream=None, slot=0):
+        """run_queues_device_io_multi that keeps each request's k best rows by score column `col`: returns the list of
+        (idx, scores) device tensors at once, ranked by one kernel launch per set (_HipNet.run_queued_device_topk_multi);
+        finish_device(slot) is the set's completion."""
+        return self.net.run_queued_device_topk_multi(requests, k, col=col, out=out, stream=stream, slot=slot)
 
     def finish_device(self, slot=0):
         return self.net.finish_device(slot=slot)

@@ -411,7 +411,8 @@ const char* drs_comm_last_error(void);
  * set instead of on the host.  drs_device_outputs.h adds the form of THAT call whose results stay on the device as well,
  * optionally ordered on a stream of the caller's at both ends.  drs_device_weights.h adds the form of both calls that
  * carries per-sample weights as device arrays too.  drs_device_rows.h adds the update and the read-back of single table
- * rows whose ids and values are DEVICE arrays, optionally ordered behind a stream of the caller's.                        */
+ * rows whose ids and values are DEVICE arrays, optionally ordered behind a stream of the caller's.  drs_device_topk.h adds
+ * the form of the device-output call that hands back each query's top-k rows by one score column, in one launch per set.  */
 #include "drs_weights.h"
 #include "drs_fp8.h"
 #include "drs_rows.h"
@@ -419,6 +420,7 @@ const char* drs_comm_last_error(void);
 #include "drs_device_outputs.h"
 #include "drs_device_weights.h"
 #include "drs_device_rows.h"
+#include "drs_device_topk.h"
 
 #ifdef __cplusplus
 }
