@@ -29,8 +29,12 @@ stream_kernel: ceil(N / 128) * ceil(K / 64).  The budget is 159 744 B = 39 936 f
 
 build: Built(case) makes the model's weights, tables and inputs from the case's own seed; the CPU test (oracle against
 float64) and the GPU test (engine against oracle) share it.
+
+poison: Built(case, poison=True) and poisoned(net, bs), at the end of this file, put NaN, +-inf and +-3e38 INSIDE valid rows
+(tests/test_mlp_nonfinite_cpu.py, tests/test_mlp_nonfinite.py).
 """
 import collections
+import copy
 import re
 import zlib
 
@@ -319,9 +323,11 @@ KIND = {"dlrm_cat": N.MODEL_DLRM, "dlrm_dot": N.MODEL_DLRM, "wnd": N.MODEL_WND, 
 
 class Built(object):
     """One catalogue model: weights normal(0, 1 / sqrt(K)), biases normal(0, 0.1), tables and dense inputs uniform(-1, 1).
-    Every table carries one extra LAST row of NaN that no valid bag names: stage(bs) points the bags beyond bs at it."""
+    Every table carries one extra LAST row of NaN that no valid bag names: stage(bs) points the bags beyond bs at it.
+    poison=True: the tables of poison_tables() carry the POISON_ROWS in front of that NaN row (no valid bag names them
+    either; poisoned(net, bs) points bags of its hot samples at them).  Everything else is drawn as without."""
 
-    def __init__(self, case, seed=None):
+    def __init__(self, case, seed=None, poison=False):
         self.case = c = case
         self.kind = KIND[c.kind]
         self.dot = c.kind == "dlrm_dot"
@@ -332,6 +338,8 @@ class Built(object):
             W = rng.uniform(-1, 1, (r + 1, c.D)).astype(np.float32)
             W[r] = np.nan
             self.tables.append(W)
+        self.nan_row = list(self.rows)           # per table: the index of its all-NaN row
+        self.poison_row = {}                     # table -> the index of its first poison row
         self.w = {}
 
         def mlp(which, ln):
@@ -353,10 +361,24 @@ class Built(object):
         last = c.task if self.kind == N.MODEL_MTWND else c.top
         self.sigmoid_top = len(last) - 1 if (self.kind != N.MODEL_NCF and last[-1] < 8) else -1
         self.ln_bot = list(c.bot) if self.kind != N.MODEL_NCF else [1]
+        if poison:
+            # (a stream of its own, after everything else is drawn: the clean model is the one the boundary tests build)
+            prng = np.random.RandomState(zlib.crc32(("poison " + c.name).encode()) % (1 << 31))
+            for t in self.poison_tables():
+                P = poison_rows(prng, c.D)
+                self.poison_row[t] = self.rows[t]
+                self.nan_row[t] = self.rows[t] + len(P)
+                self.tables[t] = np.ascontiguousarray(np.concatenate([self.tables[t][:-1], P, self.tables[t][-1:]]))
 
     # -- the engine's view ---------------------------------------------------------------------------------------------------
     def table_rows(self):
-        return [r + 1 for r in self.rows]
+        return [int(W.shape[0]) for W in self.tables]
+
+    def poison_tables(self):
+        """the tables that carry poison rows, in the order the hot samples take them: NCF one of the concatenated pair (the MLP
+        branch's input: its 5th hot sample, `huge`, can overflow there -- K = 2 D) and one of the summed pair (rule 11's join);
+        every other model its last table (DLRM-dot: the last pairs of the interaction)"""
+        return (2, 0) if self.kind == N.MODEL_NCF else (self.case.T - 1,)
 
     def stage(self, bs):
         """(dense, idx, lens) of the whole staged batch with everything beyond row bs poisoned: NaN dense rows, bags of the NaN row"""
@@ -368,7 +390,7 @@ class Built(object):
         idx = []
         for t in range(c.T):
             i = self.idx[t].copy()
-            i[bs * c.L:] = self.rows[t]
+            i[bs * c.L:] = self.nan_row[t]
             idx.append(i)
         return dense, idx, self.lens
 
@@ -498,3 +520,74 @@ class Float64Ops(object):
     dot = staticmethod(dot64)
     cat = staticmethod(lambda xs: np.concatenate([np.asarray(x, np.float64) for x in xs], axis=1))
     add = staticmethod(lambda a, b: np.asarray(a, np.float64) + np.asarray(b, np.float64))
+
+
+# ---- the poison layout (tests/test_mlp_nonfinite_cpu.py, tests/test_mlp_nonfinite.py) ------------------------------------------
+HOT = (0, 15, 16, 31, 32, 63, 64)            # ... and bs - 1: both sides of every 16-, 32- and 64-row tile edge
+KINDS = ("nan", "pinf", "ninf", "both", "huge")
+HUGE = 3e38                                  # finite in fp32 (max 3.4028e38); a sum of two of one sign is not
+# the poison rows of a table, in this order: (kind, variant); variant 0 plants a single element in column 0, variant 1 in the
+# last column; "both": +inf in column 0 and -inf in the last column (variant 0) or the other way round (variant 1)
+POISON_ROWS = (("nan", 0), ("nan", 1), ("pinf", 0), ("pinf", 1), ("ninf", 0), ("ninf", 1), ("both", 0), ("both", 1), ("huge", 0))
+
+
+def plant(row, kind, variant, rng):
+    """plant `kind` into the carrier `row` (a dense row, a table row), in place"""
+    at = 0 if variant == 0 else row.size - 1
+    if kind == "nan":
+        row[at] = np.nan
+    elif kind == "pinf":
+        row[at] = np.inf
+    elif kind == "ninf":
+        row[at] = -np.inf
+    elif kind == "both":
+        assert row.size >= 2
+        row[at], row[row.size - 1 - at] = np.inf, -np.inf
+    else:
+        row[:] = np.where(rng.randint(0, 2, row.size) > 0, HUGE, -HUGE).astype(np.float32)
+
+
+def poison_rows(rng, D):
+    P = rng.uniform(-1, 1, (len(POISON_ROWS), D)).astype(np.float32)
+    for j, (kind, variant) in enumerate(POISON_ROWS):
+        plant(P[j], kind, variant, rng)
+    return P
+
+
+def hot_samples(bs):
+    return sorted({s for s in HOT + (bs - 1,) if s < bs})
+
+
+def poisoned(net, bs):
+    """-> a copy of `net` (a Built(case, poison=True)) whose staged inputs (.dense, .idx, .lens: what stage_batch, compose and
+    oracle_forward read) hold the poison layout of a query of bs samples, with
+        .hot   bool[bs]: the poisoned samples -- hot_samples(bs)
+        .hot_kind  per sample its kind (None: clean), .hot_route "dense" | "table" | None
+    The hot samples, numbered 1, 2, ... in order, take KINDS in turn.  A model with a dense input carries the poison of the
+    odd-numbered ones (the 1st, 3rd, ...: nan, ninf, huge, pinf) in that sample's dense row, single elements alternately in
+    column 0 and in the last column; every even-numbered one, and every hot sample of NCF, names a poison row (POISON_ROWS)
+    in the last place of one bag: the model's poisoned table, for NCF alternately table 2 (concatenated with table 3) and table 0
+    (summed with table 1).  Rows beyond bs are as Built.stage leaves them."""
+    c = net.case
+    assert net.poison_row, "Built(case, poison=True)"
+    rng = np.random.RandomState(zlib.crc32(("hot %d " % bs + c.name).encode()) % (1 << 31))
+    out = copy.copy(net)
+    out.dense, out.idx, out.lens = net.stage(bs)
+    out.hot = np.zeros(bs, bool)
+    out.hot_kind, out.hot_route = [None] * bs, [None] * bs
+    tabs = net.poison_tables()
+    n_dense = n_table = 0
+    for p, s in enumerate(hot_samples(bs)):
+        kind = KINDS[p % len(KINDS)]
+        out.hot[s], out.hot_kind[s] = True, kind
+        if net.m_den and p % 2 == 0:
+            out.hot_route[s] = "dense"
+            plant(out.dense[s], kind, n_dense % 2, rng)
+            n_dense += kind != "huge"
+        else:
+            out.hot_route[s] = "table"
+            t = tabs[n_table % len(tabs)]
+            variant = 0 if kind == "huge" else (n_table // len(tabs)) % 2
+            out.idx[t][s * c.L + c.L - 1] = net.poison_row[t] + POISON_ROWS.index((kind, variant))
+            n_table += 1
+    return out

@@ -16,7 +16,8 @@ with no measured tolerance: the engine's output is bit-identical to the same for
 the same handle, and every bf16 layer of that composition meets the bound on the input it actually got.
 
 ReLU maps a NaN to 0 in every FC kernel of this library (v > 0 ? v : 0, fp32 and bf16 alike), so "NaN in -> NaN out" is
-checked without activation and through the sigmoid.
+checked without activation and through the sigmoid.  (The fp32 forms are held to that rule, every one of them, by
+tests/test_mlp_nonfinite.py; stream4_kernel's fmaxf(v, 0.f) gives the same 0.)
 
 profiles/r09_bf16_mlp.md records what DRS_BF16_REPORT=<file> makes these tests write: per shape the largest measured
 fraction of the bound, per model the largest difference from the fp32 engine.
