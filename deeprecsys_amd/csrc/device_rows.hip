@@ -147,20 +147,14 @@ hipError_t launch_copy_rows_strided(const void* src, int64_t src_stride, void* d
   return hipGetLastError();
 }
 
-// the device buffers of one call, allocated and freed inside it (as engine_rows.hip's RowStage): the status word, the
+// the device buffers of one call, allocated inside it and freed when it returns, however it returns (as engine_rows.hip's RowStage): the status word, the
 // de-duplication table and the winner mask, the chunk's rows side by side and packed in the table's type
 struct DeviceRowStage {
-  RowStatus* status = nullptr;
-  uint64_t* slots = nullptr;
-  uint8_t* mask = nullptr;
-  void* side = nullptr;
-  void* packed = nullptr;
-  hipEvent_t ev = nullptr;
-  ~DeviceRowStage() {
-    if (ev) (void)hipEventDestroy(ev);
-    for (void* p : {(void*)status, (void*)slots, (void*)mask, side, packed})
-      if (p) (void)hipFree(p);
-  }
+  DeviceBuf<RowStatus> status;
+  DeviceBuf<uint64_t> slots;
+  DeviceBuf<uint8_t> mask;
+  DeviceBuf<void> side, packed;
+  Event ev;
 };
 
 int64_t chunk_rows(int64_t n, int64_t D) { return std::min<int64_t>(n, std::max<int64_t>(((int64_t)16 << 20) / D, 1)); }
@@ -194,10 +188,11 @@ int32_t check_device_rows(drs_engine* e, const char* what, int32_t t, int64_t n,
 
 // the stream every pass of a call runs on, behind the caller's stream where the call is ordered
 int32_t pass_stream(drs_engine* e, DeviceRowStage& st, void* stream, int32_t ordered, hipStream_t* out) {
-  if (!e->stream_h2d) HIP_TRY(e, hipStreamCreateWithFlags(&e->stream_h2d, hipStreamNonBlocking));
+  int32_t rc;
+  if ((rc = copy_stream(e))) return rc;
   if (ordered) {
     // the engine's streams are non-blocking: the edge from the caller's stream (the null stream too) is an event
-    HIP_TRY(e, hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+    HIP_TRY(e, st.ev.create(hipEventDisableTiming));
     HIP_TRY(e, hipEventRecord(st.ev, static_cast<hipStream_t>(stream)));
     HIP_TRY(e, hipStreamWaitEvent(e->stream_h2d, st.ev, 0));
   }
@@ -255,11 +250,11 @@ int32_t drs_update_rows_device(drs_handle e, int32_t t, int64_t n, const int64_t
 
   DeviceRowStage st;
   hipStream_t s = nullptr;
-  HIP_TRY(e, hipMalloc(&st.status, sizeof(RowStatus)));
-  HIP_TRY(e, hipMalloc(&st.slots, sizeof(uint64_t) * (size_t)cap));
-  HIP_TRY(e, hipMalloc(&st.mask, (size_t)n));
-  if (!direct) HIP_TRY(e, hipMalloc(&st.packed, (size_t)(chunk * S)));
-  if (!direct && !tight) HIP_TRY(e, hipMalloc(&st.side, (size_t)(chunk * D * elem)));
+  HIP_TRY(e, st.status.alloc(1));
+  HIP_TRY(e, st.slots.alloc((size_t)cap));
+  HIP_TRY(e, st.mask.alloc((size_t)n));
+  if (!direct) HIP_TRY(e, st.packed.alloc((size_t)(chunk * S)));
+  if (!direct && !tight) HIP_TRY(e, st.side.alloc((size_t)(chunk * D * elem)));
   if ((rc = pass_stream(e, st, stream, ordered, &s))) return rc;
 
   // passes 1 and 2 over the whole call
@@ -287,7 +282,7 @@ int32_t drs_update_rows_device(drs_handle e, int32_t t, int64_t n, const int64_t
     }
     if (!tight) {
       HIP_TRY(e, launch_copy_rows_strided(src, stride, st.side, D, c, (int)D, elem, s));
-      src = static_cast<char*>(st.side);
+      src = static_cast<char*>(st.side.get());
     }
     // the chunk as c rows of a plain-layout table of the arena's type (a row that loses is converted too, and never placed)
     HIP_TRY(e, launch_convert_rows(TableSide{src, val_dtype}, TableSide{st.packed, dt, 0, mul}, RowWindow{0, c, c}, (int)D, s));
@@ -316,9 +311,9 @@ int32_t drs_get_rows_device(drs_handle e, int32_t t, int64_t n, const int64_t* d
 
   DeviceRowStage st;
   hipStream_t s = nullptr;
-  HIP_TRY(e, hipMalloc(&st.status, sizeof(RowStatus)));
-  if (!direct) HIP_TRY(e, hipMalloc(&st.packed, (size_t)(chunk * S)));
-  if (!direct && !tight) HIP_TRY(e, hipMalloc(&st.side, sizeof(float) * (size_t)(chunk * D)));
+  HIP_TRY(e, st.status.alloc(1));
+  if (!direct) HIP_TRY(e, st.packed.alloc((size_t)(chunk * S)));
+  if (!direct && !tight) HIP_TRY(e, st.side.alloc(sizeof(float) * (size_t)(chunk * D)));
   if ((rc = pass_stream(e, st, stream, ordered, &s))) return rc;
 
   // pass 1, the check alone; its verdict on the host before anything touches d_V

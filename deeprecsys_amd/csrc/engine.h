@@ -2,7 +2,11 @@
 // sls.hip / mlp.hip / gemm.hip.  One engine = one GPU = one process (accelInferenceEngine
 // counterpart, reference accelInferenceEngine.py:18-86).
 //
-// HBM layout (all hipMalloc'ed once in drs_create / first use):
+// Ownership: every GPU resource of the handle (device and pinned memory, streams, events) sits in an owning type of
+// hip_owned.h, allocated in drs_create or on first use, freed by its destructor; a raw pointer views memory something else
+// owns (dm_out, dm_span, a Batch's pointers).  An object owns or views, never both, and drs_destroy is quiesce, then delete
+// (DESIGN.md 2).  The exception: the table arenas (Arena below), copyable handle structs paired by arena_alloc / arena_free.
+// HBM layout:
 //   tables   one arena, rows row-major ("table_dtype": rows*D fp32, fp16 or bf16, table t at a 64-element aligned offset;
 //            int8 rowwise: rows of round_up(D, 8) + 8 bytes, table t at a 256-byte aligned offset; "table_int8_lines" 1:
 //            128 / S rows to a 128-byte line where S does not divide 128; int4 rowwise: rows of round_up(D / 2, 4) + 4
@@ -31,7 +35,8 @@
 // handing back each query's top-k rows: the top-k pass launch, and drs_topk_rows).  engine_host.h: the worker pool and the
 // launcher thread of the per-call input path.  input_block.h: the per-call input block's layout, the host pass that
 // fills one and the copies that move it (plain C++: a host program can build it alone).  weight_plan.h: the plan of the
-// per-sample weights a device set may carry (include/drs_device_weights.h), plain C++ likewise.
+// per-sample weights a device set may carry (include/drs_device_weights.h), plain C++ likewise.  hip_owned.h: the owning handle
+// types; model_shape.h: the per-model shape algebra drs_create starts from (both plain C++ over what HIP supplies).
 #pragma once
 #include <immintrin.h>
 #include <sched.h>
@@ -48,6 +53,8 @@
 
 #include "drs_internal.h"
 #include "input_block.h"
+#include "hip_owned.h"
+#include "model_shape.h"
 
 #include <condition_variable>
 #include <functional>
@@ -73,25 +80,32 @@ struct Layer {
   int32_t m = 0, n = 0;  // W is [m, n]
   bool set = false;
   bool packed = false;   // a packed twin (MFMA operand order, mlp.hip) follows W in the arena
-  uint16_t* Wb = nullptr;  // "mlp_dtype" 2, K >= 64 and N >= 64: the bf16 twin [m, bf16_kpad(n)] (an allocation of its own)
+  DeviceBuf<uint16_t> Wb;  // "mlp_dtype" 2, K >= 64 and N >= 64: the bf16 twin [m, bf16_kpad(n)] (an allocation of its own)
 };
 
-struct Mlp {
-  std::vector<int32_t> ln;
-  std::vector<Layer> layers;  // ln.size()-1
-  int32_t sigmoid_layer = -1; // 1-based, -1 none
+struct Mlp : MlpShape {       // ln, sigmoid_layer (model_shape.h) ...
+  std::vector<Layer> layers;  // ... and the ln.size()-1 layers
+  void shape(const MlpShape& s) { MlpShape::operator=(s); layers.resize(ln.empty() ? 0 : ln.size() - 1); }
 };
 
+// A batch as the launches read it: pointers into storage something else owns (a staged batch's BatchMem, a slot's pinned
+// or HBM block, its weight blocks) and what the host knows of the contents.
 struct Batch {
   float* dense = nullptr;
   int32_t* idx = nullptr;
   int32_t* off = nullptr;
-  float* wgt = nullptr;        // [T, cap] per-sample weights, laid out like idx (drs_stage_batch_weights; allocated on first use)
+  float* wgt = nullptr;        // [T, cap] per-sample weights, laid out like idx (drs_stage_batch_weights)
   bool weighted = false;       // ... and whether the staged batch carries them (drs_stage_batch drops them)
   int32_t n_samples = 0;
   int32_t uniform_len = -1;    // all bags of all tables have this length, else -1
   std::vector<int32_t> h_off;  // [T][off_stride] host copy (gather_bytes, validation): BlockLayout::h_off_at
   bool staged = false;
+};
+// the storage of a staged batch or of a slot's scratch batch, beside the Batch that views it (wgt: on first use)
+struct BatchMem {
+  DeviceBuf<float> dense;
+  DeviceBuf<int32_t> idx, off;
+  DeviceBuf<float> wgt;
 };
 // a batch whose inputs are the block at `base` (a device address): zc, dc and every mq[i]
 inline void view_as(Batch& b, const BlockLayout& L, void* base) {
@@ -104,50 +118,51 @@ struct Slot {
   bool split_last = false;        // the set in flight read its dense columns in place ("gemm_split"): s.T holds none
   hipStream_t stream = nullptr;   // the stream the job in flight launches its MLP side on
   hipStream_t base_stream = nullptr;   // ... as assigned by apply_stream_mode (shared or own)
-  hipStream_t own_stream = nullptr;
-  hipStream_t early_stream = nullptr;    // "mlp_early": the MLP launch of a small set whose gather runs on own_stream
-  uint32_t* d_gflag = nullptr;           // ... and the word that launch polls: seq, written by a stream-ordered write behind the gather
+  Stream own_stream;
+  Stream early_stream;                   // "mlp_early": the MLP launch of a small set whose gather runs on own_stream
+  DeviceBuf<uint32_t> d_gflag;           // ... and the word that launch polls: seq, written by a stream-ordered write behind the gather
   hipStream_t gather_stream = nullptr;   // where the gather is launched (== stream unless pipelined)
   hipStream_t cur = nullptr;             // "mlp_layout" 1: the stream the set's latest MLP launch went on
-  hipEvent_t ev_k[4] = {nullptr, nullptr, nullptr, nullptr};   // ... events that order a set's launches across the two kinds of stream
+  Event ev_k[4];   // ... events that order a set's launches across the two kinds of stream
   int n_ev = 0;
-  hipEvent_t ev_sls = nullptr;           // pipelined mode: gather done -> the MLP stream may go on
-  hipEvent_t ev_dma = nullptr;           // "out_dma": last kernel done -> the copy stream may take the outputs
+  Event ev_sls;                          // pipelined mode: gather done -> the MLP stream may go on
+  Event ev_dma;                          // "out_dma": last kernel done -> the copy stream may take the outputs
   bool on_dma = false;                   // ... the job in flight hands over through the copy stream
-  hipEvent_t ev_in = nullptr;            // pipelined mode: per-call inputs copied -> the gather may start
+  Event ev_in;                           // pipelined mode: per-call inputs copied -> the gather may start
   // device outputs (engine_device_outputs.hip): the caller's stream has reached the call -> the input pass may start; the
   // output pass has finished -> the caller's stream may go on, and wait_slot may hand the slot (and its d_out) to the next set
-  hipEvent_t ev_caller = nullptr, ev_out = nullptr;
+  Event ev_caller, ev_out;
   bool out_pass = false;                 // ... the set in flight has an output pass behind its last kernel (enqueue_forward resets it)
   Batch zc;                              // per-call inputs read in place from host-mapped pinned memory
-  float* T = nullptr;        // [max_batch, ldT]  concat buffer: dense_out | emb_0 | ...
-  float* R = nullptr;        // [max_batch, ldR]  dot-interaction output (dot only)
-  float* H = nullptr;        // [max_batch, ldH]  inter-segment MLP scratch (ping)
-  float* Hb = nullptr;       // (pong)
-  float* H2 = nullptr;       // NCF: concat(mf, mlp_out)
-  float* H3 = nullptr;       // MT-WnD: output of the shared top MLP (input of every task head)
-  float* d_out = nullptr;    // [max_batch*n_out] device outputs (copy path only)
-  uint32_t* d_err = nullptr; // device error word (kErrIndex: index out of range | kErrMlpEarly | kErrLengths: the device input pass's length ENFORCEs)
-  uint32_t* d_counter = nullptr;  // arrival counter of the completion hand-off
-  float* xbuf = nullptr;          // stream4_kernel's column-split form: exchange buffer [xrows, xcols] of the split layer's outputs ...
-  uint32_t* xcnt = nullptr;       // ... and one arrival ticket per 16-row slab (zero between launches)
+  DeviceBuf<float> T;        // [max_batch, ldT]  concat buffer: dense_out | emb_0 | ...
+  DeviceBuf<float> R;        // [max_batch, ldR]  dot-interaction output (dot only)
+  DeviceBuf<float> H;        // [max_batch, ldH]  inter-segment MLP scratch (ping)
+  DeviceBuf<float> Hb;       // (pong)
+  DeviceBuf<float> H2;       // NCF: concat(mf, mlp_out)
+  DeviceBuf<float> H3;       // MT-WnD: output of the shared top MLP (input of every task head)
+  DeviceBuf<float> d_out;    // [max_batch*n_out] device outputs (copy path only)
+  DeviceBuf<uint32_t> d_err; // device error word (kErrIndex: index out of range | kErrMlpEarly | kErrLengths: the device input pass's length ENFORCEs)
+  DeviceBuf<uint32_t> d_counter;  // arrival counter of the completion hand-off
+  DeviceBuf<float> xbuf;          // stream4_kernel's column-split form: exchange buffer [xrows, xcols] of the split layer's outputs ...
+  DeviceBuf<uint32_t> xcnt;       // ... and one arrival ticket per 16-row slab (zero between launches)
   int64_t xrows = 0;
   int32_t xcols = 0;
-  uint32_t* h_out = nullptr; // pinned host: [flag | err | outputs...]
+  PinnedBuf<uint32_t> h_out; // pinned host: [flag | err | outputs...]
   uint32_t* dm_out = nullptr;// the same memory as seen from the device (zero-copy path)
   uint32_t seq = 0;          // sequence number of the query in flight on this slot
-  uint64_t* d_ts = nullptr;  // [2 * max gather workgroups] device clock stamps (profiling)
+  DeviceBuf<uint64_t> d_ts;  // [2 * max gather workgroups] device clock stamps (profiling)
   std::vector<uint64_t> h_ts;
   int64_t ts_blocks = 0, ts_blocks_done = 0;
-  uint64_t* d_span_acc = nullptr;  // device [2]: running (min, max) of the stamps
-  uint64_t* h_span = nullptr;  // pinned [2]: (min start, max end) of the gather launch
+  DeviceBuf<uint64_t> d_span_acc;  // device [2]: running (min, max) of the stamps
+  PinnedBuf<uint64_t> h_span;  // pinned [2]: (min start, max end) of the gather launch
   uint64_t* dm_span = nullptr;
-  Batch scratch;             // drs_forward_inputs staging
-  char* d_stage = nullptr;   // device copy of the staging block (one-DMA-copy input path)
+  Batch scratch;             // drs_forward_inputs staging ...
+  BatchMem scratch_mem;      // ... and its storage
+  DeviceBuf<char> d_stage;   // device copy of the staging block (one-DMA-copy input path)
   Batch dc;                  // ... viewed as a batch: [dense | idx | off]
-  void* h_stage = nullptr;   // pinned host staging for forward_inputs
+  PinnedBuf<char> h_stage;   // pinned host staging for forward_inputs
   size_t h_stage_bytes = 0;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  Event ev[3];
   bool ev_pending = false;
   int64_t ts_bytes = 0;      // algorithmic bytes of the gather launch being timed
   int32_t last_bs = 0;       // total valid samples of the job in flight
@@ -159,13 +174,13 @@ struct Slot {
   // per-call inputs of a whole launch set (drs_run_queues_multi_async; allocated on first use):
   // DRS_MAX_COALESCE blocks [dense | idx | off] back to back in ONE pinned allocation and their
   // twins in ONE HBM allocation, so that a set's inputs cross the bus in one DMA copy
-  char* h_multi = nullptr;
-  char* d_multi = nullptr;   // (BlockLayout::padded bytes from one block to the next)
+  PinnedBuf<char> h_multi;
+  DeviceBuf<char> d_multi;   // (BlockLayout::padded bytes from one block to the next)
   std::vector<Batch> mq;    // block i viewed as a batch (device pointers into d_multi)
   // per-sample weights of a device set (drs_run_queues_device_weighted_multi_async): DRS_MAX_COALESCE blocks of [T, cap]
-  // fp32 in ONE allocation, made when the slot first sees a weighted set and kept until drs_destroy; mq[i].wgt points at
+  // fp32 in ONE allocation, made when the slot first sees a weighted set and kept as long as the slot; mq[i].wgt points at
   // block i while mq[i].weighted, which every path that fills mq sets or clears
-  float* d_wgt = nullptr;
+  DeviceBuf<float> d_wgt;
   int32_t launch_rc = 0;     // status of the launches the launcher thread made for the job in flight
   std::string launch_err;
   DispatchLog dlog = {{0}, 0};   // what the launch functions chose for the set last enqueued here (drs_last_dispatch)
@@ -220,10 +235,10 @@ struct drs_engine {
   int64_t vmm_chunk = -1;           // bytes of physical memory per handle (0: one handle | -1: 1 GiB handles from 1 GiB on, else one); rounded up to whole 2 MiB pages
   int64_t vmm_align = 0;            // alignment of the reserved address range (0: the allocation granularity)
   // arena_alloc_selected: scratch of the gather probe and what the last selection saw
-  int32_t* probe_idx = nullptr;
-  float* probe_out = nullptr;
-  int64_t* probe_tab = nullptr;
-  int32_t* probe_err = nullptr;
+  DeviceBuf<int32_t> probe_idx;
+  DeviceBuf<float> probe_out;
+  DeviceBuf<int64_t> probe_tab;
+  DeviceBuf<int32_t> probe_err;
   int64_t probe_rows = 0;
   int32_t probe_bags = 0, probe_L = 0;
   int64_t sel_want_pool = 0;        // "table_select_pool": chunks the next selection allocates (0: 2 n + 8)
@@ -233,28 +248,27 @@ struct drs_engine {
   int probe_windows = 0, probe_sorted = 0, probe_row_bytes = 256, probe_nt = 1, probe_loads = 20;
   int64_t probe_ps = 0;             // result of the last "table_probe_latency": picoseconds per dependent load
   int vmm_shuffle = 0;              // lab: map the chunks in a permuted order (neighbouring addresses, distant memory)
-  int64_t* d_tab_off = nullptr;
-  int64_t* d_tab_rows = nullptr;
+  DeviceBuf<int64_t> d_tab_off, d_tab_rows;
   // "table_dtype" 4 (fp8 e4m3): each table's scale exponent k (drs_table_fp8_exponent; 0 under every other type), its
   // 2^-k on the device (SlsArgs::tab_scale), and the word the device absmax reduction of a conversion lands in
   std::vector<int32_t> fp8_k;
-  float* d_tab_scale = nullptr;
-  uint32_t* d_absmax = nullptr;
+  DeviceBuf<float> d_tab_scale;
+  DeviceBuf<uint32_t> d_absmax;
   std::vector<bool> table_set;
   Mlp bot, top, fin;
   std::vector<Mlp> tasks;        // MT-WnD task heads
   std::vector<Mlp> att;          // DIN attention units (one small MLP per behaviour table)
-  const float** d_att = nullptr; // device: 4 pointers per unit (W1, b1, W2, b2) ...
-  float* d_att_packed = nullptr; // ... and the units' weights packed for the DIN kernels (din.hip)
+  DeviceBuf<const float*> d_att; // device: 4 pointers per unit (W1, b1, W2, b2) ...
+  DeviceBuf<float> d_att_packed; // ... and the units' weights packed for the DIN kernels (din.hip)
   bool att_dirty = true;         // a unit's weights changed since the last pack
   bool din_any = false;          // DIN: units din.hip has no form for (depth != 2, wide hidden layer, D not 4 k <= 256) -> din_any.hip
   int din_maxw = 0;              // ... their widest hidden layer
-  int32_t* d_att_ln = nullptr;   // ... and the units' widths on the device
+  DeviceBuf<int32_t> d_att_ln;   // ... and the units' widths on the device
   int dien_fuse_top = 1;         // DIEN: the top MLP inside the recurrence's launch when it fits (dien.hip dien_top_fusable)
   int dien_mfma = 2;             // DIEN recurrence on the matrix cores, 16 samples per workgroup: 2 = one wave set per layer | 1 = every wave both layers | 0 one wave per sample (VALU) | 3 the any-shape form (din_any.hip)
   int din_fused = 1;             // gather + attention units + Concat in one launch (default mode)
   std::vector<Mlp> rnn;          // DIEN: the two BasicRNN layers, each {i2h, gates_t}; packed into d_att_packed
-  float* w_arena = nullptr;      // all FC weights + biases in ONE allocation (large pages: the
+  DeviceBuf<float> w_arena;      // all FC weights + biases in ONE allocation (large pages: the
   size_t w_arena_floats = 0;     // MLP kernels' per-CU TLBs then hold every weight page)
   size_t w_arena_used = 0;
   int32_t interaction_op = DRS_INTERACT_CAT, itself = 0;
@@ -264,20 +278,21 @@ struct drs_engine {
   int64_t ldT = 0, ldR = 0, ldH = 0, cap = 0;
   BlockLayout blk;               // a batch's / per-call input block's [dense | idx | off] (set in drs_create before the slots are built)
   int64_t max_rows = 0;          // virtual rows of a slot's activation buffers
-  std::vector<Batch> batches;
+  std::vector<Batch> batches;    // the staged batches ...
+  std::vector<BatchMem> batch_mem;   // ... and the storage of each
   std::vector<Slot> slots;
   // op-level scratch
-  int64_t* d_op_tab = nullptr;   // [2]: tab_off, tab_rows for drs_sls
+  DeviceBuf<int64_t> d_op_tab;   // [2]: tab_off, tab_rows for drs_sls
   // options
   int sls_exact = 0, mlp_split = 1, zero_copy = 1, sls_uniform = 1, shared_stream = 2, mlp_fuse = 1;
   int dispatch_log = 0;             // "dispatch_log": keep the per-slot record of the kernel forms chosen (drs_last_dispatch)
-  hipStream_t stream_g = nullptr;   // shared_stream == 2: all gathers, back to back
-  hipStream_t stream_dma = nullptr; // "out_dma": the copy-engine transfers of the outputs and the flag writes behind them
+  Stream stream_g;                  // shared_stream == 2: all gathers, back to back
+  Stream stream_dma;                // "out_dma": the copy-engine transfers of the outputs and the flag writes behind them
 #ifdef DRS_LAB
-  hipStream_t stream_g2 = nullptr;  // lab ("gather_streams" 2): the gathers of consecutive slots alternate between two streams
+  Stream stream_g2;                 // lab ("gather_streams" 2): the gathers of consecutive slots alternate between two streams
   int gather_streams = 1;
 #endif
-  hipStream_t stream_h2d = nullptr; // input copies of drs_run_queues_multi_async (created on first use)
+  Stream stream_h2d;                // input copies of drs_run_queues_multi_async (created on first use)
   int mlp_streams = 1;              // pipelined mode: streams the MLP launches alternate between (set in drs_create)
   // "mlp_layout" 1 (MLP-bound models, pipelined mode): streams by KERNEL TYPE instead of by launch set -- the
   // gather and every wide-layer GEMM of every set go on stream_g, strictly one after the other (each fills
@@ -352,8 +367,8 @@ inline char* table_ptr(void* base, const std::vector<int64_t>& off, int t, int d
 hipError_t upload_fp8_scales(drs_engine* e);   // fp8_k -> d_tab_scale
 int32_t fail(drs_engine* e, int32_t code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
 int32_t set_device(drs_engine* e);
-int32_t alloc_batch(drs_engine* e, Batch& b);
-void free_batch(Batch& b);
+int32_t alloc_batch(drs_engine* e, Batch& b, BatchMem& mem);   // the three arrays every batch has, and b as their view
+int32_t copy_stream(drs_engine* e);    // stream_h2d, created on first use
 // engine_arena.hip
 hipError_t arena_map(const Arena& a, float* at, int device);
 void arena_free(Arena& a);

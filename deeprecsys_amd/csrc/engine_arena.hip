@@ -45,6 +45,7 @@ hipError_t arena_map(const Arena& a, float* at, int device) {
 
 void arena_free(Arena& a) {
   if (!a.p) { a = Arena(); return; }
+  count_live(-1);
   if (a.kind == 0) {
     (void)hipFree(a.p);
   } else {
@@ -72,7 +73,6 @@ hipError_t probe_gather(drs_engine* e, const float* base, size_t bytes, double* 
   if (rows < L || rows >= (1ll << 31)) return hipErrorInvalidValue;
   hipError_t r = hipSuccess;
   if (!e->probe_idx || e->probe_rows != rows || e->probe_L != L) {
-    if (e->probe_idx) { (void)hipFree(e->probe_idx); e->probe_idx = nullptr; }
     std::vector<int32_t> idx((size_t)bags * L);
     uint32_t z = 0x2545F491u;
     for (int b = 0; b < bags; ++b)
@@ -81,11 +81,11 @@ hipError_t probe_gather(drs_engine* e, const float* base, size_t bytes, double* 
         const int64_t lo = rows * j / L, hi = rows * (j + 1) / L;
         idx[(size_t)b * L + j] = (int32_t)(lo + (int64_t)(z % (uint32_t)(hi > lo ? hi - lo : 1)));
       }
-    if ((r = hipMalloc(&e->probe_idx, sizeof(int32_t) * idx.size())) != hipSuccess) return r;
+    if ((r = e->probe_idx.alloc(idx.size())) != hipSuccess) return r;
     if ((r = hipMemcpy(e->probe_idx, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice)) != hipSuccess) return r;
-    if (!e->probe_out && (r = hipMalloc(&e->probe_out, sizeof(float) * (size_t)bags * D)) != hipSuccess) return r;
-    if (!e->probe_tab && (r = hipMalloc(&e->probe_tab, sizeof(int64_t) * 2)) != hipSuccess) return r;
-    if (!e->probe_err && (r = hipMalloc(&e->probe_err, sizeof(int32_t))) != hipSuccess) return r;
+    if (!e->probe_out && (r = e->probe_out.alloc((size_t)bags * D)) != hipSuccess) return r;
+    if (!e->probe_tab && (r = e->probe_tab.alloc(2)) != hipSuccess) return r;
+    if (!e->probe_err && (r = e->probe_err.alloc(1)) != hipSuccess) return r;
     const int64_t tab[2] = {0, rows};
     if ((r = hipMemcpy(e->probe_tab, tab, sizeof tab, hipMemcpyHostToDevice)) != hipSuccess) return r;
     if ((r = hipMemset(e->probe_err, 0, sizeof(int32_t))) != hipSuccess) return r;
@@ -101,9 +101,8 @@ hipError_t probe_gather(drs_engine* e, const float* base, size_t bytes, double* 
   Tune t = e->tune;
   t.log = nullptr;
   const SlsPlan plan = plan_sls(a, false, L <= e->sls_short_bag, t, DRS_TABLE_FP32);
-  hipEvent_t e0, e1;
-  if ((r = hipEventCreate(&e0)) != hipSuccess) return r;
-  if ((r = hipEventCreate(&e1)) != hipSuccess) { (void)hipEventDestroy(e0); return r; }
+  Event e0, e1;
+  if ((r = e0.create()) != hipSuccess || (r = e1.create()) != hipSuccess) return r;
   const int warm = 2, reps = 6;
   for (int i = 0; i < warm + reps && r == hipSuccess; ++i) {
     if (i == warm) r = hipEventRecord(e0, nullptr);
@@ -114,8 +113,6 @@ hipError_t probe_gather(drs_engine* e, const float* base, size_t bytes, double* 
   float ms = 0.f;
   if (r == hipSuccess) r = hipEventElapsedTime(&ms, e0, e1);
   if (r == hipSuccess) *us = (double)ms * 1e3 / reps;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   return r;
 }
 
@@ -204,8 +201,15 @@ hipError_t arena_alloc_selected(drs_engine* e, size_t bytes, Arena* out) {
 
 #endif  // DRS_LAB
 // `bytes` of device memory for the tables, built as e->table_alloc / vmm_* say.  On failure nothing stays
-// allocated and *out is empty.
+// allocated and *out is empty.  (An arena is a plain handle struct, freed by arena_free alone; the pair keeps the count of
+// live objects that hip_owned.h's types keep for themselves.)
+static hipError_t arena_build(drs_engine* e, size_t bytes, Arena* out);
 hipError_t arena_alloc(drs_engine* e, size_t bytes, Arena* out) {
+  const hipError_t r = arena_build(e, bytes, out);
+  if (r == hipSuccess) count_live(1);
+  return r;
+}
+static hipError_t arena_build(drs_engine* e, size_t bytes, Arena* out) {
   *out = Arena();
 #ifdef DRS_LAB
   if (e->table_alloc == 3) {

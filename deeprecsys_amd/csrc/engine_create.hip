@@ -72,29 +72,26 @@ std::vector<Mlp*> served_mlps(drs_engine* e) {
 
 hipError_t build_bf16_twin(Layer& L) {
   const bool fresh = !L.Wb;
-  hipError_t r = fresh ? hipMalloc(&L.Wb, sizeof(uint16_t) * (size_t)L.m * bf16_kpad(L.n)) : hipSuccess;
-  if (r != hipSuccess) { L.Wb = nullptr; return r; }
+  hipError_t r = fresh ? L.Wb.alloc((size_t)L.m * bf16_kpad(L.n)) : hipSuccess;
+  if (r != hipSuccess) return r;
   r = launch_bf16_twin(L.W, L.n, L.m, L.Wb, nullptr);
   if (r == hipSuccess) r = hipStreamSynchronize(nullptr);
-  if (r != hipSuccess && fresh) { (void)hipFree(L.Wb); L.Wb = nullptr; }
+  if (r != hipSuccess && fresh) L.Wb.reset();
   return r;
 }
 
-int32_t alloc_batch(drs_engine* e, Batch& b) {
-  if (e->m_den > 0)
-    HIP_TRY(e, hipMalloc(&b.dense, sizeof(float) * (size_t)e->max_batch * e->m_den));
-  HIP_TRY(e, hipMalloc(&b.idx, e->blk.idx_bytes));
-  HIP_TRY(e, hipMalloc(&b.off, e->blk.off_bytes));
+int32_t alloc_batch(drs_engine* e, Batch& b, BatchMem& mem) {
+  if (e->m_den > 0) HIP_TRY(e, mem.dense.alloc((size_t)e->max_batch * e->m_den));
+  HIP_TRY(e, mem.idx.alloc(e->blk.idx_elems()));
+  HIP_TRY(e, mem.off.alloc(e->blk.off_elems()));
+  b.dense = mem.dense; b.idx = mem.idx; b.off = mem.off;
   b.h_off.assign(e->blk.off_elems(), 0);
   return DRS_OK;
 }
 
-void free_batch(Batch& b) {
-  if (b.dense) (void)hipFree(b.dense);
-  if (b.idx) (void)hipFree(b.idx);
-  if (b.off) (void)hipFree(b.off);
-  if (b.wgt) (void)hipFree(b.wgt);
-  b = Batch();
+int32_t copy_stream(drs_engine* e) {
+  if (!e->stream_h2d) HIP_TRY(e, e->stream_h2d.create(hipStreamNonBlocking));
+  return DRS_OK;
 }
 
 }  // namespace eng
@@ -240,6 +237,155 @@ size_t drs::eng::table_layout(const drs_engine* e, int dtype, std::vector<int64_
   }
   return (size_t)o * (size_t)table_unit_bytes(dtype);
 }
+// ---- drs_create, step by step: each allocates into the handle's owning fields and returns a status with its text in e->err;
+// what a failed step leaves half built goes with the handle.  The ORDER of the allocations stays: where things land in HBM is
+// measured behaviour.
+namespace drs {
+namespace eng {
+
+// the config and the model's shape into the handle, and the strides and capacities that follow from them
+static void lay_out(drs_engine* e, const drs_model_cfg& cfg, const ModelShape& m) {
+  const int T = e->T = cfg.num_tables, D = e->D = cfg.sparse_dim;
+  e->kind = cfg.model_kind;
+  e->rows.assign(cfg.table_rows, cfg.table_rows + T);
+  e->interaction_op = cfg.interaction_op; e->itself = cfg.interaction_itself ? 1 : 0;
+  e->max_batch = cfg.max_batch; e->max_lookups = cfg.max_lookups;
+  e->n_batches = cfg.num_staged_batches; e->n_slots = cfg.num_slots > 0 ? cfg.num_slots : 1;
+  e->m_den = m.m_den; e->w0 = m.w0; e->num_int = m.num_int; e->n_out = m.n_out;
+  e->din_any = m.din_any; e->din_maxw = m.din_maxw;
+  e->bot.shape(m.bot); e->top.shape(m.top); e->fin.shape(m.fin);
+  e->tasks.resize((size_t)m.n_tasks);
+  for (auto& tk : e->tasks) tk.shape(m.task);
+  e->att.resize((size_t)m.n_att);
+  for (auto& au : e->att) au.shape(m.att);
+  e->rnn.resize(m.rnn.size());
+  for (size_t i = 0; i < m.rnn.size(); ++i) e->rnn[i].shape(m.rnn[i]);
+  e->cap = (int64_t)e->max_batch * e->max_lookups;
+  e->blk = BlockLayout(e->max_batch, e->m_den, T, e->cap);
+  e->max_rows = (int64_t)DRS_MAX_COALESCE * ((e->max_batch + 63) / 64 * 64);
+  e->ldT = e->kind == DRS_MODEL_NCF ? 4 * D : e->w0 + (int64_t)T * D;   // (DIN: w0 == 0)
+  e->ldR = round_up(e->num_int, 4);
+  int maxw = 4;
+  for (int w : e->bot.ln) maxw = w > maxw ? w : maxw;
+  for (int w : e->top.ln) maxw = w > maxw ? w : maxw;
+  for (auto& tk : e->tasks) for (int w : tk.ln) maxw = w > maxw ? w : maxw;
+  e->ldH = round_up(maxw, 4);
+}
+
+// where the tables start and how many rows each has, on the host and on the device; the fp8 scales (all 1)
+static int32_t build_table_meta(drs_engine* e) {
+  const int T = e->T;
+  e->tables_bytes = table_layout(e, DRS_TABLE_FP32, &e->tab_off);
+  e->table_set.assign(T, false);
+  e->tune.device = e->device;
+  int khz = 0;
+  if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, e->device) == hipSuccess && khz > 0) e->wall_clock_khz = khz;
+  HIP_TRY(e, device_init(e->device, &e->tune.zero));
+  HIP_TRY(e, e->d_tab_off.alloc(T));
+  HIP_TRY(e, e->d_tab_rows.alloc(T));
+  HIP_TRY(e, e->d_op_tab.alloc(2));
+  HIP_TRY(e, hipMemcpy(e->d_tab_off, e->tab_off.data(), sizeof(int64_t) * T, hipMemcpyHostToDevice));
+  HIP_TRY(e, hipMemcpy(e->d_tab_rows, e->rows.data(), sizeof(int64_t) * T, hipMemcpyHostToDevice));
+  e->fp8_k.assign(T, 0);
+  HIP_TRY(e, e->d_tab_scale.alloc(T));
+  HIP_TRY(e, e->d_absmax.alloc(1));
+  HIP_TRY(e, upload_fp8_scales(e));
+  return DRS_OK;
+}
+
+// one slot: its stream, activation and output buffers, events and per-call input blocks
+static int32_t build_slot(drs_engine* e, Slot& s) {
+  const int T = e->T;
+  const size_t rows = (size_t)e->max_rows;
+  HIP_TRY(e, s.own_stream.create(hipStreamNonBlocking));
+  HIP_TRY(e, s.T.alloc(rows * e->ldT));
+  HIP_TRY(e, hipMemset(s.T, 0, sizeof(float) * rows * e->ldT));
+  HIP_TRY(e, s.R.alloc(rows * e->ldR));
+  HIP_TRY(e, hipMemset(s.R, 0, sizeof(float) * rows * e->ldR));
+  HIP_TRY(e, s.H.alloc(rows * e->ldH));
+  HIP_TRY(e, s.Hb.alloc(rows * e->ldH));
+  HIP_TRY(e, s.H2.alloc(rows * (e->num_int + 4)));
+  if (e->kind == DRS_MODEL_MTWND) HIP_TRY(e, s.H3.alloc(rows * e->ldH));
+  const size_t out_words = kOutOffset + rows * (e->kind == DRS_MODEL_NCF ? 1024 : e->n_out);
+  HIP_TRY(e, s.d_out.alloc(out_words));
+  HIP_TRY(e, s.d_err.alloc(1));
+  HIP_TRY(e, s.d_counter.alloc(1));
+#ifdef DRS_LAB
+  // "mlp_early" (lab only): its stream, and the word a RUNNING kernel polls while another stream's write lands in it --
+  // fine-grained memory, so that the write is visible across the XCDs' L2s
+  HIP_TRY(e, s.early_stream.create(hipStreamNonBlocking));
+  HIP_TRY(e, s.d_gflag.alloc(1, hipDeviceMallocFinegrained));
+  HIP_TRY(e, hipMemset(s.d_gflag, 0, sizeof(uint32_t)));
+#endif
+  HIP_TRY(e, hipMemset(s.d_err, 0, sizeof(uint32_t)));
+  HIP_TRY(e, hipMemset(s.d_counter, 0, sizeof(uint32_t)));
+  // column-split MLP launches (mlp.hip NSplit; DLRM's first top layer): up to 4 096 rows of that layer's outputs
+  if (e->kind == DRS_MODEL_DLRM && e->top.ln.size() >= 3 && e->top.ln[1] >= 128 && e->top.ln[1] <= 1024 && !(e->top.ln[1] & 63)) {
+    s.xrows = e->max_rows < 4096 ? e->max_rows : 4096;
+    s.xcols = e->top.ln[1];
+    HIP_TRY(e, s.xbuf.alloc((size_t)s.xrows * s.xcols));
+    HIP_TRY(e, s.xcnt.alloc((size_t)(s.xrows / 16 + 1)));
+    HIP_TRY(e, hipMemset(s.xcnt, 0, sizeof(uint32_t) * (size_t)(s.xrows / 16 + 1)));
+  }
+  // coherent (fine-grained) pinned memory: device stores become visible to a polling CPU
+  HIP_TRY(e, s.h_out.alloc(out_words, hipHostMallocMapped | hipHostMallocCoherent));
+  memset(s.h_out, 0, sizeof(uint32_t) * out_words);
+  HIP_TRY(e, hipHostGetDevicePointer(reinterpret_cast<void**>(&s.dm_out), s.h_out, 0));
+  HIP_TRY(e, s.d_ts.alloc(2 * (rows * T + 8)));   // + 8: the XCD-ordered grid is rounded up to 8
+  HIP_TRY(e, s.d_span_acc.alloc(2 * 65536));
+  HIP_TRY(e, s.h_span.alloc(2, hipHostMallocMapped | hipHostMallocCoherent));
+  s.h_span[0] = s.h_span[1] = 0;
+  HIP_TRY(e, hipHostGetDevicePointer(reinterpret_cast<void**>(&s.dm_span), s.h_span, 0));
+  s.h_ts.resize(2 * (rows * T + 8));
+  for (auto& ev : s.ev) HIP_TRY(e, ev.create());
+  // Cross-stream ordering on ONE device only (no host reader): the kernels' own agent-scope
+  // release/acquire at their boundaries carries the data; the system-scope fence an event
+  // record adds by default costs ~3 us between consecutive gathers (measured: 128 k -> 132 k QPS)
+  for (Event* ev : {&s.ev_sls, &s.ev_dma, &s.ev_in, &s.ev_k[0], &s.ev_k[1], &s.ev_k[2], &s.ev_k[3]})
+    HIP_TRY(e, ev->create(hipEventDisableTiming | hipEventDisableSystemFence));
+  // the two edges to a caller's stream (device outputs): what the caller runs on either side, copies included, is not
+  // the engine's to know, so these keep the default fence
+  for (Event* ev : {&s.ev_caller, &s.ev_out}) HIP_TRY(e, ev->create(hipEventDisableTiming));
+  int32_t rc;
+  if ((rc = alloc_batch(e, s.scratch, s.scratch_mem))) return rc;
+  s.scratch.n_samples = 0;
+  s.h_stage_bytes = e->blk.bytes;
+  HIP_TRY(e, s.h_stage.alloc(s.h_stage_bytes, hipHostMallocMapped));
+  // device view of the same block, laid out like a staged batch: [dense | idx | off]
+  char* dm = nullptr;
+  HIP_TRY(e, hipHostGetDevicePointer(reinterpret_cast<void**>(&dm), s.h_stage, 0));
+  view_as(s.zc, e->blk, dm);
+  // the same layout once more in HBM: target of the one-copy input path
+  HIP_TRY(e, s.d_stage.alloc(s.h_stage_bytes));
+  view_as(s.dc, e->blk, s.d_stage);
+  return DRS_OK;
+}
+
+// the shared streams, the launch forms, and -- last -- the table arena: one hipMalloc (where it lands in HBM, and what
+// DLRM_Net.tune_table_placement does about it: DESIGN.md 5)
+static int32_t build_tail(drs_engine* e) {
+  HIP_TRY(e, e->stream_g.create(hipStreamNonBlocking));
+  HIP_TRY(e, e->stream_dma.create(hipStreamNonBlocking));
+  choose_launch_forms(e);
+  apply_stream_mode(e);
+#ifdef DRS_LAB
+  // lab build, DRS_TABLE_SELECT=1: "table_alloc" 3 (arena_alloc_selected: the fastest gigabytes of a pool by a one-table
+  // run of the model's gather kernel) -- an experiment that did NOT work (profiles/r05_placement/README.md)
+  const char* env = getenv("DRS_TABLE_SELECT");
+  if (env && atoi(env) != 0 && e->kind == DRS_MODEL_DLRM && e->mlp_streams <= 2 && e->max_lookups >= 8 && e->tables_bytes >= ((size_t)1 << 30)) e->table_alloc = 3;
+#endif
+  Arena first;
+  HIP_TRY(e, arena_alloc(e, e->tables_bytes, &first));
+  e->tables = first.p;
+  e->arenas.assign(1, first);
+  return DRS_OK;
+}
+
+struct EngineDestroy { void operator()(drs_engine* e) const { (void)drs_destroy(e); } };
+
+}  // namespace eng
+}  // namespace drs
+
 extern "C" {
 
 int32_t drs_create(const drs_model_cfg* cfg, int32_t device_id, drs_handle* out) {
@@ -260,346 +406,53 @@ int32_t drs_create(const drs_model_cfg* cfg, int32_t device_id, drs_handle* out)
                 r == hipSuccess ? "device count 0" : hipGetErrorString(r));
   if (device_id < 0 || device_id >= ndev) return fail(nullptr, DRS_ERR_BAD_ARG, "device %d of %d", device_id, ndev);
 
-  drs_engine* e = new drs_engine();
+  // a refusal leaves with its text in g_create_error; the handle built so far goes with `e`
+  // (and HIP's own last error cleared: the next launch's hipGetLastError() must not report this call's failed allocation)
+  auto bail = [](int32_t code, const std::string& msg) { g_create_error = msg; (void)hipGetLastError(); return code; };
+  // shape algebra of the reference builders, then what only the kernels can say: do the units / the recurrence fit the LDS?
+  const ModelShape shape = model_shape(*cfg);
+  if (shape.code) return bail(shape.code, shape.msg);
+  // (din.hip's forms: model_shape's din_any; D in {16, 32, 64} with hidden_size in {8, 16, 32, 64}: dien.hip's forms; any
+  // other pair: din_any.hip)
+  if (cfg->model_kind == DRS_MODEL_DIN && shape.din_any && !din_any_fits(D, shape.din_maxw))
+    return bail(DRS_ERR_UNSUPPORTED, "DIN: 4*D + 2*(widest hidden layer of a unit) floats must fit 160 KB of LDS");
+  if (cfg->model_kind == DRS_MODEL_DIEN && !dien_applicable(D, shape.rnn[0].ln[1]) && !dien_any_fits(D, shape.rnn[0].ln[1]))
+    return bail(DRS_ERR_UNSUPPORTED, "DIEN: D + 4*hidden_size floats must fit 160 KB of LDS");
+
+  std::unique_ptr<drs_engine, EngineDestroy> owner(new drs_engine());
+  drs_engine* e = owner.get();
   e->device = device_id;
-  e->kind = cfg->model_kind; e->T = cfg->num_tables; e->D = D;
-  e->rows.assign(cfg->table_rows, cfg->table_rows + e->T);
-  e->interaction_op = cfg->interaction_op; e->itself = cfg->interaction_itself ? 1 : 0;
-  e->max_batch = cfg->max_batch; e->max_lookups = cfg->max_lookups;
-  e->n_batches = cfg->num_staged_batches; e->n_slots = cfg->num_slots > 0 ? cfg->num_slots : 1;
-  e->bot.ln.assign(cfg->ln_bot, cfg->ln_bot + cfg->n_bot);
-  e->top.ln.assign(cfg->ln_top, cfg->ln_top + cfg->n_top);
-  e->bot.layers.resize(cfg->n_bot - 1);
-  e->top.layers.resize(cfg->n_top - 1);
-  e->top.sigmoid_layer = cfg->sigmoid_top;
-  const int T = e->T, F = T + 1;
-
-  auto bail = [&](int32_t code, const char* msg) {
-    g_create_error = msg;
-    drs_destroy(e);
-    return code;
-  };
-  // shape algebra of the reference builders
-  switch (e->kind) {
-    case DRS_MODEL_DLRM: {
-      e->m_den = e->bot.ln.front();
-      e->w0 = e->bot.ln.back();
-      if (e->w0 != D) return bail(DRS_ERR_BAD_ARG, "arch_sparse_feature_size does not match last dim of bottom mlp");
-      if (e->interaction_op == DRS_INTERACT_DOT)
-        e->num_int = (e->itself ? F * (F + 1) / 2 : F * (F - 1) / 2) + D;
-      else if (e->interaction_op == DRS_INTERACT_CAT)
-        e->num_int = F * D;
-      else
-        return bail(DRS_ERR_BAD_ARG, "unknown interaction op");
-      if (e->num_int != e->top.ln.front()) return bail(DRS_ERR_BAD_ARG, "# of feature interactions does not match first dim of top mlp");
-      e->n_out = e->top.ln.back();
-      break;
-    }
-    case DRS_MODEL_WND: {
-      if (cfg->n_bot != 1) return bail(DRS_ERR_BAD_ARG, "W&D has no bottom MLP layers");
-      e->m_den = e->w0 = e->bot.ln.front();
-      e->num_int = T * D + e->w0;
-      if (e->num_int != e->top.ln.front()) return bail(DRS_ERR_BAD_ARG, "num_int does not match first dim of top mlp");
-      e->n_out = e->top.ln.back();
-      break;
-    }
-    case DRS_MODEL_MTWND: {
-      if (cfg->n_bot != 1) return bail(DRS_ERR_BAD_ARG, "MT-W&D has no bottom MLP layers");
-      e->m_den = e->w0 = e->bot.ln.front();
-      e->num_int = T * D + e->w0;
-      if (e->num_int != e->top.ln.front()) return bail(DRS_ERR_BAD_ARG, "num_int does not match first dim of top mlp");
-      if (cfg->n_task < 2 || !cfg->ln_task || cfg->num_tasks < 1 || cfg->num_tasks > 64)
-        return bail(DRS_ERR_BAD_ARG, "MT-W&D needs arch_mlp_tasks and 1..64 task heads");
-      if (cfg->ln_task[0] != e->top.ln.back())
-        return bail(DRS_ERR_BAD_ARG, "Shared top layer and task MLP layers must have same input/output dimension");
-      e->tasks.resize(cfg->num_tasks);
-      for (auto& tk : e->tasks) {
-        tk.ln.assign(cfg->ln_task, cfg->ln_task + cfg->n_task);
-        tk.layers.resize(cfg->n_task - 1);
-        tk.sigmoid_layer = cfg->sigmoid_top;     // multi_task_wnd.py:309 passes self.sigmoid_top to the heads
-      }
-      e->top.sigmoid_layer = -1;                 // :301 create_mlp(self.ln_top, -1, ...)
-      e->n_out = cfg->num_tasks * cfg->ln_task[cfg->n_task - 1];
-      break;
-    }
-    case DRS_MODEL_DIN: {
-      if (T < 4) return bail(DRS_ERR_BAD_ARG, "DIN needs at least 4 embedding tables");
-      // an attention unit is create_mlp over 3*D - <arch_mlp_bot> - D (models/din.py:255-277): any depth, any widths
-      if (cfg->n_bot < 2 || e->bot.ln.front() != 3 * D || e->bot.ln.back() != D)
-        return bail(DRS_ERR_BAD_ARG, "DIN attention unit must be 3*D -> ... -> D");
-      for (int w : e->bot.ln) if (w < 1) return bail(DRS_ERR_BAD_ARG, "DIN attention unit with an empty layer");
-      // din.hip's forms: one hidden layer of <= 64 units, rows in 16-byte pieces; the two-launch attention kernel (the only
-      // path for sls_exact = 1 and for shapes the fused launch is not instantiated for) keeps 4 samples x (T - 3) units x
-      // h hidden values in 64 KB of LDS.  Everything else: din_any.hip.
-      e->din_any = cfg->n_bot != 3 || e->bot.ln[1] > 64 || (int64_t)(T - 3) * e->bot.ln[1] > 4096 || (D & 3) || D > 256;
-      for (int l = 1; l + 1 < cfg->n_bot; ++l) e->din_maxw = std::max(e->din_maxw, e->bot.ln[l]);
-      if (e->din_any && !din_any_fits(D, e->din_maxw))
-        return bail(DRS_ERR_UNSUPPORTED, "DIN: 4*D + 2*(widest hidden layer of a unit) floats must fit 160 KB of LDS");
-      e->m_den = 0; e->w0 = 0;
-      e->num_int = 4 * D;
-      if (e->num_int != e->top.ln.front()) return bail(DRS_ERR_BAD_ARG, "# of feature interactions does not match first dim of top mlp");
-      e->att.resize(T - 3);
-      for (auto& au : e->att) { au.ln = e->bot.ln; au.layers.resize(cfg->n_bot - 1); au.sigmoid_layer = -1; }
-      e->bot.ln = {0}; e->bot.layers.clear();      // no bottom MLP of its own
-      e->top.sigmoid_layer = -1;
-      e->n_out = e->top.ln.back();
-      break;
-    }
-    case DRS_MODEL_DIEN: {
-      if (T < 4) return bail(DRS_ERR_BAD_ARG, "DIEN needs at least 4 embedding tables");
-      if (cfg->n_bot != 2 || e->bot.ln[0] != D || e->bot.ln[1] < 1) return bail(DRS_ERR_BAD_ARG, "DIEN: ln_bot must be [D, hidden_size]");
-      // D in {16, 32, 64} with hidden_size in {8, 16, 32, 64}: dien.hip's forms; any other pair: din_any.hip
-      if (!dien_applicable(D, e->bot.ln[1]) && !dien_any_fits(D, e->bot.ln[1]))
-        return bail(DRS_ERR_UNSUPPORTED, "DIEN: D + 4*hidden_size floats must fit 160 KB of LDS");
-      const int H = e->bot.ln[1];
-      e->m_den = 0; e->w0 = 0;
-      e->num_int = H + 3 * D;
-      if (e->num_int != e->top.ln.front()) return bail(DRS_ERR_BAD_ARG, "# of feature interactions does not match first dim of top mlp");
-      e->rnn.resize(2);
-      e->rnn[0].ln = {D, H, H};
-      e->rnn[1].ln = {H, H, H};
-      for (auto& rn : e->rnn) { rn.layers.resize(2); rn.sigmoid_layer = -1; }
-      e->bot.ln = {0}; e->bot.layers.clear();
-      e->top.sigmoid_layer = -1;
-      e->n_out = e->top.ln.back();
-      break;
-    }
-    case DRS_MODEL_NCF: {
-      if (T != 4) return bail(DRS_ERR_BAD_ARG, "NCF has 4 embedding tables");
-      if (e->top.ln.front() != 2 * D) return bail(DRS_ERR_BAD_ARG, "NCF MLP branch input must be 2*D");
-      e->m_den = 0; e->w0 = 0;
-      e->num_int = D + e->top.ln.back();
-      e->top.sigmoid_layer = -1;
-      e->fin.ln = {e->num_int, 0};  // output width arrives with drs_set_fc(DRS_MLP_FINAL)
-      e->fin.layers.resize(1);
-      e->n_out = 0;
-      break;
-    }
-    default:
-      return bail(DRS_ERR_BAD_ARG, "unknown model kind");
-  }
-  for (int t = 0; t < T; ++t) {
-    if (e->rows[t] <= 0) return bail(DRS_ERR_BAD_ARG, "table with no rows");
-    // row offsets travel as 32-bit counts of load-width units (8 or 16 bytes): 32 GiB per table
-    if (e->rows[t] * (int64_t)D >= (1ll << 33)) return bail(DRS_ERR_UNSUPPORTED, "rows*D must be < 2^33 per table");
-  }
-
-  // prefix sums and bag * length products are int32 on the device
-  if ((int64_t)cfg->max_batch * cfg->max_lookups >= (1ll << 31) / DRS_MAX_COALESCE)
-    return bail(DRS_ERR_UNSUPPORTED, "max_batch * max_lookups must stay below 2^31 / 8");
-  if (set_device(e)) return bail(DRS_ERR_HIP, e->err.c_str());
-  {
-    int khz = 0;
-    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device_id) == hipSuccess && khz > 0)
-      e->wall_clock_khz = khz;
-  }
-  // table arena
-  const size_t arena_bytes = table_layout(e, DRS_TABLE_FP32, &e->tab_off);
-  e->table_set.assign(T, false);
-  hipError_t last_rr = hipSuccess;
-  auto hip_ok = [&](hipError_t rr) { last_rr = rr; if (rr != hipSuccess) { e->err = hipGetErrorString(rr); return false; } return true; };
-  // only an allocation failure is DRS_ERR_OOM; stream/event creation, bad device ... are DRS_ERR_HIP
-#define CREATE_TRY(call) if (!hip_ok(call)) return bail(last_rr == hipErrorOutOfMemory ? DRS_ERR_OOM : DRS_ERR_HIP, (std::string(#call ": ") + e->err).c_str())
-  e->tune.device = device_id;
-  CREATE_TRY(device_init(device_id, &e->tune.zero));
-  e->tables_bytes = arena_bytes;
-  CREATE_TRY(hipMalloc(&e->d_tab_off, sizeof(int64_t) * T));
-  CREATE_TRY(hipMalloc(&e->d_tab_rows, sizeof(int64_t) * T));
-  CREATE_TRY(hipMalloc(&e->d_op_tab, sizeof(int64_t) * 2));
-  CREATE_TRY(hipMemcpy(e->d_tab_off, e->tab_off.data(), sizeof(int64_t) * T, hipMemcpyHostToDevice));
-  CREATE_TRY(hipMemcpy(e->d_tab_rows, e->rows.data(), sizeof(int64_t) * T, hipMemcpyHostToDevice));
-  e->fp8_k.assign(T, 0);
-  CREATE_TRY(hipMalloc(&e->d_tab_scale, sizeof(float) * T));
-  CREATE_TRY(hipMalloc(&e->d_absmax, sizeof(uint32_t)));
-  CREATE_TRY(upload_fp8_scales(e));
-
-  e->cap = (int64_t)e->max_batch * e->max_lookups;
-  e->blk = BlockLayout(e->max_batch, e->m_den, T, e->cap);
-  e->max_rows = (int64_t)DRS_MAX_COALESCE * ((e->max_batch + 63) / 64 * 64);
-  e->ldT = e->kind == DRS_MODEL_NCF ? 4 * D : e->w0 + (int64_t)T * D;   // (DIN: w0 == 0)
-  e->ldR = round_up(e->num_int, 4);
-  int maxw = 4;
-  for (int w : e->bot.ln) maxw = w > maxw ? w : maxw;
-  for (int w : e->top.ln) maxw = w > maxw ? w : maxw;
-  for (auto& tk : e->tasks) for (int w : tk.ln) maxw = w > maxw ? w : maxw;
-  e->ldH = round_up(maxw, 4);
+  lay_out(e, *cfg, shape);
+  int32_t rc;
+  if ((rc = set_device(e))) return bail(rc, e->err);
+  if ((rc = build_table_meta(e))) return bail(rc, e->err);
   e->batches.resize(e->n_batches);
-  for (auto& b : e->batches)
-    if (alloc_batch(e, b)) return bail(DRS_ERR_OOM, e->err.c_str());
+  e->batch_mem.resize(e->n_batches);
+  for (int i = 0; i < e->n_batches; ++i)
+    if ((rc = alloc_batch(e, e->batches[i], e->batch_mem[i]))) return bail(rc, e->err);
   e->slots.resize(e->n_slots);
-  const int n_out_cap = e->kind == DRS_MODEL_NCF ? 1024 : e->n_out;
-  for (auto& s : e->slots) {
-    CREATE_TRY(hipStreamCreateWithFlags(&s.own_stream, hipStreamNonBlocking));
-    CREATE_TRY(hipMalloc(&s.T, sizeof(float) * (size_t)e->max_rows * e->ldT));
-    CREATE_TRY(hipMemset(s.T, 0, sizeof(float) * (size_t)e->max_rows * e->ldT));
-    CREATE_TRY(hipMalloc(&s.R, sizeof(float) * (size_t)e->max_rows * e->ldR));
-    CREATE_TRY(hipMemset(s.R, 0, sizeof(float) * (size_t)e->max_rows * e->ldR));
-    CREATE_TRY(hipMalloc(&s.H, sizeof(float) * (size_t)e->max_rows * e->ldH));
-    CREATE_TRY(hipMalloc(&s.Hb, sizeof(float) * (size_t)e->max_rows * e->ldH));
-    CREATE_TRY(hipMalloc(&s.H2, sizeof(float) * (size_t)e->max_rows * (e->num_int + 4)));
-    if (e->kind == DRS_MODEL_MTWND) CREATE_TRY(hipMalloc(&s.H3, sizeof(float) * (size_t)e->max_rows * e->ldH));
-    const size_t out_words = kOutOffset + (size_t)e->max_rows * n_out_cap;
-    CREATE_TRY(hipMalloc(&s.d_out, sizeof(float) * out_words));
-    CREATE_TRY(hipMalloc(&s.d_err, sizeof(uint32_t)));
-    CREATE_TRY(hipMalloc(&s.d_counter, sizeof(uint32_t)));
-#ifdef DRS_LAB
-    // "mlp_early" (lab only): its stream, and the word a RUNNING kernel polls while another stream's write lands in it --
-    // fine-grained memory, so that the write is visible across the XCDs' L2s
-    CREATE_TRY(hipStreamCreateWithFlags(&s.early_stream, hipStreamNonBlocking));
-    CREATE_TRY(hipExtMallocWithFlags(reinterpret_cast<void**>(&s.d_gflag), sizeof(uint32_t), hipDeviceMallocFinegrained));
-    CREATE_TRY(hipMemset(s.d_gflag, 0, sizeof(uint32_t)));
-#endif
-    CREATE_TRY(hipMemset(s.d_err, 0, sizeof(uint32_t)));
-    CREATE_TRY(hipMemset(s.d_counter, 0, sizeof(uint32_t)));
-    // column-split MLP launches (mlp.hip NSplit; DLRM's first top layer): up to 4 096 rows of that layer's outputs
-    if (e->kind == DRS_MODEL_DLRM && e->top.ln.size() >= 3 && e->top.ln[1] >= 128 && e->top.ln[1] <= 1024 && !(e->top.ln[1] & 63)) {
-      s.xrows = e->max_rows < 4096 ? e->max_rows : 4096;
-      s.xcols = e->top.ln[1];
-      CREATE_TRY(hipMalloc(&s.xbuf, sizeof(float) * (size_t)s.xrows * s.xcols));
-      CREATE_TRY(hipMalloc(&s.xcnt, sizeof(uint32_t) * (size_t)(s.xrows / 16 + 1)));
-      CREATE_TRY(hipMemset(s.xcnt, 0, sizeof(uint32_t) * (size_t)(s.xrows / 16 + 1)));
-    }
-    // coherent (fine-grained) pinned memory: device stores become visible to a polling CPU
-    CREATE_TRY(hipHostMalloc(&s.h_out, sizeof(uint32_t) * out_words, hipHostMallocMapped | hipHostMallocCoherent));
-    memset(s.h_out, 0, sizeof(uint32_t) * out_words);
-    CREATE_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s.dm_out), s.h_out, 0));
-    CREATE_TRY(hipMalloc(&s.d_ts, sizeof(uint64_t) * 2 * ((size_t)e->max_rows * T + 8)));   // + 8: the XCD-ordered grid is rounded up to 8
-    CREATE_TRY(hipMalloc(&s.d_span_acc, sizeof(uint64_t) * 2 * 65536));
-    CREATE_TRY(hipHostMalloc(&s.h_span, sizeof(uint64_t) * 2, hipHostMallocMapped | hipHostMallocCoherent));
-    s.h_span[0] = s.h_span[1] = 0;
-    CREATE_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s.dm_span), s.h_span, 0));
-    s.h_ts.resize(2 * ((size_t)e->max_rows * T + 8));
-    for (auto& ev : s.ev) CREATE_TRY(hipEventCreate(&ev));
-    // Cross-stream ordering on ONE device only (no host reader): the kernels' own agent-scope
-    // release/acquire at their boundaries carries the data; the system-scope fence an event
-    // record adds by default costs ~3 us between consecutive gathers (measured: 128 k -> 132 k QPS)
-    CREATE_TRY(hipEventCreateWithFlags(&s.ev_sls, hipEventDisableTiming | hipEventDisableSystemFence));
-    CREATE_TRY(hipEventCreateWithFlags(&s.ev_dma, hipEventDisableTiming | hipEventDisableSystemFence));
-    CREATE_TRY(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming | hipEventDisableSystemFence));
-    for (auto& ev : s.ev_k) CREATE_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventDisableSystemFence));
-    // the two edges to a caller's stream (device outputs): what the caller runs on either side, copies included, is not
-    // the engine's to know, so these keep the default fence
-    CREATE_TRY(hipEventCreateWithFlags(&s.ev_caller, hipEventDisableTiming));
-    CREATE_TRY(hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
-    if (alloc_batch(e, s.scratch)) return bail(DRS_ERR_OOM, e->err.c_str());
-    s.scratch.n_samples = 0;
-    s.h_stage_bytes = e->blk.bytes;
-    CREATE_TRY(hipHostMalloc(&s.h_stage, s.h_stage_bytes, hipHostMallocMapped));
-    {
-      // device view of the same block, laid out like a staged batch: [dense | idx | off]
-      char* dm = nullptr;
-      CREATE_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&dm), s.h_stage, 0));
-      view_as(s.zc, e->blk, dm);
-      // the same layout once more in HBM: target of the one-copy input path
-      CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&s.d_stage), s.h_stage_bytes));
-      view_as(s.dc, e->blk, s.d_stage);
-    }
-  }
-  CREATE_TRY(hipStreamCreateWithFlags(&e->stream_g, hipStreamNonBlocking));
-  CREATE_TRY(hipStreamCreateWithFlags(&e->stream_dma, hipStreamNonBlocking));
-  choose_launch_forms(e);
-  apply_stream_mode(e);
-  {
-    // The table arena, last: one hipMalloc (where it lands in HBM, and what DLRM_Net.tune_table_placement does about
-    // it: DESIGN.md 5).
-#ifdef DRS_LAB
-    // lab build, DRS_TABLE_SELECT=1: "table_alloc" 3 (arena_alloc_selected: the fastest gigabytes of a pool by a one-table
-    // run of the model's gather kernel) -- an experiment that did NOT work (profiles/r05_placement/README.md)
-    const char* env = getenv("DRS_TABLE_SELECT");
-    if (env && atoi(env) != 0 && e->kind == DRS_MODEL_DLRM && e->mlp_streams <= 2 && e->max_lookups >= 8 && e->tables_bytes >= ((size_t)1 << 30)) e->table_alloc = 3;
-#endif
-    Arena first;
-    CREATE_TRY(arena_alloc(e, e->tables_bytes, &first));
-    e->tables = first.p;
-    e->arenas.assign(1, first);
-  }
-#undef CREATE_TRY
-  *out = e;
+  for (auto& s : e->slots)
+    if ((rc = build_slot(e, s))) return bail(rc, e->err);
+  if ((rc = build_tail(e))) return bail(rc, e->err);
+  *out = owner.release();
   return DRS_OK;
 }
 
+// Quiesce, then delete: every resource of the handle is owned by a field's type (hip_owned.h) and goes with the handle.
+// What is left to do by hand is to stop what could still use them, and the table arenas, which are handle structs.
 int32_t drs_destroy(drs_handle e) {
   if (!e) return DRS_OK;
-  const bool trc = getenv("DRS_TRACE_DESTROY") != nullptr;
-#define DTR(x) do { if (trc) { fprintf(stderr, "destroy %p: %s\n", (void*)e, x); fflush(stderr); } } while (0)
-  DTR("begin");
   e->launcher.reset();           // (finishes the jobs it holds, then joins)
-  DTR("launcher gone");
   (void)hipSetDevice(e->device);
-  if (e->stream_g) { (void)hipStreamSynchronize(e->stream_g); (void)hipStreamDestroy(e->stream_g); }
-  if (e->stream_dma) { (void)hipStreamSynchronize(e->stream_dma); (void)hipStreamDestroy(e->stream_dma); }
+  for (hipStream_t st : {e->stream_g.get(), e->stream_dma.get(), e->stream_h2d.get()}) if (st) (void)hipStreamSynchronize(st);
 #ifdef DRS_LAB
-  if (e->stream_g2) { (void)hipStreamSynchronize(e->stream_g2); (void)hipStreamDestroy(e->stream_g2); }
+  if (e->stream_g2) (void)hipStreamSynchronize(e->stream_g2);
 #endif
-  if (e->stream_h2d) { (void)hipStreamSynchronize(e->stream_h2d); (void)hipStreamDestroy(e->stream_h2d); }
-  DTR("g and h2d streams gone");
-  for (auto& s : e->slots) {
-    DTR("slot");
-    if (s.h_multi) (void)hipHostFree(s.h_multi);
-    if (s.d_multi) (void)hipFree(s.d_multi);
-    if (s.d_wgt) (void)hipFree(s.d_wgt);
-    s.mq.clear();
-    DTR("multi freed");
-    if (s.own_stream) { (void)hipStreamSynchronize(s.own_stream); (void)hipStreamDestroy(s.own_stream); }
-    if (s.early_stream) { (void)hipStreamSynchronize(s.early_stream); (void)hipStreamDestroy(s.early_stream); }
-    if (s.d_gflag) (void)hipFree(s.d_gflag);
-    DTR("own stream gone");
-    if (s.ev_sls) (void)hipEventDestroy(s.ev_sls);
-    if (s.ev_dma) (void)hipEventDestroy(s.ev_dma);
-    if (s.ev_in) (void)hipEventDestroy(s.ev_in);
-    if (s.ev_caller) (void)hipEventDestroy(s.ev_caller);
-    if (s.ev_out) (void)hipEventDestroy(s.ev_out);
-    for (auto& ev : s.ev_k) if (ev) (void)hipEventDestroy(ev);
-    if (s.T) (void)hipFree(s.T);
-    if (s.R) (void)hipFree(s.R);
-    if (s.H) (void)hipFree(s.H);
-    if (s.Hb) (void)hipFree(s.Hb);
-    if (s.H2) (void)hipFree(s.H2);
-    if (s.H3) (void)hipFree(s.H3);
-    if (s.d_out) (void)hipFree(s.d_out);
-    if (s.d_err) (void)hipFree(s.d_err);
-    if (s.d_ts) (void)hipFree(s.d_ts);
-    if (s.h_span) (void)hipHostFree(s.h_span);
-    if (s.d_span_acc) (void)hipFree(s.d_span_acc);
-    if (s.d_counter) (void)hipFree(s.d_counter);
-    if (s.xbuf) (void)hipFree(s.xbuf);
-    if (s.xcnt) (void)hipFree(s.xcnt);
-    if (s.h_out) (void)hipHostFree(s.h_out);
-    if (s.h_stage) (void)hipHostFree(s.h_stage);
-    if (s.d_stage) (void)hipFree(s.d_stage);
-    s.dc = Batch();
-    for (auto& ev : s.ev) if (ev) (void)hipEventDestroy(ev);
-    free_batch(s.scratch);
-  }
-  DTR("slots freed");
-  for (auto& b : e->batches) free_batch(b);
-  for (Mlp* m : served_mlps(e))
-    for (auto& l : m->layers) { if (l.Wb) (void)hipFree(l.Wb); l.Wb = nullptr; }
-  for (Mlp* m : {&e->bot, &e->top, &e->fin})
-    for (auto& l : m->layers) { l.W = l.b = nullptr; }
-  e->tasks.clear();
-  e->att.clear();
-  e->rnn.clear();
-  if (e->d_att) (void)hipFree(e->d_att);
-  if (e->d_att_packed) (void)hipFree(e->d_att_packed);
-  if (e->d_att_ln) (void)hipFree(e->d_att_ln);
-  if (e->w_arena) (void)hipFree(e->w_arena);
+  for (auto& s : e->slots)
+    for (hipStream_t st : {s.own_stream.get(), s.early_stream.get()}) if (st) (void)hipStreamSynchronize(st);
   for (Arena& a : e->arenas) arena_free(a);
-  for (auto& h : e->spacers) (void)hipMemRelease(h);
-  e->tables = nullptr;
-  if (e->probe_idx) (void)hipFree(e->probe_idx);
-  if (e->probe_out) (void)hipFree(e->probe_out);
-  if (e->probe_tab) (void)hipFree(e->probe_tab);
-  if (e->probe_err) (void)hipFree(e->probe_err);
-  if (e->d_tab_off) (void)hipFree(e->d_tab_off);
-  if (e->d_tab_rows) (void)hipFree(e->d_tab_rows);
-  if (e->d_tab_scale) (void)hipFree(e->d_tab_scale);
-  if (e->d_absmax) (void)hipFree(e->d_absmax);
-  if (e->d_op_tab) (void)hipFree(e->d_op_tab);
-  DTR("device memory freed");
+  drop_spacers(e);
   delete e;
-  if (trc) { fprintf(stderr, "destroy: done\n"); fflush(stderr); }
-#undef DTR
   return DRS_OK;
 }
 
@@ -631,18 +484,17 @@ int32_t drs_set_table(drs_handle e, int32_t t, const float* h_W, int64_t rows) {
       HIP_TRY(e, upload_fp8_scales(e));
     }
     char* dst = table_ptr(e->tables, e->tab_off, t, dt);
-    float* stage = nullptr;
-    HIP_TRY(e, hipMalloc(&stage, sizeof(float) * (size_t)(chunk * D)));
+    DeviceBuf<float> stage;
+    HIP_TRY(e, stage.alloc((size_t)(chunk * D)));
     hipError_t r = hipSuccess;
     for (int64_t i = 0; i < rows && r == hipSuccess; i += chunk) {
       const int64_t m = std::min(chunk, rows - i);
       r = hipMemcpy(stage, h_W + i * D, sizeof(float) * (size_t)(m * D), hipMemcpyHostToDevice);
       // (rowwise: the kernel places rows i .. i + m - 1 of the table itself -- an int8 chunk may start inside a line)
       const TableSide to{table_rowwise(dt) ? dst : dst + i * table_row_stride(dt, D), dt, e->i8l.n, mul};
-      if (r == hipSuccess) r = launch_convert_rows(TableSide{stage, DRS_TABLE_FP32}, to, RowWindow{i, m, rows}, (int)D, nullptr);
+      if (r == hipSuccess) r = launch_convert_rows(TableSide{stage.get(), DRS_TABLE_FP32}, to, RowWindow{i, m, rows}, (int)D, nullptr);
       if (r == hipSuccess) r = hipStreamSynchronize(nullptr);    // (before the next chunk overwrites the staging buffer)
     }
-    (void)hipFree(stage);
     if (r != hipSuccess) return fail(e, DRS_ERR_HIP, "drs_set_table: %s", hipGetErrorString(r));
   }
   e->table_set[t] = true;
@@ -723,7 +575,7 @@ int32_t drs_set_fc(drs_handle e, int32_t mlp, int32_t layer, const float* h_W, c
     const size_t zeros = 64;       // a zero page inside the arena (stream kernel: k beyond a layer's K)
     need += nbias + zeros;
     e->w_arena_floats = need < (1u << 20) ? (1u << 20) : need;   // >= 4 MiB
-    HIP_TRY(e, hipMalloc(&e->w_arena, sizeof(float) * e->w_arena_floats));
+    HIP_TRY(e, e->w_arena.alloc(e->w_arena_floats));
     HIP_TRY(e, hipMemset(e->w_arena, 0, sizeof(float) * zeros));
     e->tune.w_arena = e->w_arena; e->tune.w_arena_floats = e->w_arena_floats; e->tune.w_zero_off = 0;
     size_t boff = zeros, woff = zeros + nbias;
@@ -744,9 +596,8 @@ int32_t drs_set_fc(drs_handle e, int32_t mlp, int32_t layer, const float* h_W, c
   }
   // a bf16 layer ("mlp_dtype" 2) keeps a bf16 twin: its memory first, so that a failure leaves the layer as it was
   const bool twin = L.packed && bf16_shape(e, n, m);
-  if (twin && !L.Wb && hipMalloc(&L.Wb, sizeof(uint16_t) * (size_t)m * bf16_kpad(n)) != hipSuccess) {
+  if (twin && !L.Wb && L.Wb.alloc((size_t)m * bf16_kpad(n)) != hipSuccess) {
     (void)hipGetLastError();
-    L.Wb = nullptr;
     return fail(e, DRS_ERR_OOM, "no room for the bf16 twin of the %dx%d layer", n, m);
   }
   HIP_TRY(e, hipMemcpy(L.W, h_W, sizeof(float) * (size_t)m * n, hipMemcpyHostToDevice));

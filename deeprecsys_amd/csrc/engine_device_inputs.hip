@@ -116,9 +116,8 @@ int32_t check_device_set(drs_engine* e, int32_t slot, const DeviceSet& d, int64_
 // the slot's weight blocks, allocated when it first sees a weighted set (an engine that never sees weights allocates nothing)
 static int32_t weight_blocks(drs_engine* e, Slot& s) {
   if (s.d_wgt) return DRS_OK;
-  const hipError_t r = hipMalloc(reinterpret_cast<void**>(&s.d_wgt), sizeof(float) * e->blk.idx_elems() * DRS_MAX_COALESCE);
+  const hipError_t r = s.d_wgt.alloc(e->blk.idx_elems() * DRS_MAX_COALESCE);
   if (r != hipSuccess) {
-    s.d_wgt = nullptr;
     (void)hipGetLastError();
     return fail(e, r == hipErrorOutOfMemory ? DRS_ERR_OOM : DRS_ERR_HIP, "per-sample weight blocks of a launch set: %s", hipGetErrorString(r));
   }
@@ -139,7 +138,7 @@ int32_t enqueue_device_set(drs_engine* e, int32_t slot, const DeviceSet& d, int6
     pass_w |= bs[i] > 0 && d.weights_of(i) != nullptr;
   }
   if (any_w && (rc = weight_blocks(e, s))) return rc;
-  if (!e->stream_h2d) HIP_TRY(e, hipStreamCreateWithFlags(&e->stream_h2d, hipStreamNonBlocking));
+  if ((rc = copy_stream(e))) return rc;
 
   InPassWgtArgs aw;
   memset(&aw, 0, sizeof aw);

@@ -198,7 +198,7 @@ static hipError_t upload_weight_table(drs_engine* e, const std::vector<Mlp>& uni
   std::vector<const float*> hp;
   for (auto& u : units)
     for (size_t l = 0; l < (layers ? layers : u.layers.size()); ++l) { hp.push_back(u.layers[l].W); hp.push_back(u.layers[l].b); }
-  hipError_t r = hipMalloc(reinterpret_cast<void**>(&e->d_att), sizeof(float*) * hp.size());
+  hipError_t r = e->d_att.alloc(hp.size());
   if (r == hipSuccess) r = hipMemcpy(e->d_att, hp.data(), sizeof(float*) * hp.size(), hipMemcpyHostToDevice);
   return r;
 }
@@ -211,7 +211,7 @@ static int32_t pack_weights(drs_engine* e) {
     const int H = e->rnn[0].ln[1];
     if (!e->d_att) {
       HIP_TRY(e, upload_weight_table(e, e->rnn, 2));
-      HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&e->d_att_packed), sizeof(float) * (size_t)dien_packed_floats(e->D, H)));
+      HIP_TRY(e, e->d_att_packed.alloc((size_t)dien_packed_floats(e->D, H)));
     }
     HIP_TRY(e, launch_dien_pack(e->d_att, e->d_att_packed, e->D, H, nullptr));
     HIP_TRY(e, hipStreamSynchronize(nullptr));
@@ -219,14 +219,14 @@ static int32_t pack_weights(drs_engine* e) {
     // any-shape units (din_any.hip): the kernel reads the layers where drs_set_fc put them
     if (!e->d_att) {
       HIP_TRY(e, upload_weight_table(e, e->att, 0));
-      HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&e->d_att_ln), sizeof(int32_t) * e->att[0].ln.size()));
+      HIP_TRY(e, e->d_att_ln.alloc(e->att[0].ln.size()));
       HIP_TRY(e, hipMemcpy(e->d_att_ln, e->att[0].ln.data(), sizeof(int32_t) * e->att[0].ln.size(), hipMemcpyHostToDevice));
     }
   } else if (!e->att.empty()) {
     const int U = (int)e->att.size(), h = e->att[0].ln[1];
     if (!e->d_att) {
       HIP_TRY(e, upload_weight_table(e, e->att, 2));
-      HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&e->d_att_packed), sizeof(float) * (size_t)U * din_unit_stride(e->D, h)));
+      HIP_TRY(e, e->d_att_packed.alloc((size_t)U * din_unit_stride(e->D, h)));
     }
     HIP_TRY(e, launch_din_pack(e->d_att, e->d_att_packed, U, e->D, h, nullptr));
     HIP_TRY(e, hipStreamSynchronize(nullptr));
@@ -313,7 +313,7 @@ static int32_t launch_gather(SetCtx& x) {
   }
   a.idx_stride = e->blk.cap; a.off_stride = (int64_t)e->blk.off_stride();
   a.out = s.T; a.ld_out = e->ldT; a.col0 = e->kind == DRS_MODEL_NCF ? 0 : e->w0;
-  a.T = e->T; a.D = e->D; a.err = reinterpret_cast<int32_t*>(s.d_err);
+  a.T = e->T; a.D = e->D; a.err = reinterpret_cast<int32_t*>(s.d_err.get());
   a.ts = prof ? s.d_ts : nullptr;
   a.ln_mul = e->i8l.mul; a.ln_shift = e->i8l.shift; a.ln_pad = e->i8l.pad;   // ("table_int8_lines" / "table_int4_lines": zeros for every other layout)
   a.tab_scale = e->table_dtype == DRS_TABLE_FP8_E4M3 ? e->d_tab_scale : nullptr;   // (read by the fp8 instances alone)
@@ -847,11 +847,10 @@ static int32_t sls_op(drs_handle e, const float* d_W, int64_t rows, int32_t D, c
     off[b + 1] = (int32_t)total;
   }
   if (total != n_idx) return fail(e, DRS_ERR_LENGTHS_SUM, "sum(lengths)=%lld != len(indices)=%lld", (long long)total, (long long)n_idx);
-  int32_t* d_off = nullptr;
-  int32_t* d_err = nullptr;
-  HIP_TRY(e, hipMalloc(&d_off, sizeof(int32_t) * ((size_t)n_bags + 1)));
-  hipError_t r = hipMalloc(&d_err, sizeof(int32_t));
-  if (r != hipSuccess) { (void)hipFree(d_off); return fail(e, DRS_ERR_OOM, "hipMalloc"); }
+  DeviceBuf<int32_t> d_off, d_err;
+  HIP_TRY(e, d_off.alloc((size_t)n_bags + 1));
+  hipError_t r = d_err.alloc(1);
+  if (r != hipSuccess) return fail(e, DRS_ERR_OOM, "hipMalloc");
   const int64_t tab[2] = {0, rows};
   int32_t h_err = 0;
   r = hipMemcpy(d_off, off.data(), sizeof(int32_t) * ((size_t)n_bags + 1), hipMemcpyHostToDevice);
@@ -870,8 +869,6 @@ static int32_t sls_op(drs_handle e, const float* d_W, int64_t rows, int32_t D, c
   }
   if (r == hipSuccess) r = hipStreamSynchronize(s.stream);
   if (r == hipSuccess) r = hipMemcpy(&h_err, d_err, sizeof(int32_t), hipMemcpyDeviceToHost);
-  (void)hipFree(d_off);
-  (void)hipFree(d_err);
   if (r != hipSuccess) return fail(e, DRS_ERR_HIP, "drs_sls: %s", hipGetErrorString(r));
   if (h_err) return fail(e, DRS_ERR_INDEX_RANGE, "an index is outside [0, %lld)", (long long)rows);
   return DRS_OK;
@@ -900,20 +897,19 @@ int32_t drs_fc(drs_handle e, const float* d_x, int64_t M, int32_t K, const float
   if (s.busy && (rc = wait_slot(e, s, nullptr))) return rc;
   MlpPlan p;
   // "mlp_dtype" 2: a bf16 layer by its shape, as in a launch set -- d_W rounded into a scratch twin first
-  uint16_t* wb = nullptr;
+  DeviceBuf<uint16_t> wb;
   if (M > 0 && bf16_shape(e, K, N)) {
-    if (hipMalloc(&wb, sizeof(uint16_t) * (size_t)N * bf16_kpad(K)) != hipSuccess) {
+    if (wb.alloc((size_t)N * bf16_kpad(K)) != hipSuccess) {
       (void)hipGetLastError();
       return fail(e, DRS_ERR_OOM, "drs_fc: no room for the bf16 twin of the %dx%d layer", K, N);
     }
     hipError_t r = launch_bf16_twin(d_W, K, N, wb, s.stream);
-    if (r != hipSuccess) { (void)hipFree(wb); return fail(e, DRS_ERR_HIP, "drs_fc: %s", hipGetErrorString(r)); }
+    if (r != hipSuccess) return fail(e, DRS_ERR_HIP, "drs_fc: %s", hipGetErrorString(r));
   }
   hipError_t r = hipSuccess;
   const bool ok = M <= 0 || plan_layer(d_x, K, M, K, d_W, d_b, N, act, d_y, N, e->tune, nullptr, nullptr, &p, wb);
   if (ok && M > 0) r = launch_plan(p, e->tune, s.stream);
   if (r == hipSuccess) r = hipStreamSynchronize(s.stream);
-  if (wb) (void)hipFree(wb);
   if (!ok) return fail(e, DRS_ERR_HIP, "no kernel takes the %dx%d layer", K, N);
   HIP_TRY(e, r);
   return DRS_OK;

@@ -134,25 +134,22 @@ int32_t finish_inputs(drs_engine* e, Slot& s, int mode, int32_t bs, size_t used,
 
 // The per-query blocks of a slot's launch sets with per-call inputs, allocated on first use: the HBM blocks (s.d_multi,
 // viewed as s.mq) and, for the host form alone (host_side), their pinned twins -- the device form
-// (engine_device_inputs.hip) never needs the pinned half.  What THIS call allocated is all there or all gone (a failed
-// second allocation must not leave a half-built slot behind: the next call would index device pointers derived from
-// null -- ADVICE r3); blocks an earlier call of the other form made stay.
+// (engine_device_inputs.hip) never needs the pinned half.  What THIS call allocated is all there or all gone (the slot
+// takes the two over only once both exist); blocks an earlier call of the other form made stay.
 int32_t multi_blocks(drs_engine* e, Slot& s, bool host_side) {
   const bool need_d = !s.d_multi, need_h = host_side && !s.h_multi;
   if (!need_d && !need_h) return DRS_OK;
   const size_t block = e->blk.padded;
-  char* h = nullptr;
-  char* d = nullptr;
+  PinnedBuf<char> h;
+  DeviceBuf<char> d;
   hipError_t r = hipSuccess;
-  if (need_h) r = hipHostMalloc(reinterpret_cast<void**>(&h), block * DRS_MAX_COALESCE, hipHostMallocDefault);
-  if (r == hipSuccess && need_d) r = hipMalloc(reinterpret_cast<void**>(&d), block * DRS_MAX_COALESCE);
-  if (r != hipSuccess) {
-    if (h) (void)hipHostFree(h);
+  if (need_h) r = h.alloc(block * DRS_MAX_COALESCE, hipHostMallocDefault);
+  if (r == hipSuccess && need_d) r = d.alloc(block * DRS_MAX_COALESCE);
+  if (r != hipSuccess)
     return fail(e, r == hipErrorOutOfMemory ? DRS_ERR_OOM : DRS_ERR_HIP, "per-call input blocks of a launch set: %s", hipGetErrorString(r));
-  }
-  if (need_h) s.h_multi = h;
+  if (need_h) s.h_multi = std::move(h);
   if (need_d) {
-    s.d_multi = d;
+    s.d_multi = std::move(d);
     s.mq.assign(DRS_MAX_COALESCE, Batch());
     for (int i = 0; i < DRS_MAX_COALESCE; ++i) view_as(s.mq[i], e->blk, s.d_multi + (size_t)i * block);
   }
@@ -295,7 +292,10 @@ int32_t drs_stage_batch_weights(drs_handle e, int32_t batch_id, const float* con
   }
   // make sure no in-flight query still reads this batch
   for (auto& s : e->slots) if (s.busy) HIP_TRY(e, hipStreamSynchronize(s.stream));
-  if (!b.wgt) HIP_TRY(e, hipMalloc(&b.wgt, sizeof(float) * L.idx_elems()));
+  if (!b.wgt) {
+    HIP_TRY(e, e->batch_mem[batch_id].wgt.alloc(L.idx_elems()));
+    b.wgt = e->batch_mem[batch_id].wgt;
+  }
   std::vector<float> ones;
   for (int t = 0; t < e->T; ++t) {
     const int64_t n = b.h_off[L.h_off_at(t, b.n_samples)];
@@ -343,7 +343,7 @@ int32_t drs_run_queues_multi_async(drs_handle e, int32_t slot, int32_t n, const 
   if (s.busy && (rc = wait_slot(e, s, nullptr))) return rc;
   const BlockLayout& L = e->blk;
   if ((rc = multi_blocks(e, s, true))) return rc;
-  if (!e->stream_h2d) HIP_TRY(e, hipStreamCreateWithFlags(&e->stream_h2d, hipStreamNonBlocking));
+  if ((rc = copy_stream(e))) return rc;
   QueryIn qs[DRS_MAX_COALESCE];
   for (int i = 0; i < n; ++i) {
     if ((rc = check_bs(e, i, bs[i]))) return rc;

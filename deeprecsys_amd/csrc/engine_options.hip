@@ -219,13 +219,13 @@ int32_t set_mlp_dtype(drs_engine* e, int64_t value) {
   hipError_t r = hipSuccess;
   for (Mlp* m : served_mlps(e))
     for (Layer& L : m->layers) {
-      if (value != DRS_MLP_BF16) { if (L.Wb) (void)hipFree(L.Wb); L.Wb = nullptr; continue; }
+      if (value != DRS_MLP_BF16) { L.Wb.reset(); continue; }
       if (r != hipSuccess || !L.set || L.Wb || !bf16_shape(e, L.n, L.m)) continue;
       if ((r = build_bf16_twin(L)) == hipSuccess) built.push_back(&L);
     }
   if (r != hipSuccess) {
     (void)hipGetLastError();
-    for (Layer* L : built) { (void)hipFree(L->Wb); L->Wb = nullptr; }
+    for (Layer* L : built) L->Wb.reset();
     e->mlp_dtype = from;
     return fail(e, r == hipErrorOutOfMemory ? DRS_ERR_OOM : DRS_ERR_HIP, "mlp_dtype: the layers' bf16 twins: %s", hipGetErrorString(r));
   }
@@ -332,6 +332,8 @@ const OptDesc kOptions[] = {
     OPT_RO("table_bytes", return (int64_t)e->tables_bytes;),
     OPT_RO("table_address", return (int64_t)(uintptr_t)e->tables;),
     OPT_RO("sls_weighted", return weighted_batches(e);),
+    // owning handles (hip_owned.h) and table arenas alive in this process, over every engine: what a closed engine must give back
+    OPT_RO("live_device_objects", return live_objects();),
 };
 #undef OPT
 #undef OPT_RO
@@ -347,7 +349,7 @@ int32_t lab_set_option(drs_engine* e, const char* key, int64_t value, bool* hand
     // experiment: does a second gather stream close the ~1.4 us between back-to-back gather launches?
     int32_t rc = drs_sync(e);
     if (rc) return rc;
-    if (value == 2 && !e->stream_g2) HIP_TRY(e, hipStreamCreateWithFlags(&e->stream_g2, hipStreamNonBlocking));
+    if (value == 2 && !e->stream_g2) HIP_TRY(e, e->stream_g2.create(hipStreamNonBlocking));
     e->gather_streams = (int)value;
     apply_stream_mode(e);
   }
@@ -364,11 +366,13 @@ int32_t lab_set_option(drs_engine* e, const char* key, int64_t value, bool* hand
     for (int c = 0; c < ncu; ++c) ((value == 0 || c < value) ? mlp : rest)[(size_t)c / 32] |= 1u << (c % 32);
     if (value == 0 || !e->gather_cu_complement) rest = std::vector<uint32_t>((size_t)words, 0xffffffffu);
     for (auto& s : e->slots) {
-      if (s.own_stream) { (void)hipStreamSynchronize(s.own_stream); (void)hipStreamDestroy(s.own_stream); s.own_stream = nullptr; }
-      HIP_TRY(e, hipExtStreamCreateWithCUMask(&s.own_stream, (uint32_t)words, mlp.data()));
+      hipStream_t masked = nullptr;
+      HIP_TRY(e, hipExtStreamCreateWithCUMask(&masked, (uint32_t)words, mlp.data()));
+      s.own_stream.reset(masked);
     }
-    if (e->stream_g) { (void)hipStreamSynchronize(e->stream_g); (void)hipStreamDestroy(e->stream_g); e->stream_g = nullptr; }
-    HIP_TRY(e, hipExtStreamCreateWithCUMask(&e->stream_g, (uint32_t)words, rest.data()));
+    hipStream_t masked = nullptr;
+    HIP_TRY(e, hipExtStreamCreateWithCUMask(&masked, (uint32_t)words, rest.data()));
+    e->stream_g.reset(masked);
     e->mlp_cu_mask = (int)value;
     apply_stream_mode(e);
   }
@@ -379,8 +383,9 @@ int32_t lab_set_option(drs_engine* e, const char* key, int64_t value, bool* hand
     if (rc) return rc;
     int lo = 0, hi = 0;
     HIP_TRY(e, hipDeviceGetStreamPriorityRange(&lo, &hi));      // (numerically: hi <= lo)
-    if (e->stream_g) { (void)hipStreamSynchronize(e->stream_g); (void)hipStreamDestroy(e->stream_g); e->stream_g = nullptr; }
-    HIP_TRY(e, hipStreamCreateWithPriority(&e->stream_g, hipStreamNonBlocking, value > 0 ? hi : value < 0 ? lo : (lo + hi) / 2));
+    hipStream_t ranked = nullptr;
+    HIP_TRY(e, hipStreamCreateWithPriority(&ranked, hipStreamNonBlocking, value > 0 ? hi : value < 0 ? lo : (lo + hi) / 2));
+    e->stream_g.reset(ranked);
     e->gather_priority = (int)value;
     apply_stream_mode(e);
   }

@@ -24,18 +24,13 @@ int32_t check_rows(drs_engine* e, const char* what, int32_t t, int64_t n, const 
 // the device buffers of one call: fp32 rows, their ids, and the same rows packed in the table's type (null under fp32:
 // the fp32 rows are the stored bytes)
 struct RowStage {
-  float* f32 = nullptr;
-  int64_t* ids = nullptr;
-  void* packed = nullptr;
-  ~RowStage() {
-    if (f32) (void)hipFree(f32);
-    if (ids) (void)hipFree(ids);
-    if (packed) (void)hipFree(packed);
-  }
+  DeviceBuf<float> f32;
+  DeviceBuf<int64_t> ids;
+  DeviceBuf<void> packed;
   hipError_t alloc(int64_t chunk, int64_t D, int dt) {
-    hipError_t r = hipMalloc(&f32, sizeof(float) * (size_t)(chunk * D));
-    if (r == hipSuccess) r = hipMalloc(&ids, sizeof(int64_t) * (size_t)chunk);
-    if (r == hipSuccess && dt != DRS_TABLE_FP32) r = hipMalloc(&packed, (size_t)(chunk * table_row_stride(dt, D)));
+    hipError_t r = f32.alloc((size_t)(chunk * D));
+    if (r == hipSuccess) r = ids.alloc((size_t)chunk);
+    if (r == hipSuccess && dt != DRS_TABLE_FP32) r = packed.alloc((size_t)(chunk * table_row_stride(dt, D)));
     return r;
   }
 };

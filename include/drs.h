@@ -336,6 +336,8 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  *   read only     "preferred_coalesce"  "preferred_slots"  "gather_bound"  "device"
  *                 "table_placements"  "table_bytes"  "table_address"
  *                 "sls_weighted" (staged batches that carry per-sample weights, drs_stage_batch_weights)
+ *                 "live_device_objects" (GPU allocations, streams, events and table arenas alive in this process, over
+ *                 every engine: what closing an engine gives back)
  * Options belong to the handle: two engines in one process (the mixed-model accelerator engine) keep their own.
  * The lab build (make -C deeprecsys_amd/csrc lab-lib, -DDRS_LAB) also takes the lab's instruments and the options
  * of every form that lost its measurement (docs/OPTIONS.md, last section); the product library refuses them.      */

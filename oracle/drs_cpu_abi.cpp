@@ -629,7 +629,7 @@ int32_t drs_kernel_bytes(drs_handle e, int32_t, int64_t* bytes) {
 }
 int32_t drs_get_option(drs_handle e, const char* key, int64_t* value) {
   if (!e || !key || !value) return DRS_ERR_BAD_ARG;
-  *value = 0;
+  *value = 0;     // (every other key, "live_device_objects" among them: there is no device object to count here)
   if (!strcmp(key, "preferred_coalesce") || !strcmp(key, "preferred_slots")) {
     // the engine's own rule (csrc/engine_create.hip choose_launch_forms, engine_options.hip), so the host code above the ABI
     // runs with the launch-set sizes the product uses: 16 when the model's MLP launches overlap each
