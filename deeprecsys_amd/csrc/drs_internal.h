@@ -2,6 +2,7 @@
 // Public surface: include/drs.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/drs.h"
@@ -47,6 +48,9 @@ struct SlsArgs {
   int32_t col0;               // first output column of table 0
   int32_t T;
   int32_t D;
+  // "sls_nt_mask" (a launch planned with SlsPlan::nt == 2): bit t set -- table t's rows are read non-temporally, clear --
+  // with plain loads.  Read by the per-table instance alone; it lies in what was padding in front of `err`.
+  uint32_t nt_mask;
   int32_t* err;               // device error word: bit0 = index out of range
   uint64_t* ts;               // optional [2 * gridDim.x] start/end wall_clock64() per workgroup
   int32_t nt;                 // fused DIN launch: table rows by non-temporal loads ("sls_nt"; set by launch_din_fused)
@@ -55,6 +59,8 @@ struct SlsArgs {
   // starts r * PR + (r / n) * ln_pad pieces into its table, r / n == ln_mul ? umulhi(r, ln_mul) >> ln_shift : r.  ln_pad == 0: every other layout.
   uint32_t ln_mul, ln_shift, ln_pad;
 };
+
+static_assert(offsetof(SlsArgs, nt_mask) + 4 == offsetof(SlsArgs, err), "nt_mask fills padding: the kernels' argument layout is unchanged");
 
 // What the launch functions chose for the launch set being enqueued ("which kernel serves which shape"):
 // each launch appends "name<template args>[grid x block] " to the log of the slot (drs_last_dispatch).
@@ -78,6 +84,7 @@ struct Tune {
   int sls_flat = 1;              // fixed-length bags: all row loads of a wave in flight at once
   int sls_bpw = 0;               // ... bags per wave of that variant (0 = auto | 1 | 2 | 4)
   int sls_nt = 1;                // table rows are read with non-temporal loads (every gather kernel of sls.hip and sls_wflat.hip)
+  int64_t sls_nt_mask = -1;      // ... or table by table: bit t = table t's policy (-1: unset, the uniform sls_nt; plan_sls says which forms take it)
   int sls_weighted_flat = 0;     // a WEIGHTED launch may take the flat, flatc and one-lookup forms (their weighted instances: sls_wflat.hip); 0: the ring walk or the any-width form only
   int sls_one = 1;               // fixed bags of ONE row (W&D, MT-WnD, NCF, DIEN): the copy form (sls_one_kernel); 1 = 64 samples per wave, 16 for small launches | 64 | 16 | 0 off
   int din_nt = 1;                // fused DIN launch: non-temporal row loads ("din_nt": +2.5 % queries/s, 0.527 -> 0.545 of peak)
@@ -113,7 +120,8 @@ hipError_t fused_bf16_set_attrs();  // mlp_fused_bf16.hip's kernels, on the curr
 //   form: any (any row width) | ring (sls_kernel) | one (one lookup per bag) | flat | flatc (fixed-length bags)
 //   exact: the sequential summation order (bit-identical to Caffe2's SparseLengthsSum)
 //   G, NL, BPW, BW, L, nt: the instance -- lanes per row, loads per lane, bags per wave, samples per wave, bag length,
-//   non-temporal row loads; tiles: one-lookup sample tiles per table; grid: workgroups (0: nothing to launch)
+//   non-temporal row loads (2: table by table, nt_mask bit t -- the one-bag-per-wave forms on fp32 rows under a mixed
+//   "sls_nt_mask"); tiles: one-lookup sample tiles per table; grid: workgroups (0: nothing to launch)
 //   weighted: a query of the launch carries per-sample weights (SlsArgs::wgt): the weighted instance of the form.  With
 //   "sls_weighted_flat" 0 (the default) that is the ring walk or the any-width form, never flat, flatc or one; with 1 the
 //   form is the one the unweighted launch would take
@@ -124,6 +132,7 @@ struct SlsPlan {
   SlsForm form = SlsForm::ring;
   bool exact = false;
   int G = 0, NL = 0, BPW = 1, BW = 0, L = 0, nt = 0;
+  uint32_t nt_mask = 0;
   int tiles = 0;
   int64_t grid = 0;
   int dtype = DRS_TABLE_FP32;
@@ -135,6 +144,8 @@ SlsPlan plan_sls(const SlsArgs& a, bool exact, bool short_bags, const Tune& tune
 // stop_event (optional): recorded by the gather dispatch itself when it completes
 hipError_t launch_sls(const SlsArgs& a, const SlsPlan& plan, const Tune& tune, hipStream_t stream,
                       hipEvent_t stop_event = nullptr);
+// the per-table-policy flatc and split ring launches of launch_sls (sls_ntm.hip; plan.nt == 2, plan.grid > 0)
+hipError_t launch_sls_ntm(const SlsArgs& a, const SlsPlan& plan, hipStream_t stream, hipEvent_t stop_event);
 // the weighted flat, flatc and one-lookup launches of launch_sls (sls_wflat.hip; plan.weighted, plan.grid > 0)
 hipError_t launch_sls_wflat(const SlsArgs& a, const SlsPlan& plan, hipStream_t stream, hipEvent_t stop_event);
 // "table_dtype" layouts.  Stored bytes of one row: D elements of 4 (fp32) or 2 (fp16 / bf16) bytes; int8 rowwise: D codes,

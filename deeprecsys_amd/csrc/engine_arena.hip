@@ -100,6 +100,7 @@ hipError_t probe_gather(drs_engine* e, const float* base, size_t bytes, double* 
   a.out = e->probe_out; a.ld_out = D; a.col0 = 0; a.T = 1; a.D = D; a.err = e->probe_err; a.ts = nullptr;
   Tune t = e->tune;
   t.log = nullptr;
+  t.sls_nt_mask = -1;
   const SlsPlan plan = plan_sls(a, false, L <= e->sls_short_bag, t, DRS_TABLE_FP32);
   Event e0, e1;
   if ((r = e0.create()) != hipSuccess || (r = e1.create()) != hipSuccess) return r;

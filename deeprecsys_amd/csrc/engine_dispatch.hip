@@ -865,7 +865,9 @@ static int32_t sls_op(drs_handle e, const float* d_W, int64_t rows, int32_t D, c
     a.wgt[0] = d_wgt;        // (null: drs_sls; the table is one table, so the weights line up with the indices)
     a.out = d_out; a.ld_out = D; a.col0 = 0; a.T = 1; a.D = D; a.err = d_err; a.ts = nullptr;
     a.pool = e->sls_pool;    // the operator follows the handle: SparseLengthsMean under "sls_pool" 1
-    r = launch_sls(a, plan_sls(a, exact_order != 0, false, e->tune, DRS_TABLE_FP32), e->tune, s.stream);
+    Tune tune = e->tune;
+    tune.sls_nt_mask = -1;   // ("sls_nt_mask" names the model's tables, not the operator's one)
+    r = launch_sls(a, plan_sls(a, exact_order != 0, false, tune, DRS_TABLE_FP32), tune, s.stream);
   }
   if (r == hipSuccess) r = hipStreamSynchronize(s.stream);
   if (r == hipSuccess) r = hipMemcpy(&h_err, d_err, sizeof(int32_t), hipMemcpyDeviceToHost);

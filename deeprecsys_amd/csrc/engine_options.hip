@@ -251,6 +251,16 @@ int32_t set_sls_pool(drs_engine* e, int64_t value) {
   return DRS_OK;
 }
 
+int32_t set_sls_nt_mask(drs_engine* e, int64_t value) {
+  // The row loads' cache policy table by table: bit t set -- table t is read with non-temporal loads, clear -- with plain
+  // ones; -1 (the default): unset, every table takes "sls_nt".  Which of the two is fast depends on the physical memory a
+  // table lies in, and a 2 GB arena spans several such regions.  The mask is a 32-bit kernel argument.
+  if (value >= 0 && (e->T > 32 || (value >> e->T) != 0))
+    return fail(e, DRS_ERR_BAD_ARG, "sls_nt_mask 0x%llx: the model has %d tables (32 at the most take a mask)", (unsigned long long)value, e->T);
+  e->tune.sls_nt_mask = value;
+  return DRS_OK;
+}
+
 int64_t arena_in_use(drs_engine* e) {
   return (int64_t)(std::find_if(e->arenas.begin(), e->arenas.end(), [&](const Arena& a) { return a.p == e->tables; }) - e->arenas.begin());
 }
@@ -261,6 +271,7 @@ const OptDesc kOptions[] = {
     OPT("sls_flat", 0, 2, nullptr, 0, tune.sls_flat),
     OPT("sls_bpw", 0, 4, [](int64_t v) { return v != 3; }, 0, tune.sls_bpw),
     OPT("sls_nt", 0, 1, nullptr, O_BOOL, tune.sls_nt),
+    {"sls_nt_mask", -1, ((int64_t)1 << 32) - 1, nullptr, 0, [](drs_engine* e) -> int64_t { return e->tune.sls_nt_mask; }, nullptr, set_sls_nt_mask},
     OPT("sls_one", 0, 64, [](int64_t v) { return v == 0 || v == 1 || v == 16 || v == 64; }, 0, tune.sls_one),
     // 1: a weighted launch takes the form its unweighted twin takes (flat, flatc, one-lookup: sls_wflat.hip); 0: ring / any only
     OPT("sls_weighted_flat", 0, 1, nullptr, 0, tune.sls_weighted_flat),

@@ -342,6 +342,8 @@ hipError_t launch_sls_e(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hi
   const char* dt = tags;
   const char* sep = *dt ? "," : "";
   const long long wg = (long long)p.grid;
+  char ntm[24] = "";                      // a per-table launch (sls_ntm.hip's kernels): ",ntm=0x<mask>" where a uniform one says ",nt" or nothing
+  if (p.nt == 2) snprintf(ntm, sizeof ntm, ",ntm=0x%x", p.nt_mask);
   if (!wg && (p.form == SlsForm::any || p.form == SlsForm::one)) return hipSuccess;   // (an empty launch of these is not logged)
   switch (p.form) {
     case SlsForm::any:
@@ -349,15 +351,16 @@ hipError_t launch_sls_e(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hi
       break;
     case SlsForm::flat:
     case SlsForm::flatc:
-      log_launch(tune.log, "%s<%d,%d%s%s%s%s>[%lld wg, L=%d]", p.form == SlsForm::flatc ? "sls_flatc_kernel" : "sls_flat_kernel",
+      log_launch(tune.log, "%s<%d,%d%s%s%s%s>[%lld wg, L=%d]", p.form != SlsForm::flatc ? "sls_flat_kernel" : p.nt == 2 ? "sls_flatc_ntm_kernel" : "sls_flatc_kernel",
                  p.G, p.NL, p.form == SlsForm::flatc ? "" : (p.BPW == 4 ? ",bpw4" : p.BPW == 2 ? ",bpw2" : ",bpw1"),
-                 p.nt ? ",nt" : "", sep, dt, wg, p.L);
+                 p.nt == 2 ? ntm : p.nt ? ",nt" : "", sep, dt, wg, p.L);
       break;
     case SlsForm::one:
       log_launch(tune.log, "sls_one_kernel<%d,%d%s%s>[%lld wg]", p.G, p.BW, sep, dt, wg);
       break;
     case SlsForm::ring:
-      log_launch(tune.log, "sls_kernel<%d,%s%s%s>[%lld wg]", p.G, p.exact ? "sequential" : (p.nt ? "split,nt" : "split"), sep, dt, wg);
+      if (p.nt == 2) log_launch(tune.log, "sls_ntm_kernel<%d,split%s>[%lld wg]", p.G, ntm, wg);
+      else log_launch(tune.log, "sls_kernel<%d,%s%s%s>[%lld wg]", p.G, p.exact ? "sequential" : (p.nt ? "split,nt" : "split"), sep, dt, wg);
       break;
   }
   if (!wg) return hipSuccess;             // an empty launch enqueues nothing
@@ -370,6 +373,7 @@ hipError_t launch_sls_e(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hi
       else launch_k(sls_any_kernel<E>, grid, s, stop, a);
       break;
     case SlsForm::flatc:
+      if (p.nt == 2) return launch_sls_ntm(a, p, s, stop);   // (plan_sls: fp32 rows, unweighted; sls_ntm.hip)
       with_int<8, 16, 32>(p.G, [&](auto G) { with_int<5, 10, 20>(p.NL, [&](auto NL) { with_int<0, 1>(p.nt, [&](auto NT) {
         launch_k(sls_flatc_kernel<G, NL, NT != 0, E>, grid, s, stop, a, p.L);
       }); }); });
@@ -387,6 +391,7 @@ hipError_t launch_sls_e(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hi
       }); });
       break;
     case SlsForm::ring:
+      if (p.nt == 2) return launch_sls_ntm(a, p, s, stop);
       with_int<2, 4, 8, 16, 32, 64>(p.G, [&](auto G) { with_int<0, 1>(p.exact, [&](auto EXACT) { with_int<0, 1>(p.nt, [&](auto NT) {
         if constexpr (!(EXACT && NT)) {
           if (p.weighted) launch_k(sls_kernel<G, EXACT != 0, NT != 0, E, true>, grid, s, stop, a);
@@ -399,6 +404,15 @@ hipError_t launch_sls_e(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hi
 }
 
 }  // namespace
+
+// "sls_nt_mask" on the forms whose waves read ONE table each (flatc, the split ring walk), fp32 rows, unweighted: all zeros or
+// all ones is the uniform plain / nt instance, a mixed mask the per-table one (p.nt 2).  Every other launch keeps "sls_nt".
+static void plan_nt_mask(SlsPlan& p, int T, const Tune& tune) {
+  if (tune.sls_nt_mask < 0 || p.dtype != DRS_TABLE_FP32 || p.weighted || T < 1 || T > 32) return;
+  const uint32_t all = T == 32 ? ~0u : (1u << T) - 1u, m = (uint32_t)tune.sls_nt_mask & all;
+  p.nt = m == 0 ? 0 : m == all ? 1 : 2;
+  p.nt_mask = p.nt == 2 ? m : 0;
+}
 
 // Tunables (drs_set_option, kept per engine in Tune): "sls_flat" / "sls_bpw" the flat variant and its bags
 // per wave (0 = auto), "sls_nt" non-temporal row loads, "sls_one" the one-lookup copy form and its samples per wave,
@@ -446,6 +460,7 @@ SlsPlan plan_sls(const SlsArgs& a, bool exact, bool short_bags, const Tune& tune
   if (flat && nl && (bpw == 1 || nl <= 10)) {
     p.form = bpw == 1 && tune.sls_flat == 1 ? SlsForm::flatc : SlsForm::flat;   // "sls_flat" 2 forces the phased form
     p.G = G; p.NL = nl; p.BPW = bpw; p.L = L; p.nt = tune.sls_nt != 0;
+    if (p.form == SlsForm::flatc) plan_nt_mask(p, a.T, tune);
     const unsigned n_work = (unsigned)n_smp * (unsigned)(a.T / bpw);
     p.grid = p.form == SlsForm::flatc ? n_work : 8u * ((n_work + 7u) / 8u);   // (the phased form: whole rounds of 8 XCDs)
     return p;
@@ -470,6 +485,7 @@ SlsPlan plan_sls(const SlsArgs& a, bool exact, bool short_bags, const Tune& tune
   p.form = SlsForm::ring;
   p.G = G;
   p.nt = !p.exact && tune.sls_nt;
+  if (!p.exact) plan_nt_mask(p, a.T, tune);
   p.grid = p.exact ? (n_bags + NG - 1) / NG : n_bags;
   return p;
 }

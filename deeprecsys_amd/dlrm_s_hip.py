@@ -645,6 +645,43 @@ class _HipNet(object):
         eng.get_rows_device(t, ids_ptr, n, out_ptr, stride, stream=_stream_handle(stream))
         return out
 
+    def _takes_nt_mask(self, T, co, bs):
+        """Does a launch set of the preferred size take a mixed "sls_nt_mask" (plan_sls: the flat one-bag-per-wave form on
+        fp32 rows)?  Asked of the dispatch record of one set."""
+        eng = self.engine
+        log0 = int(eng.get_option("dispatch_log"))
+        try:
+            eng.set_option("dispatch_log", 1, user=False)
+            eng.set_option("sls_nt_mask", 1, user=False)
+            nb = int(self._n_staged)
+            eng.forward_multi_async(0, [k % nb for k in range(co)], [bs] * co)
+            eng.wait(0)
+            return any("ntm=" in tok for tok in eng.last_dispatch(0))
+        except N.DrsError:
+            return False
+        finally:
+            eng.set_option("sls_nt_mask", -1, user=False)
+            eng.set_option("dispatch_log", log0, user=False)
+
+    @staticmethod
+    def greedy_nt_mask(read, n_tables, mask, k=3):
+        """One greedy pass over the tables for the per-table load policy ("sls_nt_mask").  read(mask) -> the gather's us under
+        `mask` (bit t: table t read with non-temporal loads).  The starting mask is read k times: its median is the figure to
+        beat and max - min the spread of a reading in this process.  Then table by table, in order, the table's bit is
+        flipped and read k times; the flip is kept only if its median is below the current median by more than that spread.
+        (n_tables + 1) * k readings.  Returns (mask, us, spread, flip_medians, start_us)."""
+        def median(m):
+            v = sorted(read(m) for _ in range(k))
+            return v[len(v) // 2], v[-1] - v[0]
+        cur, spread = median(mask)
+        start, flips = cur, []
+        for t in range(n_tables):
+            us, _ = median(mask ^ (1 << t))
+            flips.append(us)
+            if us < cur - spread:
+                mask, cur = mask ^ (1 << t), us
+        return mask, cur, spread, flips, start
+
     def tune_table_placement(self, candidates=12, sets=128, spacer_gb=None, policies=(1, 0), max_extra_gb=48, sharers=1):
         """Where the tables live in HBM, and with which cache policy their rows are read, moves the many-rows-per-bag
         gather by up to 9 % -- a property of the PHYSICAL memory (it follows the memory through address changes;
@@ -756,15 +793,40 @@ class _HipNet(object):
             first = min((u, 0, policies[i]) for i, u in enumerate(times[0]))
             if best[1] != 0 and best[0] > 0.99 * first[0]:
                 best = first
-            return {"gather_us": [[round(u, 2) for u in tt] for tt in times], "timed": "pipelined, %d sets in flight" % n_slots, "policies": ["nt" if p else "plain" for p in policies],
-                    "kept": best[1], "sls_nt": best[2], "candidates": len(times), "losers": "freed",
-                    "seconds": round(_time.perf_counter() - t_begin, 2)}
+            record = {"gather_us": [[round(u, 2) for u in tt] for tt in times], "timed": "pipelined, %d sets in flight" % n_slots, "policies": ["nt" if p else "plain" for p in policies],
+                      "kept": best[1], "sls_nt": best[2], "candidates": len(times), "losers": "freed"}
+            # Then the policy TABLE BY TABLE on the kept arena ("sls_nt_mask"): the tables lie in different gigabytes of it, and
+            # the regions that are fast under the two policies differ.  Only where a launch takes the mask: DLRM's fp32
+            # tables in the one-bag-per-wave flat form (asked of the dispatch record), a policy the caller did not pin.
+            T = len(self.ln_emb) if hasattr(self, "ln_emb") else 0
+            if (self.kind == N.MODEL_DLRM and len(policies) > 1 and candidates > 1 and 2 <= T <= 32
+                    and int(eng.get_option("table_dtype")) == 0 and "sls_nt_mask" not in getattr(eng, "user_options", ())):
+                eng.set_option("table_placement", best[1], user=False)
+                eng.set_option(nt_key, best[2], user=False)
+                if self._takes_nt_mask(T, co, bs):
+                    def read(m):
+                        eng.set_option("sls_nt_mask", m, user=False)
+                        return gather_us()
+                    start = ((1 << T) - 1) if best[2] else 0
+                    nt_mask, us, spread, flips, start_us = self.greedy_nt_mask(read, T, start, k=3)
+                    uniform = nt_mask in (0, (1 << T) - 1)
+                    if uniform:                     # (every bit flipped: the other uniform policy is what was found and measured)
+                        best = (us, best[1], 1 if nt_mask else 0)
+                        record["sls_nt"] = best[2]
+                    best = best + (-1 if uniform else nt_mask,)
+                    record.update({"sls_nt_mask": None if uniform else "0x%x" % nt_mask, "mask_gather_us": round(us, 2),
+                                   "mask_start_us": round(start_us, 2), "mask_spread_us": round(spread, 3),
+                                   "mask_flip_us": [round(u, 2) for u in flips], "mask_readings": 3 * (T + 1)})
+            record["seconds"] = round(_time.perf_counter() - t_begin, 2)
+            return record
         except N.DrsError:
             return None                                 # (staged sets smaller than a full batch, ...: serve from where it is)
         finally:
             try:
                 eng.set_option("table_alloc", ta0, user=False)
                 eng.set_option(nt_key, best[2] if best else nt0, user=False)
+                if "sls_nt_mask" not in getattr(eng, "user_options", ()):
+                    eng.set_option("sls_nt_mask", best[3] if best and len(best) > 3 else -1, user=False)
                 if best:
                     eng.set_option("table_placement", best[1], user=False)
                 eng.set_option("table_placement", -2, user=False)
