@@ -22,7 +22,8 @@ TABLE_FP8_E4M3 = 4                              # ... OCP fp8 e4m3 codes (torch'
 TABLE_INT8_ROWWISE = 8                          # ... 8-bit codes with an fp32 scale and bias per row (Caffe2's Fused8BitRowwise)
 TABLE_INT4_ROWWISE = 9                          # ... 4-bit codes with an fp16 scale and bias per row (torch's embedding_bag_4bit_prepack; even D)
 POOL_SUM, POOL_MEAN = 0, 1                      # option "sls_pool": a bag's pooled vector is its sum | its mean (the fp32 sum / length)
-MLP_FP32, MLP_BF16 = 0, 2                       # option "mlp_dtype": arithmetic of the FC layers with K, N >= 64 (bf16 operands, fp32 accumulation)
+POOL_MAX = 1                                    # option "sls_max" (a key of its own): a bag's pooled vector is its element-wise maximum (EmbeddingBag(mode="max"); empty bag +0.0, NaN propagates)
+MLP_FP32, MLP_BF16 = 0, 2                      # option "mlp_dtype": arithmetic of the FC layers with K, N >= 64 (bf16 operands, fp32 accumulation)
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 MLP_BOT, MLP_TOP, MLP_FINAL = 0, 1, 2
 MLP_TASK0 = 16     # + k: task head k (MT-WnD)

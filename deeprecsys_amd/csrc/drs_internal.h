@@ -55,6 +55,7 @@ struct SlsArgs {
   uint64_t* ts;               // optional [2 * gridDim.x] start/end wall_clock64() per workgroup
   int32_t nt;                 // fused DIN launch: table rows by non-temporal loads ("sls_nt"; set by launch_din_fused)
   int32_t pool;               // "sls_pool": 0 a bag's sum | 1 its mean, the finished sum / (float)length (sls_dev.h pool_finish)
+                              // | 2 ("sls_max" 1) its element-wise maximum: sls_max.hip's kernels alone see this value
   // int8 / int4 rowwise tables in the line-packed layout ("table_int8_lines" / "table_int4_lines", I8Lines below): row r
   // starts r * PR + (r / n) * ln_pad pieces into its table, r / n == ln_mul ? umulhi(r, ln_mul) >> ln_shift : r.  ln_pad == 0: every other layout.
   uint32_t ln_mul, ln_shift, ln_pad;
@@ -148,6 +149,11 @@ hipError_t launch_sls(const SlsArgs& a, const SlsPlan& plan, const Tune& tune, h
 hipError_t launch_sls_ntm(const SlsArgs& a, const SlsPlan& plan, hipStream_t stream, hipEvent_t stop_event);
 // the weighted flat, flatc and one-lookup launches of launch_sls (sls_wflat.hip; plan.weighted, plan.grid > 0)
 hipError_t launch_sls_wflat(const SlsArgs& a, const SlsPlan& plan, hipStream_t stream, hipEvent_t stop_event);
+// max pooling ("sls_max" 1; sls_max.hip): plan_sls and launch_sls hand every launch whose SlsArgs::pool is 2 to these two.
+// The plan says SlsForm::any (sls_max_any_kernel), SlsForm::flat (sls_max_kernel<G, NL, BPW, nt>) or SlsForm::one (the
+// one-lookup copy form itself, launched with pool 0: a one-row bag's maximum is its row)
+SlsPlan plan_sls_max(const SlsArgs& a, const Tune& tune, int dtype);
+hipError_t launch_sls_max(const SlsArgs& a, const SlsPlan& plan, const Tune& tune, hipStream_t stream, hipEvent_t stop_event);
 // "table_dtype" layouts.  Stored bytes of one row: D elements of 4 (fp32) or 2 (fp16 / bf16) bytes; int8 rowwise: D codes,
 // zero padding to round_up(D, 8), fp32 scale, fp32 bias (every row 8-byte aligned); int4 rowwise: D / 2 code bytes, zero
 // padding to round_up(D / 2, 4), fp16 scale, fp16 bias (every row 4-byte aligned; D even); fp8 e4m3: D codes of one byte,

@@ -226,6 +226,7 @@ struct drs_engine {
   int mlp_dtype = DRS_MLP_FP32;     // "mlp_dtype": DRS_MLP_BF16 -- the FC layers with K >= 64 and N >= 64 on the bf16 matrix cores (bf16_layer)
   int mlp_bf16_fuse = 0;            // "mlp_bf16_fuse": with "mlp_dtype" 2, DLRM's and NCF's one-launch forms keep their bf16 layers (mlp_fused_bf16.hip)
   int sls_pool = 0;                 // "sls_pool": 1 -- every bag's pooled vector is its mean, the gather's fp32 sum / (float)length (SlsArgs::pool)
+  int sls_max = 0;                  // "sls_max": 1 -- every bag's pooled vector is its element-wise maximum (SlsArgs::pool 2, sls_max.hip); never with "sls_pool" 1
   int table_dtype = DRS_TABLE_FP32; // "table_dtype": element type of the arena (DRS_TABLE_*); sums and outputs stay fp32
   int table_int8_lines = 0;         // "table_int8_lines": an int8 rowwise arena keeps every row inside one 128-byte line (drs_internal.h I8Lines)
   int table_int4_lines = 0;         // "table_int4_lines": the same for an int4 rowwise arena (2-byte pieces)

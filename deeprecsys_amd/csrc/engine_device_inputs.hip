@@ -95,6 +95,8 @@ int32_t check_device_set(drs_engine* e, int32_t slot, const DeviceSet& d, int64_
         return fail(e, DRS_ERR_UNSUPPORTED, "drs_run_queues_device_weighted_multi_async: DIN and DIEN pool their bags by the plain sum only");
       if (e->sls_pool)
         return fail(e, DRS_ERR_UNSUPPORTED, "drs_run_queues_device_weighted_multi_async: \"sls_pool\" 1 has no weighted form (there is no weighted mean)");
+      if (e->sls_max)
+        return fail(e, DRS_ERR_UNSUPPORTED, "drs_run_queues_device_weighted_multi_async: \"sls_max\" 1 has no weighted form (there is no weighted maximum)");
       const int32_t ty = d.weight_type(i);
       if (ty != DRS_TABLE_FP32 && ty != DRS_TABLE_FP16 && ty != DRS_TABLE_BF16)
         return fail(e, DRS_ERR_BAD_ARG, "query %d: wgt_dtype=%d: 0 (fp32), 1 (fp16) or 2 (bf16)", i, ty);

@@ -317,7 +317,7 @@ static int32_t launch_gather(SetCtx& x) {
   a.ts = prof ? s.d_ts : nullptr;
   a.ln_mul = e->i8l.mul; a.ln_shift = e->i8l.shift; a.ln_pad = e->i8l.pad;   // ("table_int8_lines" / "table_int4_lines": zeros for every other layout)
   a.tab_scale = e->table_dtype == DRS_TABLE_FP8_E4M3 ? e->d_tab_scale : nullptr;   // (read by the fp8 instances alone)
-  a.pool = e->sls_pool;      // ("sls_pool": DIN and DIEN refuse 1, so the fused DIN launch never sees it)
+  a.pool = e->sls_max ? 2 : e->sls_pool;   // ("sls_pool" / "sls_max": DIN and DIEN refuse 1, so the fused DIN launch never sees either)
   // short bags (W&D / NCF: one lookup per table) take the sequential lane-group-per-bag form (plan_sls); the queries'
   // own bag lengths count here, also when "sls_uniform" 0 keeps them from the kernels
   bool short_bags = true;
@@ -864,7 +864,7 @@ static int32_t sls_op(drs_handle e, const float* d_W, int64_t rows, int32_t D, c
     a.idx[0] = d_idx; a.off[0] = d_off; a.uniform_len[0] = -1;
     a.wgt[0] = d_wgt;        // (null: drs_sls; the table is one table, so the weights line up with the indices)
     a.out = d_out; a.ld_out = D; a.col0 = 0; a.T = 1; a.D = D; a.err = d_err; a.ts = nullptr;
-    a.pool = e->sls_pool;    // the operator follows the handle: SparseLengthsMean under "sls_pool" 1
+    a.pool = e->sls_max ? 2 : e->sls_pool;   // the operator follows the handle: SparseLengthsMean under "sls_pool" 1, the maximum under "sls_max" 1
     Tune tune = e->tune;
     tune.sls_nt_mask = -1;   // ("sls_nt_mask" names the model's tables, not the operator's one)
     r = launch_sls(a, plan_sls(a, exact_order != 0, false, tune, DRS_TABLE_FP32), tune, s.stream);
@@ -887,6 +887,7 @@ int32_t drs_sls_weighted(drs_handle e, const float* d_W, int64_t rows, int32_t D
   if (rc) return rc;
   if (!d_wgt && n_idx > 0) return fail(e, DRS_ERR_BAD_ARG, "drs_sls_weighted: null weights");
   if (e->sls_pool) return fail(e, DRS_ERR_UNSUPPORTED, "drs_sls_weighted: \"sls_pool\" 1 has no weighted form (there is no weighted mean)");
+  if (e->sls_max) return fail(e, DRS_ERR_UNSUPPORTED, "drs_sls_weighted: \"sls_max\" 1 has no weighted form (there is no weighted maximum)");
   return sls_op(e, d_W, rows, D, d_idx, d_wgt, d_len, n_bags, n_idx, d_out, exact_order);
 }
 

@@ -281,6 +281,7 @@ int32_t drs_stage_batch_weights(drs_handle e, int32_t batch_id, const float* con
   if (e->kind == DRS_MODEL_DIN || e->kind == DRS_MODEL_DIEN)
     return fail(e, DRS_ERR_UNSUPPORTED, "drs_stage_batch_weights: DIN and DIEN pool their bags by the plain sum only");
   if (e->sls_pool) return fail(e, DRS_ERR_UNSUPPORTED, "drs_stage_batch_weights: \"sls_pool\" 1 has no weighted form (there is no weighted mean)");
+  if (e->sls_max) return fail(e, DRS_ERR_UNSUPPORTED, "drs_stage_batch_weights: \"sls_max\" 1 has no weighted form (there is no weighted maximum)");
   if (!h_wgt || !n_idx) return fail(e, DRS_ERR_BAD_ARG, "null weight/count arrays");
   Batch& b = e->batches[batch_id];
   if (!b.staged) return fail(e, DRS_ERR_STATE, "batch %d is not staged", batch_id);

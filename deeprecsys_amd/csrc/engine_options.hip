@@ -247,7 +247,25 @@ int32_t set_sls_pool(drs_engine* e, int64_t value) {
   // (there is no weighted mean: torch's EmbeddingBag takes per_sample_weights under mode="sum" only)
   if (value && weighted_batches(e))
     return fail(e, DRS_ERR_UNSUPPORTED, "sls_pool %lld: %lld staged batches carry per-sample weights", (long long)value, (long long)weighted_batches(e));
+  if (value && e->sls_max)
+    return fail(e, DRS_ERR_UNSUPPORTED, "sls_pool %lld: the engine pools by the maximum (\"sls_max\" 1): set that to 0 first", (long long)value);
   e->sls_pool = (int)value;
+  return DRS_OK;
+}
+
+int32_t set_sls_max(drs_engine* e, int64_t value) {
+  // Max pooling: every later launch carries SlsArgs::pool 2 and is planned and launched by sls_max.hip.  One field, as
+  // "sls_pool": nothing is converted, allocated or chosen again.  A key of its own, not a third value of "sls_pool", whose
+  // range 0|1 is part of the frozen option set.  Refused like mean: DIN and DIEN pool by sum only, and there is no weighted
+  // maximum (torch's EmbeddingBag takes per_sample_weights under mode="sum" only); and one pooling at a time.
+  if (value == e->sls_max) return DRS_OK;
+  if (e->kind == DRS_MODEL_DIN || e->kind == DRS_MODEL_DIEN)
+    return fail(e, DRS_ERR_UNSUPPORTED, "sls_max %lld: DIN and DIEN pool their bags by sum only", (long long)value);
+  if (value && e->sls_pool)
+    return fail(e, DRS_ERR_UNSUPPORTED, "sls_max %lld: the engine pools by the mean (\"sls_pool\" 1): set that to 0 first", (long long)value);
+  if (value && weighted_batches(e))
+    return fail(e, DRS_ERR_UNSUPPORTED, "sls_max %lld: %lld staged batches carry per-sample weights", (long long)value, (long long)weighted_batches(e));
+  e->sls_max = (int)value;
   return DRS_OK;
 }
 
@@ -277,6 +295,8 @@ const OptDesc kOptions[] = {
     OPT("sls_weighted_flat", 0, 1, nullptr, 0, tune.sls_weighted_flat),
     // 1: SparseLengthsMean / EmbeddingBag(mode="mean") -- the same gather form's fp32 sum, divided by the bag's length
     {"sls_pool", 0, 1, nullptr, O_SYNC, [](drs_engine* e) -> int64_t { return e->sls_pool; }, nullptr, set_sls_pool},
+    // 1: EmbeddingBag(mode="max") -- a bag's element-wise maximum, an empty bag +0.0, NaN propagates (sls_max.hip)
+    {"sls_max", 0, 1, nullptr, O_SYNC, [](drs_engine* e) -> int64_t { return e->sls_max; }, nullptr, set_sls_max},
     OPT("din_fused", 0, 1, nullptr, O_BOOL, din_fused),
     OPT("din_pipe", 0, 1, nullptr, O_BOOL, tune.din_pipe),
     OPT("din_s", 0, 4, [](int64_t v) { return v != 3; }, 0, tune.din_s),

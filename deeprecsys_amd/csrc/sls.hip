@@ -418,6 +418,7 @@ static void plan_nt_mask(SlsPlan& p, int T, const Tune& tune) {
 // per wave (0 = auto), "sls_nt" non-temporal row loads, "sls_one" the one-lookup copy form and its samples per wave,
 // "sls_weighted_flat" whether a weighted launch may take those forms.
 SlsPlan plan_sls(const SlsArgs& a, bool exact, bool short_bags, const Tune& tune, int dtype) {
+  if (a.pool == 2) return plan_sls_max(a, tune, dtype);   // "sls_max" 1: a planner and kernels of its own (sls_max.hip)
   SlsPlan p;
   p.dtype = dtype;
   const int D = a.D, n_q = a.q.n_q, n_smp = a.q.cum[n_q];
@@ -492,6 +493,7 @@ SlsPlan plan_sls(const SlsArgs& a, bool exact, bool short_bags, const Tune& tune
 
 hipError_t launch_sls(const SlsArgs& a, const SlsPlan& p, const Tune& tune, hipStream_t s, hipEvent_t stop) {
   if (a.D <= 0) return hipErrorInvalidValue;
+  if (a.pool == 2) return launch_sls_max(a, p, tune, s, stop);
   switch (p.dtype) {
     case DRS_TABLE_FP16: return launch_sls_e<F16>(a, p, tune, s, stop);
     case DRS_TABLE_BF16: return launch_sls_e<BF16>(a, p, tune, s, stop);

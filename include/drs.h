@@ -304,7 +304,12 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  *                 divided by (float)len, one correctly rounded division per element, an empty bag stays +0.0; DLRM, W&D,
  *                 MT-WnD and NCF only; set before or after the table options; same launch forms, same drs_gather_bytes;
  *                 refused while a staged batch carries weights, drs_stage_batch_weights)
- *                 "sls_flat" 0|1|2   "sls_bpw" 0|1|2|4   "sls_nt" 0|1   "sls_one" 0|1|16|64
+ *                 "sls_max" 0|1 (1: max pooling, EmbeddingBag(mode="max") -- a bag's element-wise maximum over the rows it
+ *                 names, each row as its stored value widened to fp32; an empty bag is +0.0; a NaN in a named row reaches
+ *                 the result (torch.amax's rule); the sign of a zero maximum is unspecified when +0 and -0 both occur;
+ *                 every other result is the same under every form and launch shape; drs_sls follows the handle; DLRM,
+ *                 W&D, MT-WnD and NCF only; refused together with "sls_pool" 1 and with per-sample weights)
+ *                 "sls_flat" 0|1|2  "sls_bpw" 0|1|2|4   "sls_nt" 0|1   "sls_one" 0|1|16|64
  *                 "sls_weighted_flat" 0|1 (1: a launch set that carries per-sample weights, drs_stage_batch_weights, takes
  *                 the gather form its unweighted twin takes -- flat, flat-coalesced, one-lookup -- in that form's order;
  *                 0, the default: the ring walk or the any-width form)
