@@ -97,6 +97,7 @@ struct Tune {
   int gemm32_small = 0;          // ... and smaller launches this gemm32 shape (0 = gemm_kernel | 22 | 21 | 12 | 11)
   int gemm32_blocks = 512;       // ... when its 128 x 128 workgroups number at least this many (two per CU)
   int bf16_tile = 0;             // gemm_bf16_kernel's tile shape (0 = by workgroup count | 44 | 22 | 12; gemm_bf16.hip gemm_bf16_plan)
+  int i8_tile = 0;               // gemm_i8_kernel's tile shape, likewise ("mlp_i8_tile"; gemm_i8.hip gemm_i8_plan)
   int64_t mlp_rows32 = 0;        // stream4_kernel: launches of at least this many rows take 32 rows per workgroup (0 = never)
   DispatchLog* log = nullptr;    // where the launch functions note what they chose (the slot being enqueued; may be null)
   // stream4_kernel's column-split form (mlp.hip SArgs::ns): launches of at most mlp_nsplit_rows rows spread the first
@@ -115,6 +116,7 @@ hipError_t device_init(int device, const float** zero_page);
 hipError_t mlp_set_attrs();    // mlp.hip's kernels, on the current device
 hipError_t gemm_set_attrs();   // gemm.hip's kernels, on the current device
 hipError_t gemm_bf16_set_attrs();   // gemm_bf16.hip's kernels, on the current device
+hipError_t gemm_i8_set_attrs();     // gemm_i8.hip's kernels, on the current device
 hipError_t fused_bf16_set_attrs();  // mlp_fused_bf16.hip's kernels, on the current device
 
 // One gather launch, decided once by plan_sls and run by launch_sls (sls.hip, sls_wflat.hip).  Host-only.
@@ -374,6 +376,13 @@ hipError_t launch_pack_stream_weights(const float* W, int32_t K, int32_t N, floa
 // nearest even (NaN stays NaN), zeros from K on
 inline int32_t bf16_kpad(int32_t K) { return (K + 63) / 64 * 64; }
 hipError_t launch_bf16_twin(const float* W, int32_t K, int32_t N, uint16_t* Wb, hipStream_t stream);
+
+// "mlp_int8" 1: the int8 twin of one FC layer (gemm_i8.hip): W [N, K] fp32 -> Wq [N, i8_kpad(K)] codes in [-127, 127] (zeros
+// from K on) and sw [N], each row's absmax / 127 (NaN for a row holding a NaN or an infinity, 0 below 2^-119).  kI8MaxK:
+// the longest row whose exact sum of products stays inside int32
+inline int32_t i8_kpad(int32_t K) { return (K + 63) / 64 * 64; }
+constexpr int32_t kI8MaxK = 131072;
+hipError_t launch_i8_twin(const float* W, int32_t K, int32_t N, int8_t* Wq, float* sw, hipStream_t stream);
 
 // random 128- / 256- / 512-byte row reads over [base, base + bytes) in the gather's access shape, timed with events on `s`
 // (sls_probe.hip probe_rows_kernel, lab build only); sink: >= 1 KiB of device memory nobody reads

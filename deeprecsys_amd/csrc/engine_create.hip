@@ -18,6 +18,7 @@ hipError_t device_init(int device, const float** zero_page) {
     if (e == hipSuccess) e = mlp_set_attrs();
     if (e == hipSuccess) e = gemm_set_attrs();
     if (e == hipSuccess) e = gemm_bf16_set_attrs();
+    if (e == hipSuccess) e = gemm_i8_set_attrs();
     if (e == hipSuccess) e = fused_bf16_set_attrs();
     if (e == hipSuccess && !zero[device]) {
       e = hipMalloc(reinterpret_cast<void**>(&zero[device]), 256);
@@ -77,6 +78,17 @@ hipError_t build_bf16_twin(Layer& L) {
   r = launch_bf16_twin(L.W, L.n, L.m, L.Wb, nullptr);
   if (r == hipSuccess) r = hipStreamSynchronize(nullptr);
   if (r != hipSuccess && fresh) L.Wb.reset();
+  return r;
+}
+
+hipError_t build_i8_twin(Layer& L) {
+  const bool fresh = !L.Wq;
+  hipError_t r = fresh ? L.Wq.alloc((size_t)L.m * i8_kpad(L.n)) : hipSuccess;
+  if (r == hipSuccess && fresh && (r = L.wscale.alloc((size_t)L.m)) != hipSuccess) L.Wq.reset();
+  if (r != hipSuccess) return r;
+  r = launch_i8_twin(L.W, L.n, L.m, L.Wq, L.wscale, nullptr);
+  if (r == hipSuccess) r = hipStreamSynchronize(nullptr);
+  if (r != hipSuccess && fresh) { L.Wq.reset(); L.wscale.reset(); }
   return r;
 }
 
@@ -600,6 +612,13 @@ int32_t drs_set_fc(drs_handle e, int32_t mlp, int32_t layer, const float* h_W, c
     (void)hipGetLastError();
     return fail(e, DRS_ERR_OOM, "no room for the bf16 twin of the %dx%d layer", n, m);
   }
+  // ... and an int8 layer ("mlp_int8" 1) its int8 twin and weight scales, likewise
+  const bool twin8 = L.packed && i8_shape(e, n, m);
+  if (twin8 && !L.Wq && (L.Wq.alloc((size_t)m * i8_kpad(n)) != hipSuccess || L.wscale.alloc((size_t)m) != hipSuccess)) {
+    (void)hipGetLastError();
+    L.Wq.reset(); L.wscale.reset();
+    return fail(e, DRS_ERR_OOM, "no room for the int8 twin of the %dx%d layer", n, m);
+  }
   HIP_TRY(e, hipMemcpy(L.W, h_W, sizeof(float) * (size_t)m * n, hipMemcpyHostToDevice));
   HIP_TRY(e, hipMemcpy(L.b, h_b, sizeof(float) * (size_t)m, hipMemcpyHostToDevice));
   if (L.packed) {
@@ -609,6 +628,7 @@ int32_t drs_set_fc(drs_handle e, int32_t mlp, int32_t layer, const float* h_W, c
   }
   L.m = m; L.n = n; L.set = true;
   if (twin) HIP_TRY(e, build_bf16_twin(L));
+  if (twin8) HIP_TRY(e, build_i8_twin(L));
   return DRS_OK;
 }
 

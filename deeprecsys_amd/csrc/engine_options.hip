@@ -213,6 +213,8 @@ int32_t set_mlp_dtype(drs_engine* e, int64_t value) {
   if (value == e->mlp_dtype) return DRS_OK;
   if (e->kind == DRS_MODEL_DIN || e->kind == DRS_MODEL_DIEN)
     return fail(e, DRS_ERR_UNSUPPORTED, "mlp_dtype %lld: the DIN and DIEN launches run their FC layers in fp32 only", (long long)value);
+  if (value == DRS_MLP_BF16 && e->mlp_int8)
+    return fail(e, DRS_ERR_UNSUPPORTED, "mlp_dtype %lld: the wide layers run in int8 (\"mlp_int8\" 1): set that to 0 first", (long long)value);
   const int from = e->mlp_dtype;
   e->mlp_dtype = (int)value;
   std::vector<Layer*> built;
@@ -228,6 +230,34 @@ int32_t set_mlp_dtype(drs_engine* e, int64_t value) {
     for (Layer* L : built) L->Wb.reset();
     e->mlp_dtype = from;
     return fail(e, r == hipErrorOutOfMemory ? DRS_ERR_OOM : DRS_ERR_HIP, "mlp_dtype: the layers' bf16 twins: %s", hipGetErrorString(r));
+  }
+  return DRS_OK;
+}
+
+int32_t set_mlp_int8(drs_engine* e, int64_t value) {
+  // 1: every layer already set that is an int8 layer by its shape (i8_shape) gets its int8 twin and weight scales now,
+  // layers set later get theirs in drs_set_fc; back to 0 the twins are freed.  All twins or none, as "mlp_dtype".  A key of
+  // its own, not a third value of "mlp_dtype", whose values 0|2 are part of the frozen option set; and one narrow
+  // arithmetic at a time.
+  if (value == e->mlp_int8) return DRS_OK;
+  if (e->kind == DRS_MODEL_DIN || e->kind == DRS_MODEL_DIEN)
+    return fail(e, DRS_ERR_UNSUPPORTED, "mlp_int8 %lld: the DIN and DIEN launches run their FC layers in fp32 only", (long long)value);
+  if (value && e->mlp_dtype == DRS_MLP_BF16)
+    return fail(e, DRS_ERR_UNSUPPORTED, "mlp_int8 %lld: the wide layers run in bf16 (\"mlp_dtype\" 2): set that to 0 first", (long long)value);
+  e->mlp_int8 = (int)value;
+  std::vector<Layer*> built;
+  hipError_t r = hipSuccess;
+  for (Mlp* m : served_mlps(e))
+    for (Layer& L : m->layers) {
+      if (!value) { L.Wq.reset(); L.wscale.reset(); continue; }
+      if (r != hipSuccess || !L.set || L.Wq || !i8_shape(e, L.n, L.m)) continue;
+      if ((r = build_i8_twin(L)) == hipSuccess) built.push_back(&L);
+    }
+  if (r != hipSuccess) {
+    (void)hipGetLastError();
+    for (Layer* L : built) { L->Wq.reset(); L->wscale.reset(); }
+    e->mlp_int8 = 0;
+    return fail(e, r == hipErrorOutOfMemory ? DRS_ERR_OOM : DRS_ERR_HIP, "mlp_int8: the layers' int8 twins: %s", hipGetErrorString(r));
   }
   return DRS_OK;
 }
@@ -324,6 +354,10 @@ const OptDesc kOptions[] = {
     // bf16 layers inside it (mlp_fused_bf16.hip)
     OPT("mlp_bf16_fuse", 0, 1, nullptr, 0, mlp_bf16_fuse),
     OPT("mlp_bf16_tile", 0, 44, [](int64_t v) { return v == 0 || v == 44 || v == 22 || v == 12; }, 0, tune.bf16_tile),
+    // 1: the same layers on the int8 matrix cores, per-row dynamic activation scales and per-channel weight scales (gemm_i8.hip;
+    // never with "mlp_dtype" 2); "mlp_i8_tile": force a tile shape
+    {"mlp_int8", 0, 1, nullptr, O_SYNC, [](drs_engine* e) -> int64_t { return e->mlp_int8; }, nullptr, set_mlp_int8},
+    OPT("mlp_i8_tile", 0, 44, [](int64_t v) { return v == 0 || v == 44 || v == 22 || v == 12; }, 0, tune.i8_tile),
     // streams, host side
     OPT("shared_stream", 0, 2, nullptr, O_SYNC | O_STREAMS, shared_stream),
     OPT("mlp_streams", 1, 8, nullptr, O_SYNC | O_STREAMS, mlp_streams),

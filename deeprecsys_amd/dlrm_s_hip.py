@@ -47,7 +47,8 @@ def _table_dtype(args):
     return _TABLE_DTYPES[name]
 
 
-_MLP_DTYPES = {"fp32": N.MLP_FP32, "bf16": N.MLP_BF16}
+# ("int8" is a key of its own, "mlp_int8": the engine's "mlp_dtype" stays fp32 under it -- _mlp_int8)
+_MLP_DTYPES = {"fp32": N.MLP_FP32, "bf16": N.MLP_BF16, "int8": N.MLP_FP32}
 
 
 def _mlp_dtype(args):
@@ -56,6 +57,12 @@ def _mlp_dtype(args):
     if name not in _MLP_DTYPES:
         raise ValueError("--accel_mlp_dtype %r: one of %s" % (name, ", ".join(_MLP_DTYPES)))
     return _MLP_DTYPES[name]
+
+
+def _mlp_int8(args):
+    """--accel_mlp_dtype int8 -> the engine's "mlp_int8" value (0 for every other word)."""
+    _mlp_dtype(args)
+    return int(str(getattr(args, "accel_mlp_dtype", "fp32") or "fp32") == "int8")
 
 
 def _mlp_bf16_fuse(args):
@@ -346,6 +353,7 @@ class _HipNet(object):
         max_batch = max(int(getattr(a, "max_mini_batch_size", 1)), int(getattr(a, "mini_batch_size", 1)), 1)
         dtype = _table_dtype(a)
         mlp_dtype = _mlp_dtype(a)
+        mlp_int8 = _mlp_int8(a)
         bf16_fuse = _mlp_bf16_fuse(a)
         int8_lines = _table_int8_lines(a)
         int4_lines = _table_int4_lines(a)
@@ -374,6 +382,9 @@ class _HipNet(object):
             # engine is never told)
             if mlp_dtype != N.MLP_FP32:
                 eng.set_option("mlp_dtype", mlp_dtype)
+            # --accel_mlp_dtype int8: the same place, the key "mlp_int8" (only when asked for, and no "mlp_dtype" with it)
+            if mlp_int8:
+                eng.set_option("mlp_int8", mlp_int8)
             # --accel_mlp_bf16_fuse: behind it, and only when asked for
             if bf16_fuse:
                 eng.set_option("mlp_bf16_fuse", bf16_fuse)

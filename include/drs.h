@@ -320,6 +320,12 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  *                 "mlp_nsplit" 0|2|4   "mlp_nsplit_rows" n   "mlp_gemm_tile" 0|22|12|21|11|214|322|321|312|311
  *                 "mlp_dtype" 0|2 (DRS_MLP_FP32 | DRS_MLP_BF16; DLRM, W&D, MT-WnD and NCF only)   "mlp_bf16_tile" 0|44|22|12
  *                 "mlp_bf16_fuse" 0|1 (1 with "mlp_dtype" 2: DLRM's and NCF's one-launch forms keep their bf16 layers; same results)
+ *                 "mlp_int8" 0|1 (1: the FC layers with 64 <= K <= 131 072 and N >= 64 on the int8 matrix cores -- each
+ *                 row of the input and each row of the weights quantized to codes in [-127, 127] by its own absmax / 127,
+ *                 the products summed exactly in int32, y = act((float)sum * (sx * sw) + b) in three fp32 roundings; a row
+ *                 holding a NaN or an infinity gives NaN; an output depends on its input row and weight row alone; the
+ *                 operator-level FC call follows the handle; DLRM, W&D, MT-WnD and NCF only; refused while "mlp_dtype" is
+ *                 2, which is refused while this is 1)   "mlp_i8_tile" 0|44|22|12
  *   streams, host "shared_stream" 0|1|2   "mlp_streams" 1..8   "host_threads" -1..64
  *                 "zero_copy_inputs" 1|2|3   "out_dma" bytes   "dispatch_log" 0|1
  *   table arena   "table_placement" -1|-2|k   "table_alloc" 0|1|2   "table_spacer" bytes
