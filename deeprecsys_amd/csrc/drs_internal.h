@@ -98,6 +98,7 @@ struct Tune {
   int gemm32_blocks = 512;       // ... when its 128 x 128 workgroups number at least this many (two per CU)
   int bf16_tile = 0;             // gemm_bf16_kernel's tile shape (0 = by workgroup count | 44 | 22 | 12; gemm_bf16.hip gemm_bf16_plan)
   int i8_tile = 0;               // gemm_i8_kernel's tile shape, likewise ("mlp_i8_tile"; gemm_i8.hip gemm_i8_plan)
+  int mx_tile = 0;               // gemm_mxfp8_kernel's tile shape, likewise ("mlp_mx_tile"; gemm_mxfp8.hip gemm_mxfp8_plan)
   int64_t mlp_rows32 = 0;        // stream4_kernel: launches of at least this many rows take 32 rows per workgroup (0 = never)
   DispatchLog* log = nullptr;    // where the launch functions note what they chose (the slot being enqueued; may be null)
   // stream4_kernel's column-split form (mlp.hip SArgs::ns): launches of at most mlp_nsplit_rows rows spread the first
@@ -117,6 +118,7 @@ hipError_t mlp_set_attrs();    // mlp.hip's kernels, on the current device
 hipError_t gemm_set_attrs();   // gemm.hip's kernels, on the current device
 hipError_t gemm_bf16_set_attrs();   // gemm_bf16.hip's kernels, on the current device
 hipError_t gemm_i8_set_attrs();     // gemm_i8.hip's kernels, on the current device
+hipError_t gemm_mxfp8_set_attrs();  // gemm_mxfp8.hip's kernels, on the current device
 hipError_t fused_bf16_set_attrs();  // mlp_fused_bf16.hip's kernels, on the current device
 
 // One gather launch, decided once by plan_sls and run by launch_sls (sls.hip, sls_wflat.hip).  Host-only.
@@ -383,6 +385,13 @@ hipError_t launch_bf16_twin(const float* W, int32_t K, int32_t N, uint16_t* Wb, 
 inline int32_t i8_kpad(int32_t K) { return (K + 63) / 64 * 64; }
 constexpr int32_t kI8MaxK = 131072;
 hipError_t launch_i8_twin(const float* W, int32_t K, int32_t N, int8_t* Wq, float* sw, hipStream_t stream);
+
+// "mlp_mxfp8" 1: the MX twin of one FC layer (gemm_mxfp8.hip): W [N, K] fp32 -> Wq [N, mx_kpad(K)] OCP e4m3 codes (zeros from
+// K on), We [N, mx_kpad(K) / 32] E8M0 scale bytes, one per 32 consecutive k, and wbad [mx_flags(N)] (1: the row holds a NaN or
+// an infinity; the bytes from N on are never written and never used)
+inline int32_t mx_kpad(int32_t K) { return (K + 127) / 128 * 128; }
+inline size_t mx_flags(int32_t N) { return ((size_t)N + 3) / 4 * 4; }
+hipError_t launch_mx_twin(const float* W, int32_t K, int32_t N, uint8_t* Wq, uint8_t* We, uint8_t* wbad, hipStream_t stream);
 
 // random 128- / 256- / 512-byte row reads over [base, base + bytes) in the gather's access shape, timed with events on `s`
 // (sls_probe.hip probe_rows_kernel, lab build only); sink: >= 1 KiB of device memory nobody reads

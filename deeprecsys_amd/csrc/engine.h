@@ -83,6 +83,7 @@ struct Layer {
   DeviceBuf<uint16_t> Wb;  // "mlp_dtype" 2, K >= 64 and N >= 64: the bf16 twin [m, bf16_kpad(n)] (an allocation of its own)
   DeviceBuf<int8_t> Wq;    // "mlp_int8" 1, the same shapes: the int8 twin [m, i8_kpad(n)] ...
   DeviceBuf<float> wscale; // ... and its per-output-channel scales [m] (allocations of their own; both or neither)
+  DeviceBuf<uint8_t> Mq, Me, Mbad;  // "mlp_mxfp8" 1, the same shapes: the MX twin -- e4m3 codes [m, mx_kpad(n)], E8M0 scale bytes [m, mx_kpad(n) / 32], non-finite flags [mx_flags(m)] (all three or none)
 };
 
 struct Mlp : MlpShape {       // ln, sigmoid_layer (model_shape.h) ...
@@ -228,6 +229,7 @@ struct drs_engine {
   int mlp_dtype = DRS_MLP_FP32;     // "mlp_dtype": DRS_MLP_BF16 -- the FC layers with K >= 64 and N >= 64 on the bf16 matrix cores (bf16_layer)
   int mlp_bf16_fuse = 0;            // "mlp_bf16_fuse": with "mlp_dtype" 2, DLRM's and NCF's one-launch forms keep their bf16 layers (mlp_fused_bf16.hip)
   int mlp_int8 = 0;                 // "mlp_int8": 1 -- the same layers on the int8 matrix cores, dynamic per-row activation scales (i8_shape, gemm_i8.hip); never with "mlp_dtype" 2
+  int mlp_mxfp8 = 0;                // "mlp_mxfp8": 1 -- the same layers in MXFP8 on the block-scaled matrix cores (mx_shape, gemm_mxfp8.hip); never with "mlp_dtype" 2 or "mlp_int8" 1
   int sls_pool = 0;                 // "sls_pool": 1 -- every bag's pooled vector is its mean, the gather's fp32 sum / (float)length (SlsArgs::pool)
   int sls_max = 0;                  // "sls_max": 1 -- every bag's pooled vector is its element-wise maximum (SlsArgs::pool 2, sls_max.hip); never with "sls_pool" 1
   int table_dtype = DRS_TABLE_FP32; // "table_dtype": element type of the arena (DRS_TABLE_*); sums and outputs stay fp32
@@ -360,11 +362,15 @@ void choose_launch_forms(drs_engine* e);
 inline bool bf16_shape(const drs_engine* e, int64_t K, int64_t N) { return e->mlp_dtype == DRS_MLP_BF16 && K >= 64 && N >= 64; }
 // "mlp_int8" 1: is the K x N layer an int8 layer?  The same shape rule, and a row short enough for an exact int32 sum
 inline bool i8_shape(const drs_engine* e, int64_t K, int64_t N) { return e->mlp_int8 && K >= 64 && N >= 64 && K <= kI8MaxK; }
+// "mlp_mxfp8" 1: is the K x N layer an MXFP8 layer?  The shape rule alone: the sum is fp32, so K has no upper limit
+inline bool mx_shape(const drs_engine* e, int64_t K, int64_t N) { return e->mlp_mxfp8 && K >= 64 && N >= 64; }
 // every MLP the launch sets run (bottom, top, final, task heads; not DIN's units or DIEN's recurrent layers) ...
 std::vector<Mlp*> served_mlps(drs_engine* e);
 // ... and the bf16 twin of one of their layers, built from its weights on the device (hipErrorOutOfMemory: nothing changed)
 hipError_t build_bf16_twin(Layer& L);
 hipError_t build_i8_twin(Layer& L);     // ... and its int8 twin with the weight scales, likewise
+hipError_t build_mx_twin(Layer& L);     // ... and its MX twin (codes, scale bytes, flags), likewise
+void free_mx_twin(Layer& L);
 // where the tables of an arena of type `dtype` start (*off, units of table_unit_bytes) and its bytes; lines: "table_int8_lines" / "table_int4_lines", the option of that type
 size_t table_layout(const drs_engine* e, int dtype, std::vector<int64_t>* off, int lines = 0);
 // the first byte of table t in the arena of type `dtype` at `base` whose tables start at off[]

@@ -19,6 +19,7 @@ hipError_t device_init(int device, const float** zero_page) {
     if (e == hipSuccess) e = gemm_set_attrs();
     if (e == hipSuccess) e = gemm_bf16_set_attrs();
     if (e == hipSuccess) e = gemm_i8_set_attrs();
+    if (e == hipSuccess) e = gemm_mxfp8_set_attrs();
     if (e == hipSuccess) e = fused_bf16_set_attrs();
     if (e == hipSuccess && !zero[device]) {
       e = hipMalloc(reinterpret_cast<void**>(&zero[device]), 256);
@@ -89,6 +90,22 @@ hipError_t build_i8_twin(Layer& L) {
   r = launch_i8_twin(L.W, L.n, L.m, L.Wq, L.wscale, nullptr);
   if (r == hipSuccess) r = hipStreamSynchronize(nullptr);
   if (r != hipSuccess && fresh) { L.Wq.reset(); L.wscale.reset(); }
+  return r;
+}
+
+void free_mx_twin(Layer& L) { L.Mq.reset(); L.Me.reset(); L.Mbad.reset(); }
+
+hipError_t build_mx_twin(Layer& L) {
+  const bool fresh = !L.Mq;
+  hipError_t r = hipSuccess;
+  if (fresh) {
+    const size_t kpad = (size_t)mx_kpad(L.n);
+    if ((r = L.Mq.alloc((size_t)L.m * kpad)) == hipSuccess && (r = L.Me.alloc((size_t)L.m * (kpad / 32))) == hipSuccess)
+      r = L.Mbad.alloc(mx_flags(L.m));
+  }
+  if (r == hipSuccess) r = launch_mx_twin(L.W, L.n, L.m, L.Mq, L.Me, L.Mbad, nullptr);
+  if (r == hipSuccess) r = hipStreamSynchronize(nullptr);
+  if (r != hipSuccess && fresh) free_mx_twin(L);
   return r;
 }
 
@@ -619,6 +636,14 @@ int32_t drs_set_fc(drs_handle e, int32_t mlp, int32_t layer, const float* h_W, c
     L.Wq.reset(); L.wscale.reset();
     return fail(e, DRS_ERR_OOM, "no room for the int8 twin of the %dx%d layer", n, m);
   }
+  // ... and an MXFP8 layer ("mlp_mxfp8" 1) its MX twin, likewise
+  const bool twinx = L.packed && mx_shape(e, n, m);
+  if (twinx && !L.Mq && (L.Mq.alloc((size_t)m * mx_kpad(n)) != hipSuccess || L.Me.alloc((size_t)m * (mx_kpad(n) / 32)) != hipSuccess ||
+                         L.Mbad.alloc(mx_flags(m)) != hipSuccess)) {
+    (void)hipGetLastError();
+    free_mx_twin(L);
+    return fail(e, DRS_ERR_OOM, "no room for the MXFP8 twin of the %dx%d layer", n, m);
+  }
   HIP_TRY(e, hipMemcpy(L.W, h_W, sizeof(float) * (size_t)m * n, hipMemcpyHostToDevice));
   HIP_TRY(e, hipMemcpy(L.b, h_b, sizeof(float) * (size_t)m, hipMemcpyHostToDevice));
   if (L.packed) {
@@ -629,6 +654,7 @@ int32_t drs_set_fc(drs_handle e, int32_t mlp, int32_t layer, const float* h_W, c
   L.m = m; L.n = n; L.set = true;
   if (twin) HIP_TRY(e, build_bf16_twin(L));
   if (twin8) HIP_TRY(e, build_i8_twin(L));
+  if (twinx) HIP_TRY(e, build_mx_twin(L));
   return DRS_OK;
 }
 

@@ -27,6 +27,19 @@ bool is_bf16(const drs_engine* e, const Mlp& m, int l) { return bf16_shape(e, m.
 // "mlp_int8" 1: layer l of m runs on the int8 matrix cores, always as a launch of its own (gemm_i8.hip)
 bool is_i8(const drs_engine* e, const Mlp& m, int l) { return i8_shape(e, m.ln[l], m.ln[l + 1]); }
 
+// "mlp_mxfp8" 1: layer l of m runs in MXFP8 on the block-scaled matrix cores, always as a launch of its own (gemm_mxfp8.hip)
+bool is_mx(const drs_engine* e, const Mlp& m, int l) { return mx_shape(e, m.ln[l], m.ln[l + 1]); }
+
+// the narrow twin layer l of m runs from under the handle's options (plan_layer): at most one family, by the layer's shape
+Twins twins_of(const drs_engine* e, const Mlp& m, int l) {
+  const Layer& L = m.layers[l];
+  Twins t;
+  if (is_bf16(e, m, l)) t.wb = L.Wb;
+  if (is_i8(e, m, l)) { t.wq = L.Wq; t.wsc = L.wscale; }
+  if (is_mx(e, m, l)) { t.mq = L.Mq; t.me = L.Me; t.mbad = L.Mbad; }
+  return t;
+}
+
 void fill_chain(ChainArgs& c, const Mlp& m, int l0, int cnt, const float* x, int64_t ldx, int64_t M,
                 float* y, int64_t ldy) {
   memset(&c, 0, sizeof c);
@@ -66,7 +79,8 @@ hipError_t rejoin_stream(drs_engine* e, Slot& s) {
 }
 
 
-// Run all layers of `m` on x -> y.  A huge layer, a bf16 layer ("mlp_dtype" 2) and an int8 layer ("mlp_int8" 1) run as their own 2-D launch; runs of
+// Run all layers of `m` on x -> y.  A huge layer, a bf16 layer ("mlp_dtype" 2), an int8 layer ("mlp_int8" 1) and an MXFP8 layer
+// ("mlp_mxfp8" 1) run as their own 2-D launch; runs of
 // ordinary layers between them are fused into one LDS-resident chain.  Segment outputs that are not
 // the final one ping-pong between s.H and s.Hb.  first (optional): the caller's plan of layer 0 alone.
 int32_t run_mlp(drs_engine* e, Slot& s, const Mlp& m, const float* x, int64_t ldx, int64_t M, float* y, int64_t ldy,
@@ -85,15 +99,14 @@ int32_t run_mlp(drs_engine* e, Slot& s, const Mlp& m, const float* x, int64_t ld
       const XSrc* x0 = l0 == 0 ? xs : nullptr;
       if (!n)
         return plan_layer(in, ldin, M, m.ln[l0], m.layers[l0].W, m.layers[l0].b, m.ln[l0 + 1], act_of(m, l0), out, ldo,
-                          e->tune, d, x0, &own, is_bf16(e, m, l0) ? m.layers[l0].Wb : nullptr,
-                          is_i8(e, m, l0) ? m.layers[l0].Wq : nullptr, m.layers[l0].wscale);
+                          e->tune, d, x0, &own, twins_of(e, m, l0));
       ChainArgs c;
       fill_chain(c, m, l0, n, in, ldin, M, out, ldo);
       return plan_chains(c, nullptr, e->tune, d, x0, nullptr, nullptr, &own);
     };
     const bool given = l0 == 0 && first;
     cnt = 0;
-    auto alone = [&](int l) { return is_wide(e, m, l) || is_bf16(e, m, l) || is_i8(e, m, l); };
+    auto alone = [&](int l) { return is_wide(e, m, l) || is_bf16(e, m, l) || is_i8(e, m, l) || is_mx(e, m, l); };
     if (!given && !alone(l0))
       while (l0 + cnt < n_layers && cnt < DRS_MAX_CHAIN && !alone(l0 + cnt)) ++cnt;
     while (cnt > 0 && !plan(cnt)) --cnt;   // the longest run that a chain kernel holds, else the layer alone
@@ -109,8 +122,8 @@ int32_t run_mlp(drs_engine* e, Slot& s, const Mlp& m, const float* x, int64_t ld
   return DRS_OK;
 }
 
-// What a one-launch form asks of an MLP's layers: none wide and none an int8 layer ("mlp_int8" 1: no one-launch form holds
-// one, so `wide` covers them); under "mlp_dtype" 2 which are bf16 layers, each with its twin.
+// What a one-launch form asks of an MLP's layers: none wide and none an int8 or MXFP8 layer ("mlp_int8" 1, "mlp_mxfp8" 1: no
+// one-launch form holds one, so `wide` covers them); under "mlp_dtype" 2 which are bf16 layers, each with its twin.
 struct LayerScan {
   bool wide = false, bf16 = false, twins = true;
   const uint16_t* wb[DRS_MAX_CHAIN] = {};   // per layer its bf16 twin (a bf16 layer) or null
@@ -118,7 +131,7 @@ struct LayerScan {
 LayerScan scan_layers(const drs_engine* e, const Mlp& m) {
   LayerScan r;
   for (int l = 0; l < (int)m.layers.size() && l < DRS_MAX_CHAIN; ++l) {
-    r.wide = r.wide || is_wide(e, m, l) || is_i8(e, m, l);
+    r.wide = r.wide || is_wide(e, m, l) || is_i8(e, m, l) || is_mx(e, m, l);
     if (!is_bf16(e, m, l)) continue;
     r.bf16 = true;
     r.twins = r.twins && (r.wb[l] = m.layers[l].Wb);
@@ -516,9 +529,10 @@ static int32_t mlp_dense(SetCtx& x) {
   } else {
     // W&D / MT-WnD: Concat(dense, pooled embeddings) feeds the first top layer.  When that layer goes to a GEMM form
     // that can read a split row ("gemm_split", gemm_plan) it takes the dense columns from the queries' own arrays;
-    // otherwise the dense rows are copied in front of the embeddings first (so does a bf16 or an int8 first layer:
-    // gemm_bf16_kernel and gemm_i8_kernel read whole rows).
-    if (e->gemm_split && !e->top.layers.empty() && is_wide(e, e->top, 0) && !is_bf16(e, e->top, 0) && !is_i8(e, e->top, 0)) {
+    // otherwise the dense rows are copied in front of the embeddings first (so does a bf16, an int8 or an MXFP8 first layer:
+    // gemm_bf16_kernel, gemm_i8_kernel and gemm_mxfp8_kernel read whole rows).
+    if (e->gemm_split && !e->top.layers.empty() && is_wide(e, e->top, 0) && !is_bf16(e, e->top, 0) && !is_i8(e, e->top, 0) &&
+        !is_mx(e, e->top, 0)) {
       XSrc xsp = x.xs;
       xsp.ksplit = e->m_den;
       // (the layer's output as run_mlp would place it: the model's output, or s.H ahead of further layers)
@@ -925,8 +939,21 @@ int32_t drs_fc(drs_handle e, const float* d_x, int64_t M, int32_t K, const float
     hipError_t r = launch_i8_twin(d_W, K, N, wq, wsc, s.stream);
     if (r != hipSuccess) return fail(e, DRS_ERR_HIP, "drs_fc: %s", hipGetErrorString(r));
   }
+  // "mlp_mxfp8" 1: an MXFP8 layer likewise -- codes, scale bytes and flags
+  DeviceBuf<uint8_t> mq, me, mbad;
+  if (M > 0 && mx_shape(e, K, N)) {
+    if (mq.alloc((size_t)N * mx_kpad(K)) != hipSuccess || me.alloc((size_t)N * (mx_kpad(K) / 32)) != hipSuccess ||
+        mbad.alloc(mx_flags(N)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(e, DRS_ERR_OOM, "drs_fc: no room for the MXFP8 twin of the %dx%d layer", K, N);
+    }
+    hipError_t r = launch_mx_twin(d_W, K, N, mq, me, mbad, s.stream);
+    if (r != hipSuccess) return fail(e, DRS_ERR_HIP, "drs_fc: %s", hipGetErrorString(r));
+  }
+  Twins tw;
+  tw.wb = wb; tw.wq = wq; tw.wsc = wsc; tw.mq = mq; tw.me = me; tw.mbad = mbad;
   hipError_t r = hipSuccess;
-  const bool ok = M <= 0 || plan_layer(d_x, K, M, K, d_W, d_b, N, act, d_y, N, e->tune, nullptr, nullptr, &p, wb, wq, wsc);
+  const bool ok = M <= 0 || plan_layer(d_x, K, M, K, d_W, d_b, N, act, d_y, N, e->tune, nullptr, nullptr, &p, tw);
   if (ok && M > 0) r = launch_plan(p, e->tune, s.stream);
   if (r == hipSuccess) r = hipStreamSynchronize(s.stream);
   if (!ok) return fail(e, DRS_ERR_HIP, "no kernel takes the %dx%d layer", K, N);

@@ -215,6 +215,8 @@ int32_t set_mlp_dtype(drs_engine* e, int64_t value) {
     return fail(e, DRS_ERR_UNSUPPORTED, "mlp_dtype %lld: the DIN and DIEN launches run their FC layers in fp32 only", (long long)value);
   if (value == DRS_MLP_BF16 && e->mlp_int8)
     return fail(e, DRS_ERR_UNSUPPORTED, "mlp_dtype %lld: the wide layers run in int8 (\"mlp_int8\" 1): set that to 0 first", (long long)value);
+  if (value == DRS_MLP_BF16 && e->mlp_mxfp8)
+    return fail(e, DRS_ERR_UNSUPPORTED, "mlp_dtype %lld: the wide layers run in MXFP8 (\"mlp_mxfp8\" 1): set that to 0 first", (long long)value);
   const int from = e->mlp_dtype;
   e->mlp_dtype = (int)value;
   std::vector<Layer*> built;
@@ -244,6 +246,8 @@ int32_t set_mlp_int8(drs_engine* e, int64_t value) {
     return fail(e, DRS_ERR_UNSUPPORTED, "mlp_int8 %lld: the DIN and DIEN launches run their FC layers in fp32 only", (long long)value);
   if (value && e->mlp_dtype == DRS_MLP_BF16)
     return fail(e, DRS_ERR_UNSUPPORTED, "mlp_int8 %lld: the wide layers run in bf16 (\"mlp_dtype\" 2): set that to 0 first", (long long)value);
+  if (value && e->mlp_mxfp8)
+    return fail(e, DRS_ERR_UNSUPPORTED, "mlp_int8 %lld: the wide layers run in MXFP8 (\"mlp_mxfp8\" 1): set that to 0 first", (long long)value);
   e->mlp_int8 = (int)value;
   std::vector<Layer*> built;
   hipError_t r = hipSuccess;
@@ -258,6 +262,34 @@ int32_t set_mlp_int8(drs_engine* e, int64_t value) {
     for (Layer* L : built) { L->Wq.reset(); L->wscale.reset(); }
     e->mlp_int8 = 0;
     return fail(e, r == hipErrorOutOfMemory ? DRS_ERR_OOM : DRS_ERR_HIP, "mlp_int8: the layers' int8 twins: %s", hipGetErrorString(r));
+  }
+  return DRS_OK;
+}
+
+int32_t set_mlp_mxfp8(drs_engine* e, int64_t value) {
+  // as set_mlp_int8: 1 builds the MX twin (codes, scale bytes, flags) of every layer already set that is an MXFP8 layer by
+  // its shape (mx_shape), layers set later get theirs in drs_set_fc; back to 0 the twins are freed.  All twins or none.
+  if (value == e->mlp_mxfp8) return DRS_OK;
+  if (e->kind == DRS_MODEL_DIN || e->kind == DRS_MODEL_DIEN)
+    return fail(e, DRS_ERR_UNSUPPORTED, "mlp_mxfp8 %lld: the DIN and DIEN launches run their FC layers in fp32 only", (long long)value);
+  if (value && e->mlp_dtype == DRS_MLP_BF16)
+    return fail(e, DRS_ERR_UNSUPPORTED, "mlp_mxfp8 %lld: the wide layers run in bf16 (\"mlp_dtype\" 2): set that to 0 first", (long long)value);
+  if (value && e->mlp_int8)
+    return fail(e, DRS_ERR_UNSUPPORTED, "mlp_mxfp8 %lld: the wide layers run in int8 (\"mlp_int8\" 1): set that to 0 first", (long long)value);
+  e->mlp_mxfp8 = (int)value;
+  std::vector<Layer*> built;
+  hipError_t r = hipSuccess;
+  for (Mlp* m : served_mlps(e))
+    for (Layer& L : m->layers) {
+      if (!value) { free_mx_twin(L); continue; }
+      if (r != hipSuccess || !L.set || L.Mq || !mx_shape(e, L.n, L.m)) continue;
+      if ((r = build_mx_twin(L)) == hipSuccess) built.push_back(&L);
+    }
+  if (r != hipSuccess) {
+    (void)hipGetLastError();
+    for (Layer* L : built) free_mx_twin(*L);
+    e->mlp_mxfp8 = 0;
+    return fail(e, r == hipErrorOutOfMemory ? DRS_ERR_OOM : DRS_ERR_HIP, "mlp_mxfp8: the layers' MXFP8 twins: %s", hipGetErrorString(r));
   }
   return DRS_OK;
 }
@@ -358,6 +390,10 @@ const OptDesc kOptions[] = {
     // never with "mlp_dtype" 2); "mlp_i8_tile": force a tile shape
     {"mlp_int8", 0, 1, nullptr, O_SYNC, [](drs_engine* e) -> int64_t { return e->mlp_int8; }, nullptr, set_mlp_int8},
     OPT("mlp_i8_tile", 0, 44, [](int64_t v) { return v == 0 || v == 44 || v == 22 || v == 12; }, 0, tune.i8_tile),
+    // 1: the same layers in MXFP8 -- fp8 e4m3 codes under one power-of-two scale per 32 k, scaled inside the matrix instruction
+    // (gemm_mxfp8.hip; never with "mlp_dtype" 2 or "mlp_int8" 1); "mlp_mx_tile": force a tile shape
+    {"mlp_mxfp8", 0, 1, nullptr, O_SYNC, [](drs_engine* e) -> int64_t { return e->mlp_mxfp8; }, nullptr, set_mlp_mxfp8},
+    OPT("mlp_mx_tile", 0, 44, [](int64_t v) { return v == 0 || v == 44 || v == 22 || v == 12; }, 0, tune.mx_tile),
     // streams, host side
     OPT("shared_stream", 0, 2, nullptr, O_SYNC | O_STREAMS, shared_stream),
     OPT("mlp_streams", 1, 8, nullptr, O_SYNC | O_STREAMS, mlp_streams),

@@ -527,7 +527,7 @@ hipError_t launch_plan(const MlpPlan& p, const Tune& tune, hipStream_t s) {
       "stream4_kernel<nsplit4>", "stream4_kernel<rows32,nsplit2>", "stream4_kernel<rows32,nsplit4>", "stream_kernel<packed>",
       "stream_kernel<packed,2cu>", "stream_kernel<lds>", "chain_kernel", "fc_kernel", "gemm_kernel", "gemm_kernel",
       "gemm32_kernel", "gemm32_kernel", "gemm32_kernel", "gemm_bf16_kernel", "fused_bf16_kernel", "fused_bf16_kernel<sum>",
-      "gemm_i8_kernel"};
+      "gemm_i8_kernel", "gemm_mxfp8_kernel"};
   const char* name = names[(int)p.form];
   const size_t lds = launch_lds(p);
   const int K = p.a.width[0], N = p.a.width[1];
@@ -540,7 +540,7 @@ hipError_t launch_plan(const MlpPlan& p, const Tune& tune, hipStream_t s) {
     log_launch(tune.log, "%s<%s,%d>[%u x %u wg, %dx%d]", name, p.vec ? "vec" : "scalar", p.kc, p.grid_x, p.grid_y, K, N);
   else if (p.form == MlpForm::fused_bf16 || p.form == MlpForm::fused_bf16_sum)
     log_launch(tune.log, "%s[%u wg, %d layers, %d bf16%s, %zu B lds]", name, p.grid_x, p.fa.n_layers, p.fa.n_bf16, p.fa.dot ? ", dot" : "", lds);
-  else if (p.form == MlpForm::gemm_bf16 || p.form == MlpForm::gemm_i8)
+  else if (p.form == MlpForm::gemm_bf16 || p.form == MlpForm::gemm_i8 || p.form == MlpForm::gemm_mxfp8)
     log_launch(tune.log, "%s<%dx%d%s>[%u x %u wg, %dx%d]", name, 32 * p.tm, 32 * p.tn, p.vec ? "" : ",scalar", p.grid_x, p.grid_y, K, N);
   else if (p.form == MlpForm::gemm32_split)
     log_launch(tune.log, "%s<%d,%d,sbase,split%d>[%u x %u wg, %dx%d]", name, p.tm, p.tn, p.xs.ksplit, p.grid_x, p.grid_y, K, N);
@@ -583,6 +583,8 @@ hipError_t launch_plan(const MlpPlan& p, const Tune& tune, hipStream_t s) {
       return launch_fused_bf16(p, s);
     case MlpForm::gemm_i8:
       return launch_gemm_i8(p, s);
+    case MlpForm::gemm_mxfp8:
+      return launch_gemm_mxfp8(p, s);
     case MlpForm::stream_packed: case MlpForm::stream_packed_2cu: case MlpForm::stream_lds:
       return launch_stream8(p, lds, s);
     default:

@@ -1,6 +1,6 @@
 // The MLP launch planners: which kernel form serves a launch and how its LDS is laid out.  Host code only -- no kernel
 // lives here; the kernels, their attributes and launch_plan are in mlp.hip, mlp_stream8.hip, mlp_stream4.hip and
-// mlp_fused_bf16.hip (gemm_plan / gemm_bf16_plan / gemm_i8_plan stay beside their kernels: they encode those kernels' tile shapes).
+// mlp_fused_bf16.hip (gemm_plan / gemm_bf16_plan / gemm_i8_plan / gemm_mxfp8_plan stay beside their kernels: they encode those kernels' tile shapes).
 //   plan_layer            one layer: a GEMM form, else fc_kernel
 //   plan_chains           one or two chains: a stream kernel (stream_plan), else chain_kernel (chain_plan)
 //   plan_fused_bf16       DLRM in one launch with its bf16 layers (fused_bf16_kernel)
@@ -468,19 +468,20 @@ void fused_grid(MlpPlan* p, MlpForm form) {
 }  // namespace
 
 // One layer: a GEMM form (gemm.hip) when the layer has one, else fc_kernel.  A split input row (XSrc::ksplit) is for
-// the GEMM forms only.  Wb: a bf16 layer ("mlp_dtype" 2) -- the bf16 GEMM form (gemm_bf16.hip) and no other.  Wq, wsc: an
-// int8 layer ("mlp_int8" 1) -- the int8 GEMM form (gemm_i8.hip) and no other.
+// the GEMM forms only.  tw (Twins, mlp_stream.h): a bf16 layer ("mlp_dtype" 2) -- the bf16 GEMM form (gemm_bf16.hip) and
+// no other; an int8 layer ("mlp_int8" 1) -- the int8 GEMM form (gemm_i8.hip) and no other; an MXFP8 layer ("mlp_mxfp8" 1) --
+// the MXFP8 GEMM form (gemm_mxfp8.hip) and no other.
 bool plan_layer(const float* x, int64_t ldx, int64_t M, int32_t K, const float* W, const float* b, int32_t N, int32_t act,
-                float* y, int64_t ldy, const Tune& tune, const Done* done, const XSrc* xs, MlpPlan* p, const uint16_t* Wb,
-                const int8_t* Wq, const float* wsc) {
+                float* y, int64_t ldy, const Tune& tune, const Done* done, const XSrc* xs, MlpPlan* p, const Twins& tw) {
   memset(p, 0, sizeof *p);
   if (done) p->done = *done;
   if (xs) p->xs = *xs;
   ChainArgs& L = p->a;
   L.x = x; L.ldx = ldx; L.M = M; L.n_layers = 1; L.width[0] = K; L.width[1] = N;
   L.W[0] = W; L.b[0] = b; L.act[0] = act; L.y = y; L.ldy = ldy;
-  if (Wb) { p->wb = Wb; return gemm_bf16_plan(tune, p); }
-  if (Wq) { p->wq = Wq; p->wsc = wsc; return gemm_i8_plan(tune, p); }
+  if (tw.wb) { p->wb = tw.wb; return gemm_bf16_plan(tune, p); }
+  if (tw.wq) { p->wq = tw.wq; p->wsc = tw.wsc; return gemm_i8_plan(tune, p); }
+  if (tw.mq) { p->mq = tw.mq; p->me = tw.me; p->mbad = tw.mbad; return gemm_mxfp8_plan(tune, p); }
   if (N >= 64 && K >= 64 && gemm_plan(tune, p)) return true;
   if (p->xs.ksplit > 0 || !pick_kc(K, 0, tune.mlp_kc, &p->kc, &p->nbuf)) return false;
   p->form = MlpForm::fc;

@@ -1,5 +1,5 @@
 // Shared by the MLP translation units (mlp_plan.hip: planning; mlp.hip: chain / fc kernels, launch_plan; mlp_stream8.hip:
-// stream_kernel; mlp_stream4.hip: stream4_kernel; mlp_fused_bf16.hip; gemm.hip, gemm_bf16.hip, gemm_i8.hip) and the engine: the launch
+// stream_kernel; mlp_stream4.hip: stream4_kernel; mlp_fused_bf16.hip; gemm.hip, gemm_bf16.hip, gemm_i8.hip, gemm_mxfp8.hip) and the engine: the launch
 // description a stream kernel receives, the plan of one MLP launch, the step-table flags, device helpers, the planners
 // and the launch functions each kernel translation unit exports.
 #pragma once
@@ -152,7 +152,8 @@ enum class MlpForm : int32_t {
   gemm_bf16,                                         // gemm_bf16_kernel (gemm_bf16.hip): a bf16 layer ("mlp_dtype" 2)
   fused_bf16,                                        // fused_bf16_kernel (mlp_fused_bf16.hip): DLRM in one launch with its bf16 layers ("mlp_bf16_fuse" 1)
   fused_bf16_sum,                                    // fused_bf16_sum_kernel (mlp_fused_bf16.hip): NCF's Sum + MLP branch + predictor likewise
-  gemm_i8                                            // gemm_i8_kernel (gemm_i8.hip): an int8 layer ("mlp_int8" 1)
+  gemm_i8,                                           // gemm_i8_kernel (gemm_i8.hip): an int8 layer ("mlp_int8" 1)
+  gemm_mxfp8                                         // gemm_mxfp8_kernel (gemm_mxfp8.hip): an MXFP8 layer ("mlp_mxfp8" 1)
 };
 // One MLP launch, decided once (mlp_plan.hip) and run as it stands (mlp.hip launch_plan).
 struct MlpPlan {
@@ -163,10 +164,11 @@ struct MlpPlan {
   XSrc xs;
   ChainArgs a, b;               // the chain(s) (b.n_layers 0: one); fc / GEMM forms: the layer as a one-layer chain a
   int kc, nbuf, lda, sld, vec;  // chain_kernel / fc_kernel: K chunk, staging buffers, preloaded input / slab ld, float4 loads
-  int tm, tn;                   // gemm_kernel<tm, tn> | gemm32_kernel<tm, tn> | gemm_bf16_kernel<tm, tn> | gemm_i8_kernel<tm, tn>
+  int tm, tn;                   // gemm_kernel<tm, tn> | gemm32_kernel<tm, tn> | gemm_bf16_kernel<tm, tn> | gemm_i8_kernel<tm, tn> | gemm_mxfp8_kernel<tm, tn>
   const uint16_t* wb;           // gemm_bf16: the layer's bf16 twin [N, bf16_kpad(K)]
   const int8_t* wq;             // gemm_i8: the layer's int8 twin [N, i8_kpad(K)] ...
   const float* wsc;             // ... and its weight scales [N]
+  const uint8_t *mq, *me, *mbad;// gemm_mxfp8: the layer's MX twin -- e4m3 codes [N, mx_kpad(K)], E8M0 scale bytes [N, mx_kpad(K) / 32], non-finite flags [round_up(N, 4)]
   SArgs sa;                     // stream forms
   NSplit ns;
   FArgs fa;                     // fused_bf16, fused_bf16_sum
@@ -180,11 +182,17 @@ inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 // b (may be null) on the same rows, with the dot interaction or the summed input between them.  plan_layer: one layer.
 bool plan_chains(const ChainArgs& a, const ChainArgs* b, const Tune& tune, const Done* done, const XSrc* xs,
                  const DotArgs* dot, const SumArgs* sum, MlpPlan* p);
-// Wb (optional): the layer's bf16 twin -- the layer is a bf16 layer and takes the bf16 GEMM form or none; Wq, wsc (optional,
-// never beside Wb): its int8 twin and weight scales -- an int8 layer, the int8 GEMM form or none
+// The narrow twin of a layer's weights, at most one family of the three set (all null: an fp32 layer).  A set family says
+// what the layer is, and the layer takes that family's GEMM form or none.
+struct Twins {
+  const uint16_t* wb = nullptr;                                // a bf16 layer ("mlp_dtype" 2): its bf16 twin
+  const int8_t* wq = nullptr;                                  // an int8 layer ("mlp_int8" 1): its int8 twin ...
+  const float* wsc = nullptr;                                  // ... and weight scales
+  const uint8_t *mq = nullptr, *me = nullptr, *mbad = nullptr; // an MXFP8 layer ("mlp_mxfp8" 1): codes, scale bytes, non-finite flags
+};
 bool plan_layer(const float* x, int64_t ldx, int64_t M, int32_t K, const float* W, const float* b, int32_t N, int32_t act,
                 float* y, int64_t ldy, const Tune& tune, const Done* done, const XSrc* xs, MlpPlan* p,
-                const uint16_t* Wb = nullptr, const int8_t* Wq = nullptr, const float* wsc = nullptr);
+                const Twins& tw = Twins());
 // the launch of a plan, noted in the dispatch log (tune.log)
 hipError_t launch_plan(const MlpPlan& p, const Tune& tune, hipStream_t s);
 bool gemm_plan(const Tune& tune, MlpPlan* p);   // gemm.hip: the GEMM form of the layer p->a, if it has one
@@ -193,6 +201,8 @@ bool gemm_bf16_plan(const Tune& tune, MlpPlan* p);   // gemm_bf16.hip: the bf16 
 hipError_t launch_gemm_bf16(const MlpPlan& p, hipStream_t s);
 bool gemm_i8_plan(const Tune& tune, MlpPlan* p);     // gemm_i8.hip: the int8 GEMM form of the layer p->a with the twin p->wq, p->wsc
 hipError_t launch_gemm_i8(const MlpPlan& p, hipStream_t s);
+bool gemm_mxfp8_plan(const Tune& tune, MlpPlan* p);  // gemm_mxfp8.hip: the MXFP8 GEMM form of the layer p->a with the twin p->mq, p->me, p->mbad
+hipError_t launch_gemm_mxfp8(const MlpPlan& p, hipStream_t s);
 // fused_bf16_kernel (mlp_fused_bf16.hip): bottom chain a, the interaction (dot, or null: cat) and top chain b; wb_a / wb_b:
 // per layer its bf16 twin (a bf16 layer) or null (an fp32 layer).  false: the form does not take the launch.
 bool plan_fused_bf16(const ChainArgs& a, const ChainArgs& b, const uint16_t* const* wb_a, const uint16_t* const* wb_b,

@@ -47,8 +47,9 @@ def _table_dtype(args):
     return _TABLE_DTYPES[name]
 
 
-# ("int8" is a key of its own, "mlp_int8": the engine's "mlp_dtype" stays fp32 under it -- _mlp_int8)
-_MLP_DTYPES = {"fp32": N.MLP_FP32, "bf16": N.MLP_BF16, "int8": N.MLP_FP32}
+# ("int8" and "mxfp8" are keys of their own, "mlp_int8" and "mlp_mxfp8": the engine's "mlp_dtype" stays fp32 under them --
+# _mlp_int8, _mlp_mxfp8)
+_MLP_DTYPES = {"fp32": N.MLP_FP32, "bf16": N.MLP_BF16, "int8": N.MLP_FP32, "mxfp8": N.MLP_FP32}
 
 
 def _mlp_dtype(args):
@@ -63,6 +64,12 @@ def _mlp_int8(args):
     """--accel_mlp_dtype int8 -> the engine's "mlp_int8" value (0 for every other word)."""
     _mlp_dtype(args)
     return int(str(getattr(args, "accel_mlp_dtype", "fp32") or "fp32") == "int8")
+
+
+def _mlp_mxfp8(args):
+    """--accel_mlp_dtype mxfp8 -> the engine's "mlp_mxfp8" value (0 for every other word)."""
+    _mlp_dtype(args)
+    return int(str(getattr(args, "accel_mlp_dtype", "fp32") or "fp32") == "mxfp8")
 
 
 def _mlp_bf16_fuse(args):
@@ -354,6 +361,7 @@ class _HipNet(object):
         dtype = _table_dtype(a)
         mlp_dtype = _mlp_dtype(a)
         mlp_int8 = _mlp_int8(a)
+        mlp_mxfp8 = _mlp_mxfp8(a)
         bf16_fuse = _mlp_bf16_fuse(a)
         int8_lines = _table_int8_lines(a)
         int4_lines = _table_int4_lines(a)
@@ -385,6 +393,9 @@ class _HipNet(object):
             # --accel_mlp_dtype int8: the same place, the key "mlp_int8" (only when asked for, and no "mlp_dtype" with it)
             if mlp_int8:
                 eng.set_option("mlp_int8", mlp_int8)
+            # --accel_mlp_dtype mxfp8: likewise, the key "mlp_mxfp8"
+            if mlp_mxfp8:
+                eng.set_option("mlp_mxfp8", mlp_mxfp8)
             # --accel_mlp_bf16_fuse: behind it, and only when asked for
             if bf16_fuse:
                 eng.set_option("mlp_bf16_fuse", bf16_fuse)

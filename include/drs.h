@@ -326,6 +326,12 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  *                 holding a NaN or an infinity gives NaN; an output depends on its input row and weight row alone; the
  *                 operator-level FC call follows the handle; DLRM, W&D, MT-WnD and NCF only; refused while "mlp_dtype" is
  *                 2, which is refused while this is 1)   "mlp_i8_tile" 0|44|22|12
+ *                 "mlp_mxfp8" 0|1 (1: the FC layers with K >= 64 and N >= 64 in OCP MXFP8 on the block-scaled matrix cores --
+ *                 fp8 e4m3 codes under one power-of-two (E8M0) scale per 32 consecutive k of a row of the input or of the
+ *                 weights, the scales applied inside the matrix instruction, fp32 accumulation, y = act(sum + b); a row
+ *                 holding a NaN or an infinity gives NaN; an output depends on its input row and weight row alone; the
+ *                 operator-level FC call follows the handle; DLRM, W&D, MT-WnD and NCF only; refuses and is refused by
+ *                 "mlp_dtype" 2 and "mlp_int8" 1)   "mlp_mx_tile" 0|44|22|12
  *   streams, host "shared_stream" 0|1|2   "mlp_streams" 1..8   "host_threads" -1..64
  *                 "zero_copy_inputs" 1|2|3   "out_dma" bytes   "dispatch_log" 0|1
  *   table arena   "table_placement" -1|-2|k   "table_alloc" 0|1|2   "table_spacer" bytes
