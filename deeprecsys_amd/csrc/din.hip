@@ -724,19 +724,16 @@ __global__ __launch_bounds__(64 * NW, 2) void din_pipe_kernel(SlsArgs a, const f
   }
 }
 
-struct FusedShape { int S, C; };
-// Waves per workgroup.  FIXED for every launch size: it decides which units a lane group sums, i.e.
-// the association of the fp32 Sum over the units -- a query's bits must not depend on how many
-// queries were coalesced with it.  Measured on the din.json shape (254 tables, 3 lookups, D 32),
-// 2048 samples per launch: 4 waves x 4 samples 49 us, 8 x 2 54 us, 8 x 4 62 us, 4 x 2 52 us,
-// 4 x 1 63 us; one query (256 samples): 4 x 1 16 us, 8 x 1 12 us.
-constexpr int kWaves = 4;
-
+// (FusedShape, fused_shape, din_pipe_lds and kWaves -- waves per workgroup -- are declared in drs_internal.h: din_half.hip's
+// launch shares them.)
 // The pipelined form keeps kPipe units in flight per lane group.  Measured on din.json (12-query sets; one query):
 // S = 4: depth 2 -> 40.5 us alone; S = 2: depth 2 / 3 / 4 -> 46.5 / 45.8 / 46.5 us alone, 147.8 / 138.9 / 138.3 k queries/s
 // beside the MLP launches; S = 1 (one query): 2 / 4 / 6 -> 10.15 / 10.18 / 12.1 us.  The main phase already runs at
 // ~0.77 of the HBM peak: deeper does not help, more registers hurt (profiles/r05_din/).
 constexpr int kPipe = 2;
+
+}  // namespace
+
 size_t din_pipe_lds(int T, int S) { return (size_t)T * (8 + (size_t)S * 3 * 4); }
 
 // Samples per workgroup (the units' weights are read once per workgroup; fewer for small launches
@@ -750,8 +747,6 @@ FusedShape fused_shape(const SlsArgs& a, const Tune& tune) {
     if (a.uniform_len[i] < 0 || a.uniform_len[i] > 3) f.C = 4;
   return f;
 }
-
-}  // namespace
 
 hipError_t launch_din_pack(const float* const* att, float* packed, int32_t U, int32_t D, int32_t h, hipStream_t s) {
   hipLaunchKernelGGL(din_pack_kernel, dim3((unsigned)U), dim3(256), 0, s, att, packed, D, h, din_unit_stride(D, h));

@@ -330,9 +330,25 @@ hipError_t launch_din_pack(const float* const* att, float* packed, int32_t U, in
 hipError_t launch_din_attention(const float* T, int64_t ldt, int64_t M, int32_t Tn, int32_t D, int32_t h,
                                 const float* packed, float* R, int64_t ldr, hipStream_t stream);
 bool din_fused_applicable(int32_t D, int32_t h);
+// Waves per workgroup of the fused launches.  FIXED for every launch size: it decides which units a lane group sums, i.e.
+// the association of the fp32 Sum over the units -- a query's bits must not depend on how many
+// queries were coalesced with it.  Measured on the din.json shape (254 tables, 3 lookups, D 32),
+// 2048 samples per launch: 4 waves x 4 samples 49 us, 8 x 2 54 us, 8 x 4 62 us, 4 x 2 52 us,
+// 4 x 1 63 us; one query (256 samples): 4 x 1 16 us, 8 x 1 12 us.
+constexpr int kWaves = 4;
+// S: samples per workgroup of a fused launch; C: rows per bag covered per round (3: every bag has one fixed length <= 3)
+struct FusedShape { int S, C; };
+FusedShape fused_shape(const SlsArgs& a, const Tune& tune);
+size_t din_pipe_lds(int T, int S);   // the pipelined forms' staged table offsets and row numbers: T * (8 + 12 S) bytes
 int64_t din_fused_grid(const SlsArgs& a, const Tune& tune);
 hipError_t launch_din_fused(const SlsArgs& a, int32_t h, const float* packed, float* R, int64_t ldr,
                             const Tune& tune, hipStream_t stream, hipEvent_t stop);
+// The same launch over an fp16, bf16 or fp8 e4m3 arena ("din_table_dtype"; din_half.hip din_pipe_narrow_kernel): the
+// pipelined form's shapes only -- din_narrow_applicable says whether it takes a launch set (h: the units' hidden width;
+// dtype: the arena's DRS_TABLE_*); every other set of such an engine runs launch_sls + launch_din_attention[_any].
+bool din_narrow_applicable(const SlsArgs& a, int32_t h, int dtype, const Tune& tune);
+hipError_t launch_din_narrow(const SlsArgs& a, int dtype, const float* packed, float* R, int64_t ldr,
+                             const Tune& tune, hipStream_t stream, hipEvent_t stop);
 
 // DIEN (dien.hip; models/dien.py:308-432).  w: 8 device pointers {i2h_w, i2h_b, gates_t_w, gates_t_b} of
 // layer 1 then layer 2; launch_dien_rnn: T [rows, Tn*D] pooled rows of the coalesced queries q ->

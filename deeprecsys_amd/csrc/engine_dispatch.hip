@@ -342,8 +342,12 @@ static int32_t launch_gather(SetCtx& x) {
   for (int i = 0; i < q.n_q; ++i) short_bags = short_bags && x.qb[i]->uniform_len >= 0 && x.qb[i]->uniform_len <= e->sls_short_bag;
   const SlsPlan plan = plan_sls(a, e->sls_exact, short_bags, e->tune, e->table_dtype);
   // DIN, default mode: the attention units are fused into the gather launch (din.hip)
+  // ... over an fp16 / bf16 / fp8 arena ("din_table_dtype") only where the narrow pipe form applies (din_half.hip); every
+  // other set of such an engine takes the two-launch form: the gather's instance of the type, then the attention kernel
+  const bool din_narrow = e->kind == DRS_MODEL_DIN && e->table_dtype != DRS_TABLE_FP32;
   const bool din_fused = x.din_fused = e->kind == DRS_MODEL_DIN && !e->sls_exact && e->din_fused && !e->din_any &&
-                                       din_fused_applicable(e->D, e->att[0].ln[1]);
+                                       (din_narrow ? din_narrow_applicable(a, e->att[0].ln[1], e->table_dtype, e->tune)
+                                                   : din_fused_applicable(e->D, e->att[0].ln[1]));
   s.ts_blocks = prof ? (din_fused ? din_fused_grid(a, e->tune) : plan.grid) : 0;
   if (prof) {
     // algorithmic bytes of THIS launch (rows + int32 indices + length + pooled output
@@ -361,7 +365,9 @@ static int32_t launch_gather(SetCtx& x) {
   // pipelined mode: the event the MLP stream waits for is recorded by the gather dispatch itself
   // (hipExtLaunchKernel's stop event = the packet's completion signal): no marker packet sits
   // between consecutive gathers (a hipEventRecord there costs ~2 us per set)
-  if (din_fused)
+  if (din_fused && din_narrow)
+    HIP_TRY(e, launch_din_narrow(a, e->table_dtype, e->d_att_packed, s.R, e->ldR, e->tune, gstream, piped ? s.ev_sls : nullptr));
+  else if (din_fused)
     HIP_TRY(e, launch_din_fused(a, e->att[0].ln[1], e->d_att_packed, s.R, e->ldR, e->tune, gstream, piped ? s.ev_sls : nullptr));
   else
     HIP_TRY(e, launch_sls(a, plan, e->tune, gstream, piped ? s.ev_sls : nullptr));

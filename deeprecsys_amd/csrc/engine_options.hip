@@ -185,6 +185,20 @@ int32_t set_table_dtype(drs_engine* e, int64_t value) {
   return convert_tables(e, (int)value, value == DRS_TABLE_INT4_ROWWISE ? e->table_int4_lines : e->table_int8_lines);
 }
 
+int32_t set_din_table_dtype(drs_engine* e, int64_t value) {
+  // DIN's arena in fp16, bf16 or fp8 e4m3: "table_dtype"'s conversion (convert_tables: its rounding, its fp8 exponents, its
+  // 3/4-free-memory refusal -- and nothing changes when it fails), under a key of its own because "table_dtype" keeps
+  // refusing on DIN as it always has.  The fused launch over such an arena is din_half.hip's; the launch sets it does not
+  // cover take the gather's instances of the type and the attention kernels (engine_dispatch.hip launch_gather).  The
+  // rowwise types are not offered.
+  if (e->kind != DRS_MODEL_DIN) {
+    if (value == DRS_TABLE_FP32) return DRS_OK;
+    return fail(e, DRS_ERR_UNSUPPORTED, "din_table_dtype %lld: a DIN engine's option; the other models' tables take \"table_dtype\"", (long long)value);
+  }
+  if (value == e->table_dtype) return DRS_OK;
+  return convert_tables(e, (int)value, 0);
+}
+
 int32_t set_table_int8_lines(drs_engine* e, int64_t value) {
   // An int8 rowwise arena whose rows the option moves is laid out again (convert_tables: its refusals, and nothing changes
   // when it fails); any other arena only remembers the value for a later "table_dtype" 8 -- either order, the same arena.
@@ -413,6 +427,8 @@ const OptDesc kOptions[] = {
     OPT("table_alloc", 0, 2, nullptr, 0, table_alloc),
 #endif
     {"table_dtype", 0, 9, [](int64_t v) { return v <= DRS_TABLE_BF16 || v == DRS_TABLE_FP8_E4M3 || v == DRS_TABLE_INT8_ROWWISE || v == DRS_TABLE_INT4_ROWWISE; }, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_dtype; }, nullptr, set_table_dtype},
+    // DIN's arena: 0 fp32 | 1 fp16 | 2 bf16 | 4 fp8 e4m3 (din_half.hip); reads the arena's type, as "table_dtype" does
+    {"din_table_dtype", 0, 4, [](int64_t v) { return v <= DRS_TABLE_BF16 || v == DRS_TABLE_FP8_E4M3; }, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_dtype; }, nullptr, set_din_table_dtype},
     // an int8 rowwise arena keeps every row inside one 128-byte line: 128 / S rows to a line where S < 128 does not divide 128
     {"table_int8_lines", 0, 1, nullptr, O_SYNC, [](drs_engine* e) -> int64_t { return e->table_int8_lines; }, nullptr, set_table_int8_lines},
     // ... and an int4 rowwise arena: its rows are 36 bytes at D 64 (3 to a line), 20 at D 32 (6 to a line)

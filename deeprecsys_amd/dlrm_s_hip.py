@@ -47,6 +47,20 @@ def _table_dtype(args):
     return _TABLE_DTYPES[name]
 
 
+_DIN_TABLE_DTYPES = {k: _TABLE_DTYPES[k] for k in ("fp32", "fp16", "bf16", "fp8_e4m3")}
+
+
+def _din_table_dtype(args, kind):
+    """--accel_din_table_dtype -> the engine's "din_table_dtype" value (fp32 when the flag is absent).  The key is DIN's:
+    a model of another kind given a word other than fp32 is an error (its tables take --accel_table_dtype)."""
+    name = str(getattr(args, "accel_din_table_dtype", "fp32") or "fp32")
+    if name not in _DIN_TABLE_DTYPES:
+        raise ValueError("--accel_din_table_dtype %r: one of %s" % (name, ", ".join(_DIN_TABLE_DTYPES)))
+    if name != "fp32" and kind != N.MODEL_DIN:
+        raise ValueError("--accel_din_table_dtype %s: DIN's flag; this model's tables take --accel_table_dtype" % name)
+    return _DIN_TABLE_DTYPES[name]
+
+
 # ("int8" and "mxfp8" are keys of their own, "mlp_int8" and "mlp_mxfp8": the engine's "mlp_dtype" stays fp32 under them --
 # _mlp_int8, _mlp_mxfp8)
 _MLP_DTYPES = {"fp32": N.MLP_FP32, "bf16": N.MLP_BF16, "int8": N.MLP_FP32, "mxfp8": N.MLP_FP32}
@@ -338,6 +352,7 @@ class _HipNet(object):
         self._device = int(getattr(cli_args, "_drs_device", 0))
         self._table_init = getattr(cli_args, "accel_table_init", "numpy")
         self.tout = "prob_click"
+        _din_table_dtype(cli_args, self.kind)   # (--accel_din_table_dtype on a model other than DIN: refused here, at construction)
 
     # -- weights ------------------------------------------------------------------
     def _make_tables(self, m, ln_emb):
@@ -359,6 +374,7 @@ class _HipNet(object):
         n_stage = max(int(getattr(a, "num_batches", 0)), 1)
         max_batch = max(int(getattr(a, "max_mini_batch_size", 1)), int(getattr(a, "mini_batch_size", 1)), 1)
         dtype = _table_dtype(a)
+        din_dtype = _din_table_dtype(a, self.kind)
         mlp_dtype = _mlp_dtype(a)
         mlp_int8 = _mlp_int8(a)
         mlp_mxfp8 = _mlp_mxfp8(a)
@@ -386,6 +402,9 @@ class _HipNet(object):
             # forms (and "preferred_slots") for the element size, and every table write below is rounded on the device
             if dtype != N.TABLE_FP32:
                 eng.set_option("table_dtype", dtype)
+            # --accel_din_table_dtype: DIN's key for the same step, at the same place (only when asked for)
+            if din_dtype != N.TABLE_FP32:
+                eng.set_option("din_table_dtype", din_dtype)
             # --accel_mlp_dtype: the layers set below get their bf16 twins as they arrive (only when asked for: an fp32
             # engine is never told)
             if mlp_dtype != N.MLP_FP32:

@@ -70,6 +70,7 @@ EXTRA_FLAGS = [
     ("accel_device_offset", _I, 0),   # first GPU ordinal used by the accel engines
     ("accel_table_init", _S, "numpy"),  # "numpy": reference RNG stream | "device": counter-based fill
     ("accel_table_dtype", _S, "fp32"),  # element type the accel engines store the tables in: fp32 | fp16 | bf16 | int8_rowwise | int4_rowwise | fp8_e4m3 (sums stay fp32; fp8_e4m3: OCP e4m3 codes under one power-of-two scale per table, about 2 % rms element error)
+    ("accel_din_table_dtype", _S, "fp32"),  # DIN only: element type its accel engines store the tables in: fp32 | fp16 | bf16 | fp8_e4m3 (engine option "din_table_dtype"; --accel_table_dtype stays refused on DIN; any other model given a word other than fp32 is an error)
     ("accel_table_int8_lines", _I, 0),  # 1 with --accel_table_dtype int8_rowwise: no int8 row crosses a 128-byte line, rows packed 128 // S to a line (engine option "table_int8_lines"; same results)
     ("accel_sls_pool", _S, "sum"),    # how the accel engines pool an embedding bag: sum (SparseLengthsSum) | mean (SparseLengthsMean, torch's EmbeddingBag(mode="mean"): the fp32 sum / the bag's length; engine option "sls_pool")
     ("accel_sls_max", _I, 0),         # 1: the accel engines pool an embedding bag by its element-wise maximum (torch's EmbeddingBag(mode="max"): an empty bag is +0.0, NaN propagates; engine option "sls_max"; not with --accel_sls_pool mean or --accel_sls_weights)
@@ -98,7 +99,7 @@ def debugPrint(args, system_tag, message):
 
 
 # EXTRA_FLAGS that take one of a few words
-FLAG_CHOICES = {"accel_table_dtype": ("fp32", "fp16", "bf16", "int8_rowwise", "int4_rowwise", "fp8_e4m3"), "accel_mlp_dtype": ("fp32", "bf16", "int8", "mxfp8"),
+FLAG_CHOICES = {"accel_table_dtype": ("fp32", "fp16", "bf16", "int8_rowwise", "int4_rowwise", "fp8_e4m3"), "accel_din_table_dtype": ("fp32", "fp16", "bf16", "fp8_e4m3"), "accel_mlp_dtype": ("fp32", "bf16", "int8", "mxfp8"),
                 "accel_mlp_bf16_fuse": (0, 1), "accel_table_int8_lines": (0, 1), "accel_table_int4_lines": (0, 1), "accel_sls_pool": ("sum", "mean"), "accel_sls_max": (0, 1),
                 "accel_sls_weights": ("none", "uniform"), "accel_sls_weighted_flat": (0, 1)}
 

@@ -344,6 +344,9 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  *                 relative element error: an explicit accuracy cost); every form sums the bits its fp32 twin sums on
  *                 the decoded table.  drs_fill_table_uniform takes the scale from max(|lo|, |hi|), not from the samples.
  *                 From an int8 / int4 rowwise arena 4 stays DRS_ERR_BAD_ARG: convert to 0, 1 or 2 first)
+ *                 "din_table_dtype" 0|1|2|4 (DIN engines only, whose arena "table_dtype" refuses to change: the same
+ *                 conversion to fp16, bf16 or fp8 e4m3 and the same bits as the fp32 twin on the upcast tables; any other
+ *                 value DRS_ERR_BAD_ARG; on another model kind a value other than 0 is DRS_ERR_UNSUPPORTED)
  *                 "table_int8_lines" 0|1 (1 with "table_dtype" 8: no int8 row crosses a 128-byte line -- 128 / S rows of
  *                 S = round_up(D, 8) + 8 bytes share a line where S < 128 does not divide 128; set before or after
  *                 "table_dtype", the same arena; same results)
