@@ -384,6 +384,12 @@ int32_t dien_top_kmax(int32_t n_layers, const int32_t* widths);
 hipError_t launch_dien_rnn(const float* T, int64_t ldt, const QTable& q, int32_t Tn, int32_t D, int32_t H,
                            const float* packed, const float* const* w, int mfma, float* R, int64_t ldr,
                            hipStream_t stream, const DienTop* top = nullptr, const Done* done = nullptr);
+// "dien_bf16" 1 (dien_bf16.hip dien_rnn_bf16_kernel): the same recurrence with bf16 operands, exact products and fp32
+// accumulation on v_mfma_f32_16x16x32_bf16, reading the row-major fp32 weights w[8]; R as above, the last state in fp32.
+// Instances: dien_applicable's shapes with H % 16 == 0.
+bool dien_bf16_applicable(int32_t D, int32_t H);
+hipError_t launch_dien_rnn_bf16(const float* T, int64_t ldt, const QTable& q, int32_t Tn, int32_t D, int32_t H,
+                                const float* const* w, float* R, int64_t ldr, hipStream_t stream);
 
 // Weights of one FC layer (W [N, K] row-major) in the stream kernel's MFMA-operand order (mlp.hip):
 // per 128-column pass and 64-k chunk, per wave (16 columns), four float4 per lane.

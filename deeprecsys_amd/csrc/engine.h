@@ -273,6 +273,7 @@ struct drs_engine {
   int dien_fuse_top = 1;         // DIEN: the top MLP inside the recurrence's launch when it fits (dien.hip dien_top_fusable)
   int dien_mfma = 2;             // DIEN recurrence on the matrix cores, 16 samples per workgroup: 2 = one wave set per layer | 1 = every wave both layers | 0 one wave per sample (VALU) | 3 the any-shape form (din_any.hip)
   int din_fused = 1;             // gather + attention units + Concat in one launch (default mode)
+  int dien_bf16 = 0;             // DIEN: the recurrence's products in bf16 on the matrix cores (dien_bf16.hip); "dien_mfma" and "dien_fuse_top" are then ignored
   std::vector<Mlp> rnn;          // DIEN: the two BasicRNN layers, each {i2h, gates_t}; packed into d_att_packed
   DeviceBuf<float> w_arena;      // all FC weights + biases in ONE allocation (large pages: the
   size_t w_arena_floats = 0;     // MLP kernels' per-CU TLBs then hold every weight page)

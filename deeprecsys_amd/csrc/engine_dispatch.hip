@@ -418,6 +418,13 @@ static int32_t mlp_dien(SetCtx& x) {
   memset(&tp, 0, sizeof tp);
   const int nt = (int)e->top.layers.size();
   // 3: the any-shape form (din_any.hip) -- every shape without an instance in dien.hip, or on request
+  if (e->dien_bf16) {
+    // "dien_bf16" 1: always dien_bf16.hip's kernel (the option is refused where it has no instance); the top MLP follows
+    // in fp32 as a launch of its own
+    log_launch(e->tune.log, "dien_rnn_bf16_kernel<%d,%d>[%d wg]", e->D, Hh, (c + 15) / 16);
+    HIP_TRY(e, launch_dien_rnn_bf16(s.T, e->ldT, x.q, e->T, e->D, Hh, rw, s.R, e->ldR, s.stream));
+    return run_mlp(e, s, e->top, s.R, e->ldR, x.Mv, x.out, e->n_out, x.dp);
+  }
   const int form = dien_applicable(e->D, Hh) ? e->dien_mfma : 3;
   const bool mfma_form = form != 3 && form && Hh % 16 == 0;
   if (e->dien_fuse_top && mfma_form && nt >= 1 && nt <= 4 && e->top.layers[0].packed &&

@@ -308,6 +308,22 @@ int32_t set_mlp_mxfp8(drs_engine* e, int64_t value) {
   return DRS_OK;
 }
 
+int32_t set_dien_bf16(drs_engine* e, int64_t value) {
+  // 1: the two recurrent layers run in dien_bf16.hip's arithmetic (bf16 operands, fp32 accumulation).  One field that every
+  // later launch reads: the kernel packs its operands from the fp32 weights itself, nothing is converted or allocated.
+  // A DIEN engine's option, and only where the kernel has an instance -- no other form computes this arithmetic.
+  if (e->kind != DRS_MODEL_DIEN) {
+    if (!value) return DRS_OK;
+    return fail(e, DRS_ERR_UNSUPPORTED, "dien_bf16 %lld: a DIEN engine's option", (long long)value);
+  }
+  const int H = e->rnn[0].ln[1];
+  if (value && !dien_bf16_applicable(e->D, H))
+    return fail(e, DRS_ERR_UNSUPPORTED, "dien_bf16 %lld: no bf16 recurrence for D = %d, H = %d (D in {16, 32, 64}, H in {16, 32, 64})",
+                (long long)value, e->D, H);
+  e->dien_bf16 = (int)value;
+  return DRS_OK;
+}
+
 // "sls_weighted": staged batches that carry per-sample weights (drs_stage_batch_weights)
 int64_t weighted_batches(drs_engine* e) {
   return (int64_t)std::count_if(e->batches.begin(), e->batches.end(), [](const Batch& b) { return b.staged && b.weighted; });
@@ -379,6 +395,8 @@ const OptDesc kOptions[] = {
     OPT("din_nt", 0, 1, nullptr, O_BOOL, tune.din_nt),
     OPT("dien_mfma", 0, 3, nullptr, 0, dien_mfma),
     OPT("dien_fuse_top", 0, 1, nullptr, 0, dien_fuse_top),
+    // 1: DIEN's recurrence with bf16 operands on v_mfma_f32_16x16x32_bf16 (dien_bf16.hip); "dien_mfma" and "dien_fuse_top" are then ignored
+    {"dien_bf16", 0, 1, nullptr, O_SYNC, [](drs_engine* e) -> int64_t { return e->dien_bf16; }, nullptr, set_dien_bf16},
     // MLP side
     OPT("gemm_split", 0, 1, nullptr, O_BOOL, gemm_split),
     OPT("mlp_split", 0, 1, nullptr, O_BOOL, mlp_split),

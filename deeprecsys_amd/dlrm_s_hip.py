@@ -61,6 +61,17 @@ def _din_table_dtype(args, kind):
     return _DIN_TABLE_DTYPES[name]
 
 
+def _dien_bf16(args, kind):
+    """--accel_dien_bf16 -> the engine's "dien_bf16" value (0 when the flag is absent).  The key is DIEN's: a model of
+    another kind given 1 is an error."""
+    v = int(getattr(args, "accel_dien_bf16", 0) or 0)
+    if v not in (0, 1):
+        raise ValueError("--accel_dien_bf16 %r: 0 or 1" % (v,))
+    if v and kind != N.MODEL_DIEN:
+        raise ValueError("--accel_dien_bf16 1: DIEN's flag; this model has no recurrent layers")
+    return v
+
+
 # ("int8" and "mxfp8" are keys of their own, "mlp_int8" and "mlp_mxfp8": the engine's "mlp_dtype" stays fp32 under them --
 # _mlp_int8, _mlp_mxfp8)
 _MLP_DTYPES = {"fp32": N.MLP_FP32, "bf16": N.MLP_BF16, "int8": N.MLP_FP32, "mxfp8": N.MLP_FP32}
@@ -353,6 +364,7 @@ class _HipNet(object):
         self._table_init = getattr(cli_args, "accel_table_init", "numpy")
         self.tout = "prob_click"
         _din_table_dtype(cli_args, self.kind)   # (--accel_din_table_dtype on a model other than DIN: refused here, at construction)
+        _dien_bf16(cli_args, self.kind)         # (--accel_dien_bf16 1 on a model other than DIEN: likewise)
 
     # -- weights ------------------------------------------------------------------
     def _make_tables(self, m, ln_emb):
@@ -375,6 +387,7 @@ class _HipNet(object):
         max_batch = max(int(getattr(a, "max_mini_batch_size", 1)), int(getattr(a, "mini_batch_size", 1)), 1)
         dtype = _table_dtype(a)
         din_dtype = _din_table_dtype(a, self.kind)
+        dien_bf16 = _dien_bf16(a, self.kind)
         mlp_dtype = _mlp_dtype(a)
         mlp_int8 = _mlp_int8(a)
         mlp_mxfp8 = _mlp_mxfp8(a)
@@ -405,6 +418,9 @@ class _HipNet(object):
             # --accel_din_table_dtype: DIN's key for the same step, at the same place (only when asked for)
             if din_dtype != N.TABLE_FP32:
                 eng.set_option("din_table_dtype", din_dtype)
+            # --accel_dien_bf16 1: DIEN's recurrence in bf16 (only when asked for: an fp32 engine is never told)
+            if dien_bf16:
+                eng.set_option("dien_bf16", dien_bf16)
             # --accel_mlp_dtype: the layers set below get their bf16 twins as they arrive (only when asked for: an fp32
             # engine is never told)
             if mlp_dtype != N.MLP_FP32:

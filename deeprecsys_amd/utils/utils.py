@@ -78,6 +78,7 @@ EXTRA_FLAGS = [
     ("accel_sls_weights", _S, "none"),  # per-index weights of the staged input sets (SparseLengthsWeightedSum, EmbeddingBag(per_sample_weights=)): none | uniform (one fp32 weight in [0, 1) per index from a RandomState of its own seeded with numpy_rand_seed: indices and dense inputs stay what they are without the flag)
     ("accel_sls_weighted_flat", _I, 0),  # 1 with --accel_sls_weights: a weighted launch set takes the gather form its unweighted twin takes (flat, flat-coalesced, one-lookup; engine option "sls_weighted_flat") instead of the ring walk
     ("accel_mlp_dtype", _S, "fp32"),  # arithmetic of the wide FC layers (K, N >= 64) on the accel engines: fp32 | bf16 (bf16 operands, fp32 accumulation) | int8 (engine option "mlp_int8": int8 operands with per-row / per-channel scales, int32 accumulation) | mxfp8 (engine option "mlp_mxfp8": OCP MX, fp8 e4m3 operands under one power-of-two scale per 32 k, fp32 accumulation)
+    ("accel_dien_bf16", _I, 0),       # DIEN only, 1: the two recurrent layers run with bf16 operands and fp32 accumulation on the matrix cores (engine option "dien_bf16"; D in 16 | 32 | 64 and hidden_size in 16 | 32 | 64; any other model given 1 is an error)
     ("accel_mlp_bf16_fuse", _I, 0),   # 1 with --accel_mlp_dtype bf16: DLRM's bottom MLP + interaction + top MLP, and NCF's Sum + MLP branch + predictor, stay one launch, the bf16 layers inside it (engine option "mlp_bf16_fuse")
     ("accel_table_placements", _I, 12),  # places in HBM tried for the table arena at engine start (1 = wherever hipMalloc put it)
     ("accel_slots", _I, 0),           # launch sets in flight per accel engine; 0 = the engine's preference (3: gather | MLP | enqueue; MLP-bound models 6)
@@ -100,7 +101,7 @@ def debugPrint(args, system_tag, message):
 
 # EXTRA_FLAGS that take one of a few words
 FLAG_CHOICES = {"accel_table_dtype": ("fp32", "fp16", "bf16", "int8_rowwise", "int4_rowwise", "fp8_e4m3"), "accel_din_table_dtype": ("fp32", "fp16", "bf16", "fp8_e4m3"), "accel_mlp_dtype": ("fp32", "bf16", "int8", "mxfp8"),
-                "accel_mlp_bf16_fuse": (0, 1), "accel_table_int8_lines": (0, 1), "accel_table_int4_lines": (0, 1), "accel_sls_pool": ("sum", "mean"), "accel_sls_max": (0, 1),
+                "accel_mlp_bf16_fuse": (0, 1), "accel_dien_bf16": (0, 1), "accel_table_int8_lines": (0, 1), "accel_table_int4_lines": (0, 1), "accel_sls_pool": ("sum", "mean"), "accel_sls_max": (0, 1),
                 "accel_sls_weights": ("none", "uniform"), "accel_sls_weighted_flat": (0, 1)}
 
 

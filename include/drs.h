@@ -315,6 +315,9 @@ int32_t drs_interact_dot(drs_handle h, const float* d_T, int64_t B, int32_t F, i
  *                 0, the default: the ring walk or the any-width form)
  *                 "din_fused" 0|1   "din_pipe" 0|1   "din_s" 0|1|2|4   "din_nt" 0|1
  *                 "dien_mfma" 0|1|2|3   "dien_fuse_top" 0|1
+ *                 "dien_bf16" 0|1 (DIEN engines with D and hidden size in 16|32|64 only: the two recurrent layers with bf16
+ *                 operands and fp32 accumulation on the matrix cores; "dien_mfma" and "dien_fuse_top" are ignored under 1;
+ *                 1 is DRS_ERR_UNSUPPORTED on any other shape or model)
  *   MLP side      "mlp_fuse" 0|1   "mlp_split" 0|1   "mlp_wide_kn" n   "gemm_split" 0|1
  *                 "mlp_stream" 2|4   "mlp_stream_2cu" 0|1   "mlp_rows32" n
  *                 "mlp_nsplit" 0|2|4   "mlp_nsplit_rows" n   "mlp_gemm_tile" 0|22|12|21|11|214|322|321|312|311
